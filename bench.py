@@ -7,13 +7,15 @@ Workload (BASELINE.json configs[1]): 64 synthetic object grids per GPU, 0.2 m vo
 16->32->64->128), bf16 features, forward + backward + optimizer step.
 Metric: object-grids / second (whole job, all ranks).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU; tracklets (object grids) are sharded across ranks, the only
 collective is the gradient all-reduce over RCCL ("weak" scaling).  Rank 0 prints ONE JSON
-line with the contract fields plus "roofline" (dominant kernel, HIP-event timed inside
-the timed region) and "cpu_baseline" (the oracle port on one host core, bounded sample).
+line with the contract fields.  A plain run sets up, warms up, times the K steps and prints
+that line; --full adds "roofline" (dominant kernel, HIP-event timed in steps of its own),
+"cpu_baseline" (the oracle port on the host cores, bounded sample) and "also" (short runs of
+the other workloads and sizes).
 """
 import argparse
 import json
@@ -35,6 +37,7 @@ sys.path.insert(0, ROOT)
 
 GRIDS_PER_GPU = 64
 POINTS_PER_GRID = 2000
+DUMP_ROWS = 32768   # --dump-outputs: encoder output rows sampled (the 126 k rows of configs[1] in f32 would be 65 MB)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 # The roofline object is reported on the LONGEST convolution kernel of the step: every conv launch is bracketed with HIP
 # events (spconv.ops.KernelProbe, keyed family<kd,ncols>) and the key with the largest average launch time is the one
@@ -76,10 +79,16 @@ def parse():
     ap.add_argument('--warmup', type=int, default=None, help='untimed warm-up steps (default 20 / 10)')
     ap.add_argument('--grids', type=int, default=GRIDS_PER_GPU)
     ap.add_argument('--points', type=int, default=POINTS_PER_GRID)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='measure what the headline figure does not need as well: the roofline probe steps, the host cost '
+                         'of queueing one step, the CPU baseline and the short runs of the other workloads and sizes under '
+                         '"also" (--workload ococcnet: its CPU baseline)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='configs[1]: write what the last timed step computed to DIR/<name>.npy (float32 / float64)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-also', action='store_true',
-                    help='skip the short runs of the other workloads (ococcnet at 4 and 64 tracklets, sst) whose JSON lines '
-                         'the default run attaches under "also"')
+                    help='with --full: skip the short runs of the other workloads (ococcnet at 4 and 64 tracklets, sst) '
+                         'whose JSON lines are attached under "also"')
     ap.add_argument('--workload', default='submconv', choices=['submconv', 'ococcnet', 'sst', 'decode'],
                     help='submconv = BASELINE.json configs[1] (the quoted metric); ococcnet = configs[2]; sst = configs[4] per-GPU share')
     ap.add_argument('--tracklets', type=int, default=4)
@@ -100,6 +109,8 @@ def parse():
                     help='test hook: every rank saves its parameters (one flat f32 vector) to <path>.rank<r>.pt when the timed '
                          'steps are done, i.e. after exactly warmup + steps optimizer steps (tests/test_gpu_bench_ranks.py)')
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != 'submconv':
+        ap.error('--dump-outputs is implemented for the submconv workload (configs[1]) only')
     if args.steps is None:
         args.steps = 500 if args.workload == 'submconv' else 50
     if args.warmup is None:
@@ -111,6 +122,27 @@ def dump_params(args, rank, params):
     if args.dump_params:
         torch.cuda.synchronize()
         torch.save(torch.cat([p.detach().float().reshape(-1) for p in params]).cpu(), f'{args.dump_params}.rank{rank}.pt')
+
+
+def dump_outputs(path, out, params):
+    """What the last timed step computed, as .npy files (about 18 MB): the encoder output's active rows (a fixed-capacity
+    step also carries inert rows with -1 coordinates) in coordinate order -- per-channel sums over all of them, and the
+    features and coordinates of a fixed seeded sample of DUMP_ROWS of them -- and the parameters after the optimizer step."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    idx = out.indices.detach().cpu().numpy()
+    feats = out.features.detach().float().cpu().numpy()
+    keep = (idx >= 0).all(axis=1)
+    idx, feats = idx[keep], feats[keep]
+    order = np.lexsort(idx.T[::-1])
+    idx, feats = idx[order], feats[order]
+    sample = np.sort(np.random.default_rng(0).choice(len(idx), min(len(idx), DUMP_ROWS), replace=False))
+    arrays = {'features_sample': feats[sample], 'indices_sample': idx[sample].astype(np.float64),
+              'feature_channel_sums': feats.astype(np.float64).sum(axis=0),
+              'params': torch.cat([p.detach().float().reshape(-1) for p in params]).cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def host_cores(limit=16):
@@ -297,7 +329,7 @@ def bench_ococcnet(args, world, rank, dev):
                          # input-gradient GEMMs per tile: 2 x (60 x 512 + 2 x 512 x 1024 + 2 x 1024 x 1024) flop per query)
                          'per_kernel': {k: dict(v, frac=round(v['tflops'] / peak, 4)) for k, v in probe_summary(kprobe)[2].items()}},
             'cpu_baseline': None}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res['cpu_baseline'] = cpu_baseline_ococcnet(L)
         print(json.dumps(res), flush=True)
 
@@ -583,7 +615,8 @@ def conv_sweep(sizes=(256, 512)):
     here = os.path.abspath(__file__)
     out = {}
     for grids in sizes:
-        cmd = [sys.executable, here, '--grids', str(grids), '--steps', '20', '--warmup', '5', '--no-cpu-baseline', '--no-also']
+        cmd = [sys.executable, here, '--grids', str(grids), '--steps', '20', '--warmup', '5', '--full', '--no-cpu-baseline',
+               '--no-also']
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             line = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -655,7 +688,7 @@ def main():
         # that has ANY neighbour at an offset (the block masks), useful are the rulebook pairs
         over_issue = None
         rb = getattr(ref_out.indice_dict['subm1'][2], '_ococc', None)
-        if rb is not None and rb.tables.get((False, 'fwd'), (None, None))[1] is not None:
+        if args.full and rb is not None and rb.tables.get((False, 'fwd'), (None, None))[1] is not None:
             mask = rb.tables[(False, 'fwd')][1].to(torch.int64) & 0xffffffff
             active = int(((mask[:, None] >> torch.arange(27, device=mask.device)[None, :]) & 1).sum().item())
             over_issue = round(active * 16 / max(n_pairs, 1), 2)
@@ -811,7 +844,7 @@ def main():
 
     for _ in range(args.warmup):
         out = step()
-    if not use_graph:
+    if args.full and not use_graph:
         sp_ops.set_probe(probe)
     if world > 1:
         dist.barrier()
@@ -825,22 +858,25 @@ def main():
     dt = time.perf_counter() - t0
     sp_ops.set_probe(None)
     dump_params(args, rank, params)
-    # host cost of queueing one step on an idle device (one hipGraphLaunch, or the eager launch sequence): when it
-    # approaches ms_per_step the number above is the host's, not the GPU's
-    host_us = []
-    for _ in range(5):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, params)
+    if args.full:
+        # host cost of queueing one step on an idle device (one hipGraphLaunch, or the eager launch sequence): when it
+        # approaches ms_per_step the number above is the host's, not the GPU's
+        host_us = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            h0 = time.perf_counter()
+            step()
+            host_us.append((time.perf_counter() - h0) * 1e6)
         torch.cuda.synchronize()
-        h0 = time.perf_counter()
-        step()
-        host_us.append((time.perf_counter() - h0) * 1e6)
-    torch.cuda.synchronize()
-    host_us = sorted(host_us)[len(host_us) // 2]
-    if use_graph:
-        sp_ops.set_probe(probe)
-        for _ in range(min(args.steps, 20)):
-            eager_step()
-        torch.cuda.synchronize()
-        sp_ops.set_probe(None)
+        host_us = sorted(host_us)[len(host_us) // 2]
+        if use_graph:
+            sp_ops.set_probe(probe)
+            for _ in range(min(args.steps, 20)):
+                eager_step()
+            torch.cuda.synchronize()
+            sp_ops.set_probe(None)
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -848,22 +884,6 @@ def main():
 
     if rank == 0:
         n_vox = int(n_act)
-        sorted_used, sorted_over_issue = sorted_kernel_in_use()
-        # the longest convolution kernel of the step, and every other one beside it
-        per_kernel = {}
-        for key in probe.keys():
-            ms = probe.mean_ms(key)
-            if ms:
-                nbytes, what = conv_algorithmic_bytes(key, n_vox, n_pairs)
-                per_kernel[key] = {'avg_launch_ms': round(ms, 5), 'launches_timed': probe.count(key),
-                                   'algorithmic_bytes_per_launch': nbytes,
-                                   'frac': round(nbytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-        top = max(per_kernel, key=lambda k: per_kernel[k]['avg_launch_ms']) if per_kernel else None
-        kern_ms = per_kernel[top]['avg_launch_ms'] if top else None
-        alg_bytes, what = conv_algorithmic_bytes(top, n_vox, n_pairs) if top else (None, '')
-        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms else None
-        family = top.split('<')[0] if top else ''
-        kd_top, nc_top = (int(v) for v in top.split('<')[1].rstrip('>').split(',')) if top else (0, 0)
         res = {
             'metric': 'object-grids/sec (fwd+bwd)',
             'value': round(world * B * args.steps / dt, 1),
@@ -883,9 +903,28 @@ def main():
                             'channels 16-32-64-128, LN+GELU, bf16 features',
                 'grids_per_gpu': B, 'points_per_grid': P, 'active_voxels': n_vox,
                 'rulebook_pairs': n_pairs, 'parallelism': f'dp{world}', 'launch': graph_note,
-                'host_us_to_queue_one_step': round(host_us, 1),
             },
-            'roofline': {
+        }
+        wall = {'to_result_s': round(time.time() - T_START, 1)}
+        if args.full:
+            res['config']['host_us_to_queue_one_step'] = round(host_us, 1)
+            sorted_used, sorted_over_issue = sorted_kernel_in_use()
+            # the longest convolution kernel of the step, and every other one beside it
+            per_kernel = {}
+            for key in probe.keys():
+                ms = probe.mean_ms(key)
+                if ms:
+                    nbytes, what = conv_algorithmic_bytes(key, n_vox, n_pairs)
+                    per_kernel[key] = {'avg_launch_ms': round(ms, 5), 'launches_timed': probe.count(key),
+                                       'algorithmic_bytes_per_launch': nbytes,
+                                       'frac': round(nbytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+            top = max(per_kernel, key=lambda k: per_kernel[k]['avg_launch_ms']) if per_kernel else None
+            kern_ms = per_kernel[top]['avg_launch_ms'] if top else None
+            alg_bytes, what = conv_algorithmic_bytes(top, n_vox, n_pairs) if top else (None, '')
+            achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms else None
+            family = top.split('<')[0] if top else ''
+            kd_top, nc_top = (int(v) for v in top.split('<')[1].rstrip('>').split(',')) if top else (0, 0)
+            res['roofline'] = {
                 'kernel': ('%s<%d,%d> (SubMConv3d %d->%d %s: %s)' % (
                     KERNEL_NAMES.get(family, family), kd_top, nc_top, *((kd_top, nc_top, 'forward') if kd_top < nc_top
                                                                        else (nc_top, kd_top, 'input gradient')), what)) if top else None,
@@ -907,17 +946,15 @@ def main():
                 'timed_in': 'timed region' if not use_graph else
                             'eager steps after the timed graph replays, 8 back-to-back launches per event pair',
                 'per_kernel': per_kernel,
-            },
-        }
-        wall = {'to_result_s': round(time.time() - T_START, 1)}
-        if not args.no_cpu_baseline and world == 1:  # (rank 0 at N = 1 only: the other ranks would sit in the barrier)
-            t0 = time.time()
-            res['cpu_baseline'] = cpu_baseline(16, P, model)
-            wall['cpu_baseline_s'] = round(time.time() - t0, 1)
-        if world == 1 and not args.no_also:
-            t0 = time.time()
-            res['also'] = also_workloads()
-            wall['also_s'] = round(time.time() - t0, 1)
+            }
+            if not args.no_cpu_baseline and world == 1:  # (rank 0 at N = 1 only: the other ranks would sit in the barrier)
+                t0 = time.time()
+                res['cpu_baseline'] = cpu_baseline(16, P, model)
+                wall['cpu_baseline_s'] = round(time.time() - t0, 1)
+            if world == 1 and not args.no_also:
+                t0 = time.time()
+                res['also'] = also_workloads()
+                wall['also_s'] = round(time.time() - t0, 1)
         res['wall'] = wall
         print(json.dumps(res), flush=True)
     if world > 1:

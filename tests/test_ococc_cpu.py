@@ -132,18 +132,29 @@ def test_dense_voxel_centers_batched_matches_reference_golden():
     assert c0.shape == (0, 3) and b0.numel() == 0 and k0.numel() == 0
 
 
-_REF_CFG = '/root/reference/configs/ococc/ococcnet.py'
+def _reference_model_cfg():
+    """the model dict of the reference's own configs/ococc/ococcnet.py:17-181 as plain python evaluates it
+    (tests/golden/ococcnet_model_cfg.pkl, oracle/gen_golden_config.py: the pickle keeps the lists it shares)"""
+    import pickle
+    with open(os.path.join(os.path.dirname(__file__), 'golden', 'ococcnet_model_cfg.pkl'), 'rb') as f:
+        return pickle.load(f)
 
 
-@pytest.mark.skipif(not os.path.exists(_REF_CFG), reason='reference checkout absent (GPU box)')
-def test_verbatim_reference_config_builds_through_the_registry(gold):
+def test_verbatim_reference_config_builds_through_the_registry(gold, tmp_path):
     """The drop-in boundary itself: mmcv-free Config.fromfile on the reference's own
     configs/ococc/ococcnet.py:17-181 -> DETECTORS.build(cfg.model).  269 tensors / 66 553 173 parameters with the
     reference's names; the ``[[16, 32]] * 6`` aliasing of ococcnet.py:42-45,68-71 must not leak
-    into the model (an aliasing-preserving loader builds 66 927 378 parameters)."""
+    into the model (an aliasing-preserving loader builds 66 927 378 parameters).  The config file is written here from
+    the stored model dict, its six blocks sharing one rel_mlp_hidden_dims list as in the reference's file."""
+    raw = _reference_model_cfg()
+    dims = raw['roi_head']['bbox_head']['rel_mlp_hidden_dims']
+    assert len(dims) == 6 and all(d is dims[0] for d in dims)
+    cfg_file = tmp_path / 'ococcnet.py'
+    cfg_file.write_text('import pickle\nwith open(%r, "rb") as f:\n    model = pickle.load(f)\ndel f\n'
+                        % os.path.join(os.path.dirname(__file__), 'golden', 'ococcnet_model_cfg.pkl'))
     from objectcentricocccompletion_amd import config, heads, point_pool, roi_head  # noqa: F401 (register)
     from objectcentricocccompletion_amd.registry import DETECTORS
-    cfg = config.fromfile(_REF_CFG)
+    cfg = config.fromfile(str(cfg_file))
     assert cfg.model.type == 'TrackletDetectorOCC' and cfg.model.roi_head.type == 'TrackletRoIHeadOCC'
     model = DETECTORS.build(cfg.model)
     bh = model.roi_head.bbox_head
@@ -162,7 +173,7 @@ def test_verbatim_reference_config_builds_through_the_registry(gold):
     assert model.roi_head.train_cfg['rcnn_code_weights'] == [2.0, 2.0, 1.0, 1.0, 1.0, 1.0, 1.0]
     assert model.roi_head.test_cfg['iou_chunk_size'] == 10 and bh.occ_label_thresh == 0.4
     # building twice from one loaded config must give the same network (the reference mutates its config lists)
-    again = DETECTORS.build(config.fromfile(_REF_CFG).model)
+    again = DETECTORS.build(config.fromfile(str(cfg_file)).model)
     assert sum(p.numel() for p in again.parameters()) == 66553173
 
 

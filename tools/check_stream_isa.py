@@ -20,10 +20,11 @@ import os, re, subprocess, sys, tempfile
 
 here = os.path.dirname(os.path.abspath(__file__))
 src = os.path.join(here, '..', 'objectcentricocccompletion_amd', 'csrc', 'sparse_conv.hip')
-out = os.path.join(tempfile.gettempdir(), 'ococc_sparse_conv.s')
+out = os.path.join(tempfile.gettempdir(), f'ococc_sparse_conv_{os.getpid()}.s')
 subprocess.run(['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-S', '-x', 'hip', src, '-o', out,
                 '--cuda-device-only'], check=True, stderr=subprocess.DEVNULL)
 s = open(out).read()
+os.unlink(out)
 fail = 0
 for m in re.finditer(r'\n(_ZN12_GLOBAL__N_125gather_gemm_stream_kernel(\w+)):', s):
     a = m.end(); b = s.index('s_endpgm', a); body = s[a:b].split('\n')

@@ -3,13 +3,14 @@
 # HBM-side bytes per launch of ONE kernel of the configs[1] step (bench.py's graph replays and probe steps), collected as
 # MI355X_MICROARCH.md prescribes: FETCH_SIZE and WRITE_SIZE in separate bounded passes, FETCH_SIZE x 2 on gfx950.
 tag=$1; kern=$2; shift 2
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/pmc_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  timeout 200 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $out -o h$i -- python3 $GRAFT_REPO_ROOT/bench.py --no-also --no-cpu-baseline --steps 20 --warmup 5 "$@" > /dev/null 2>$out/herr$i.txt || echo "pass $i failed/timeout"
+  timeout 200 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $out -o h$i -- python3 $root/bench.py --full --no-also --no-cpu-baseline --steps 20 --warmup 5 "$@" > /dev/null 2>$out/herr$i.txt || echo "pass $i failed/timeout"
 done
 python3 - <<PY
 import csv, glob, collections, json

@@ -2,8 +2,8 @@
 
 usage: python tools/replay_table.py <kernel_trace.csv> [min_us]
 
-bench.py's default run = eager warm-up and probe launches + W + K replays of ONE captured graph + eager roofline-probe
-steps.  Only the replays are the timed region.  All kernels of one hipGraphLaunch carry the launch's correlation id, so a
+bench.py's run = eager warm-up launches + W + K replays of ONE captured graph (+ eager roofline-probe steps with
+--full).  Only the replays are the timed region.  All kernels of one hipGraphLaunch carry the launch's correlation id, so a
 replay is a correlation id with many dispatches; should the profiler number them one by one, the fallback finds the
 longest stretch of the trace in which the kernel-name sequence repeats with a fixed period.  The table averages over
 the replays only: its sum is <= the measured step (the span from a replay's first kernel start to its last kernel end

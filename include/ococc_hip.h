@@ -627,6 +627,40 @@ int ococc_window_attn_bwd_gather_bf16(const uint16_t* q, const uint16_t* k, cons
                                       uint16_t* dv, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
                                       ococc_stream_t stream);
 
+/* Dropout twins of the four calls above: nn.MultiheadAttention(dropout=dropout_p) as SST's WindowAttention builds it
+ * (mmdet3d/models/sst/sst_basic_block_v2.py:16-35, 79-81; CosineMultiheadAttention, cosine_msa.py:181-182, 431-433).
+ * Same arguments plus dropout_p in [0, 1) and seed, a device pointer to one uint64 (required when dropout_p > 0; read by
+ * the kernel, so a captured graph that redraws it draws a new mask per replay).  After the key mask and the softmax a
+ * probability is kept iff hash24(seed, head, query row, key row) >= floor(dropout_p * 2^24) and then scaled by
+ * 1 / (1 - dropout_p) in f32, rounded to bf16 as the P V operand; rows are token_index rows (gather forms) or
+ * window * max_tokens + slot (padded forms).  lse stays that of the undropped softmax; the backward regenerates the mask
+ * (dV = P_drop^T dO, dS = P o (keep dP / (1 - p) - delta), delta = dO . O).  dropout_p = 0: the calls above. */
+int ococc_window_attn_fwd_drop_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
+                                    int64_t k_stride, int64_t v_stride, const int32_t* key_len,
+                                    int64_t num_windows, int32_t max_tokens, int32_t num_heads, int32_t head_dim,
+                                    float scale, uint16_t* out, int64_t out_stride, float* lse, float dropout_p,
+                                    const uint64_t* seed, ococc_stream_t stream);
+int ococc_window_attn_bwd_drop_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
+                                    int64_t k_stride, int64_t v_stride, const uint16_t* out, const uint16_t* dout,
+                                    int64_t o_stride, const float* lse, const int32_t* key_len,
+                                    int64_t num_windows, int32_t max_tokens, int32_t num_heads, int32_t head_dim,
+                                    float scale, uint16_t* dq, uint16_t* dk, uint16_t* dv, int64_t dq_stride,
+                                    int64_t dk_stride, int64_t dv_stride, float dropout_p, const uint64_t* seed,
+                                    ococc_stream_t stream);
+int ococc_window_attn_fwd_gather_drop_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
+                                           int64_t k_stride, int64_t v_stride, const int32_t* token_index,
+                                           const int32_t* key_len, int64_t num_windows, int32_t max_tokens,
+                                           int32_t num_heads, int32_t head_dim, float scale, uint16_t* out,
+                                           int64_t out_stride, float* lse, float dropout_p, const uint64_t* seed,
+                                           ococc_stream_t stream);
+int ococc_window_attn_bwd_gather_drop_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
+                                           int64_t k_stride, int64_t v_stride, const uint16_t* out, const uint16_t* dout,
+                                           int64_t o_stride, const float* lse, const int32_t* token_index,
+                                           const int32_t* key_len, int64_t num_windows, int32_t max_tokens,
+                                           int32_t num_heads, int32_t head_dim, float scale, uint16_t* dq, uint16_t* dk,
+                                           uint16_t* dv, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
+                                           float dropout_p, const uint64_t* seed, ococc_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * B7, fused  one SST encoder layer as two tile kernels per direction
  * replaces EncoderLayer.forward (post-norm, mmdet3d/models/sst/sst_basic_block_v2.py:105-127):
@@ -692,6 +726,41 @@ int ococc_window_attn_block_bwd_saved_bf16(const uint16_t* x, const uint16_t* po
                                            const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag,
                                            const uint16_t* attn_saved, const float* lse_saved, uint16_t* dx, uint16_t* dqkv,
                                            uint16_t* dz, float* ln_partial, ococc_stream_t stream);
+/* Dropout twins of the four attention-block calls above (the attention of EncoderLayer with its reference default
+ * dropout=0.1: sst_basic_block_v2.py:79-81, 133 -> nn.MultiheadAttention(dropout=...) / CosineMultiheadAttention,
+ * cosine_msa.py:181-182).  Same arguments plus dropout_p in [0, 1) and seed (device uint64, required when dropout_p > 0).
+ * The mask is that of ococc_window_attn_*_drop_bf16 over the flat rows of tile_rows -- the gather kernels and these make
+ * the same decision for the same (seed, head, query row, key row).  lse_save stays the log-sum-exp of the undropped
+ * softmax; attn_save / attn_out is the dropped attention output (the out-projection's input).  dropout_p = 0: the calls
+ * above. */
+int ococc_window_attn_block_fwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
+                                          const int32_t* tile_span, int64_t num_tiles, int32_t d_model, int32_t num_heads,
+                                          const uint16_t* wqkv_frag, const float* bqkv, const uint16_t* wo_frag,
+                                          const float* bo, const float* ln_weight, const float* ln_bias, float eps,
+                                          uint16_t* y, float dropout_p, const uint64_t* seed, ococc_stream_t stream);
+int ococc_window_attn_block_bwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
+                                          const int32_t* tile_rows, const int32_t* tile_span, int64_t num_tiles,
+                                          int32_t d_model, int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
+                                          const uint16_t* wo_frag, const float* bo, const float* ln_weight, float eps,
+                                          const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag, uint16_t* dx,
+                                          uint16_t* dqkv, uint16_t* dz, uint16_t* attn_out, float* ln_partial,
+                                          float dropout_p, const uint64_t* seed, ococc_stream_t stream);
+int ococc_window_attn_block_train_fwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
+                                                const int32_t* tile_span, int64_t num_tiles, int32_t d_model,
+                                                int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
+                                                const uint16_t* wo_frag, const float* bo, const float* ln_weight,
+                                                const float* ln_bias, float eps, uint16_t* y, uint16_t* attn_save,
+                                                float* lse_save, float dropout_p, const uint64_t* seed,
+                                                ococc_stream_t stream);
+int ococc_window_attn_block_bwd_saved_drop_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
+                                                const int32_t* tile_rows, const int32_t* tile_span, int64_t num_tiles,
+                                                int32_t d_model, int32_t num_heads, const uint16_t* wqkv_frag,
+                                                const float* bqkv, const uint16_t* wo_frag, const float* bo,
+                                                const float* ln_weight, float eps, const uint16_t* wo_t_frag,
+                                                const uint16_t* wqkv_t_frag, const uint16_t* attn_saved,
+                                                const float* lse_saved, uint16_t* dx, uint16_t* dqkv, uint16_t* dz,
+                                                float* ln_partial, float dropout_p, const uint64_t* seed,
+                                                ococc_stream_t stream);
 int ococc_token_ffn_block_fwd_bf16(const uint16_t* x, int64_t num_tokens, int32_t d_model, int32_t d_ffn,
                                    const uint16_t* w1_frag, const float* b1, const uint16_t* w2_frag, const float* b2,
                                    const float* ln_weight, const float* ln_bias, float eps, int32_t act, uint16_t* y,

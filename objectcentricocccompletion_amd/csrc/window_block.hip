@@ -20,6 +20,13 @@
 // (flash-style), then runs the chain rule inside the tile, and writes the operands of the weight gradients
 // (dqkv, attention output, dz1 | act(h), dh, dz2) for ococc_token_wgrad_bf16.
 // No atomics anywhere: results are bit-reproducible.
+// Attention-probability dropout (nn.MultiheadAttention(dropout=p)) is a compile-time flag of the two attention-block
+// kernels: the softmax's probabilities are dropped and scaled by 1 / (1 - p) before their bf16 rounding as the P V
+// operand, by the hash of attn_dropout.hpp over (seed, head, flat query row, flat key row) -- the same decision the
+// per-window gather kernels of window_attn.hip make for the same pair; the backward regenerates it.  The log-sum-exp
+// stays that of the undropped softmax, the attention output (kept for the out-projection's weight gradient) is the
+// dropped one.  The DROP = false instantiations are the kernels without dropout.
+#include "attn_dropout.hpp"
 #include "common.hpp"
 #include "ln_math.hpp"
 
@@ -401,8 +408,11 @@ __device__ __forceinline__ void tile_range(const int tid_, const TileMeta* tm, i
 // madd: the lane's additive key mask (0 for a key of the query's window, -inf otherwise; slot [kt][r] = key 16 kt + 4 g + r),
 // the same for every head: the caller works it out once per query tile.  Scores are kept in base 2 (the 1 / sqrt(16)
 // scale times log2 e goes into one fused multiply-add with the mask), so that an exponential is v_sub + v_exp.
+// DROP: rows = the tile's flat rows, dstate = ococc_drop_head_state(seed, h).
+template <bool DROP>
 __device__ __forceinline__ f32x4 attn_head_fwd(const int tid_, const uint16_t* qs, int h, int qt, int klo, int khi,
-                                               const f32x4 (&madd)[4], float& lse) {
+                                               const f32x4 (&madd)[4], float& lse, const int* rows = nullptr,
+                                               uint32_t dstate = 0, uint32_t drop_thr = 0, float drop_scale = 1.f) {
   const int lane = tid_ & 63, c = lane & 15, g = lane >> 4;
   const int q_ = c >> 2, p_ = c & 3;
   const uint16_t* qh = qs + h * HD;
@@ -444,11 +454,21 @@ __device__ __forceinline__ f32x4 attn_head_fwd(const int tid_, const uint16_t* q
   sum += __shfl_xor(sum, 32, 64);
   const float inv = sum > 0.f ? 1.f / sum : 0.f;
   lse = sum > 0.f ? (m + __log2f(sum)) * 0.69314718055994530942f : 0.f;   // natural units, as the backward reads it
+  if (DROP) {   // P <- keep ? P / (1 - p) : 0 (f32), before its bf16 rounding as the P V operand
+    const uint32_t qrow = (uint32_t)rows[qt * 16 + c];
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+      if (kt >= klo && kt <= khi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          s[kt][r] = ococc_drop_keep(dstate, qrow, (uint32_t)rows[kt * 16 + 4 * g + r], drop_thr)
+                         ? s[kt][r] * inv * drop_scale : 0.f;
+  }
   f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     if (2 * u + 1 >= klo && 2 * u <= khi) {
-      const bf16x8 pb = pack_tiles(s[2 * u] * inv, s[2 * u + 1] * inv);
+      const bf16x8 pb = DROP ? pack_tiles(s[2 * u], s[2 * u + 1]) : pack_tiles(s[2 * u] * inv, s[2 * u + 1] * inv);
       const uint16_t* a0 = vh + (32 * u + 4 * g + q_) * LDQ + 4 * p_;
       o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_pair(a0, a0 + 16 * LDQ), pb, o, 0, 0, 0);   // rows: d, col: query
     }
@@ -457,8 +477,9 @@ __device__ __forceinline__ f32x4 attn_head_fwd(const int tid_, const uint16_t* q
 }
 
 // all heads of the tile: wave w runs heads [w * 8 / NW, (w + 1) * 8 / NW); o -> os (row stride LDX), lse -> lse_s or null
-template <int NW>
-__device__ __forceinline__ void attn_tile_fwd(const int tid_, const TileMeta* tm, const uint16_t* qs, uint16_t* os, float* lse_s) {
+template <int NW, bool DROP>
+__device__ __forceinline__ void attn_tile_fwd(const int tid_, const TileMeta* tm, const uint16_t* qs, uint16_t* os, float* lse_s,
+                                              uint64_t seed = 0, uint32_t drop_thr = 0, float drop_scale = 1.f) {
   const int lane = tid_ & 63, wave = tid_ >> 6, c = lane & 15, g = lane >> 4;
   for (int qt = 0; qt < 4; ++qt) {
     int klo, khi;
@@ -477,7 +498,9 @@ __device__ __forceinline__ void attn_tile_fwd(const int tid_, const TileMeta* tm
     for (int hh = 0; hh < NH / NW; ++hh) {
       const int h = (NH / NW) * wave + hh;
       float lse;
-      const f32x4 o = attn_head_fwd(tid_, qs, h, qt, klo, khi, madd, lse);
+      const f32x4 o = DROP ? attn_head_fwd<true>(tid_, qs, h, qt, klo, khi, madd, lse, tm->rows,
+                                                 ococc_drop_head_state(seed, (uint32_t)h), drop_thr, drop_scale)
+                           : attn_head_fwd<false>(tid_, qs, h, qt, klo, khi, madd, lse);
       *(u32x2*)(os + (qt * 16 + c) * LDX + h * HD + 4 * g) = pack4(o);
       if (lse_s && g == 0) lse_s[h * TM + qt * 16 + c] = lse;
     }
@@ -495,13 +518,15 @@ constexpr int attn_lds() {
 constexpr int NW = 4;
 
 // Forward of the attention block.
+template <bool DROP>
 __global__ void __launch_bounds__(256, 2)
 window_attn_block_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pos,
                              const int32_t* __restrict__ tile_rows, const int32_t* __restrict__ tile_span,
                              int64_t num_tiles, const uint16_t* __restrict__ wqkv, const float* __restrict__ bqkv,
                              const uint16_t* __restrict__ wo, const float* __restrict__ bo,
                              const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps,
-                             uint16_t* __restrict__ y, uint16_t* __restrict__ o_save, float* __restrict__ lse_save) {
+                             uint16_t* __restrict__ y, uint16_t* __restrict__ o_save, float* __restrict__ lse_save,
+                             uint32_t drop_thr, float drop_scale, const uint64_t* __restrict__ drop_seed) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint16_t* xs = (uint16_t*)smem;                 // x | x + pos | attention output
   uint16_t* qs = xs + TM * LDX;                   // Q | K | V, then y staging
@@ -554,7 +579,8 @@ window_attn_block_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __r
             pv.fetch(pos, tms[(it & 1) ^ 1].rows, 0, 0);
           }
         });
-    attn_tile_fwd<NW>(tid_, tm, qs, xs, o_save ? lse_s : nullptr);   // o goes where x + pos was (its last reader was the Q | K GEMM)
+    attn_tile_fwd<NW, DROP>(tid_, tm, qs, xs, o_save ? lse_s : nullptr,   // o goes where x + pos was (its last reader was the Q | K GEMM)
+                            DROP ? *drop_seed : 0, drop_thr, drop_scale);
     TILE_BARRIER();
     if (o_save) {
       // training: the attention output and the softmax's log-sum-exp of every (token, head) leave for the backward kernel,
@@ -814,6 +840,7 @@ token_ffn_block_bwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __res
 // ---------------------------------------------------------------------------------------------------------------
 // Backward of the attention block.  In: x, pos, dy (gradient of y1).  Out: dx, and for the weight gradients dqkv
 // [*,384], o (attention output) [*,128], dz (gradient at the LN input) [*,128]; LN partial sums per workgroup.
+template <bool DROP>
 __global__ void __launch_bounds__(512, 2)
 window_attn_block_bwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pos,
                              const uint16_t* __restrict__ dy, const int32_t* __restrict__ tile_rows,
@@ -824,7 +851,8 @@ window_attn_block_bwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __r
                              const uint16_t* __restrict__ wqkvt, uint16_t* __restrict__ dx,
                              uint16_t* __restrict__ dqkv_out, uint16_t* __restrict__ dz_out,
                              uint16_t* __restrict__ o_out, float* __restrict__ ln_partial,
-                             const uint16_t* __restrict__ o_in, const float* __restrict__ lse_in) {
+                             const uint16_t* __restrict__ o_in, const float* __restrict__ lse_in,
+                             uint32_t drop_thr, float drop_scale, const uint64_t* __restrict__ drop_seed) {
   constexpr int NW = 8;                           // one head per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint16_t* xs = (uint16_t*)smem;                 // x | x + pos | o | dz1 | dO | dx staging
@@ -911,7 +939,7 @@ window_attn_block_bwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __r
       ov.stash(xs, LDX);
       lse_s[(tid_ & 7) * TM + (tid_ >> 3)] = lse_mine;
     } else {
-      attn_tile_fwd<NW>(tid_, tm, qs, xs, lse_s);
+      attn_tile_fwd<NW, DROP>(tid_, tm, qs, xs, lse_s, DROP ? *drop_seed : 0, drop_thr, drop_scale);
     }
     TILE_BARRIER();
     WSTAMP(it, 2);   // attention forward
@@ -968,6 +996,7 @@ window_attn_block_bwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __r
       const uint16_t* dh_ = xs + h * HD;            // dO of the head, row stride LDX
       float* lq = lse_s + h * TM;
       float* dl = red0 + wave * TM;                 // delta of the head's queries (red0 is free here)
+      const uint32_t dstate = DROP ? ococc_drop_head_state(*drop_seed, (uint32_t)h) : 0u;
       f32x4 gq[4], gk[4], gv[4];
 #pragma unroll
       for (int qt = 0; qt < 4; ++qt) {
@@ -995,8 +1024,11 @@ window_attn_block_bwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __r
               const int key = kt * 16 + 4 * g + r;
               const float p = (key >= lo && key < hi) ? __expf(sc[r] * 0.25f - lse_q) : 0.f;
               pT[kt][r] = p;
-              dpT[kt][r] = dp[r];
-              delta += p * dp[r];
+              dpT[kt][r] = dp[r];   // (dropout: the gradient of the undropped probability, keep dP / (1 - p))
+              if (DROP)
+                dpT[kt][r] = ococc_drop_keep(dstate, (uint32_t)tm->rows[qi], (uint32_t)tm->rows[key], drop_thr)
+                                 ? dp[r] * drop_scale : 0.f;
+              delta += p * dpT[kt][r];
             }
           }
         }
@@ -1048,8 +1080,14 @@ window_attn_block_bwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __r
             for (int r = 0; r < 4; ++r) {
               const int qi = qt * 16 + 4 * g + r;   // a query sees this key iff both sit in the same (non-empty) window
               const float p = (qi >= klo_ && qi < khi_) ? __expf(sc[r] * 0.25f - l4[r]) : 0.f;
-              pvv[qt][r] = p;
-              dsv[qt][r] = p * (dp[r] - d4[r]) * 0.25f;
+              if (DROP) {   // dV takes the dropped probabilities, dS the dropped dP
+                const bool kept = ococc_drop_keep(dstate, (uint32_t)tm->rows[qi], (uint32_t)tm->rows[kj], drop_thr);
+                pvv[qt][r] = kept ? p * drop_scale : 0.f;
+                dsv[qt][r] = p * ((kept ? dp[r] * drop_scale : 0.f) - d4[r]) * 0.25f;
+              } else {
+                pvv[qt][r] = p;
+                dsv[qt][r] = p * (dp[r] - d4[r]) * 0.25f;
+              }
             }
           }
         }
@@ -1480,8 +1518,11 @@ namespace {
 int attn_block_fwd(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows, const int32_t* tile_span,
                    int64_t num_tiles, int32_t d_model, int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
                    const uint16_t* wo_frag, const float* bo, const float* ln_weight, const float* ln_bias, float eps,
-                   uint16_t* y, uint16_t* attn_save, float* lse_save, ococc_stream_t stream) {
+                   uint16_t* y, uint16_t* attn_save, float* lse_save, float dropout_p, const uint64_t* seed,
+                   ococc_stream_t stream) {
   OCOCC_BLOCK_DIMS_OK(d_model, num_heads, FF);
+  OCOCC_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0, 1)");
+  OCOCC_REQUIRE(dropout_p == 0.f || seed, "dropout_p > 0 needs the device seed");
   OCOCC_REQUIRE(num_tiles >= 0, "bad sizes");
   if (num_tiles == 0) return OCOCC_OK;
   OCOCC_REQUIRE(x && tile_rows && tile_span && wqkv_frag && bqkv && wo_frag && bo && ln_weight && ln_bias && y,
@@ -1489,11 +1530,17 @@ int attn_block_fwd(const uint16_t* x, const uint16_t* pos, const int32_t* tile_r
   OCOCC_REQUIRE(aligned16(x) && aligned16(pos) && aligned16(y) && aligned16(wqkv_frag) && aligned16(wo_frag) &&
                     aligned16(bqkv) && aligned16(bo) && aligned16(ln_weight) && aligned16(ln_bias),
                 "buffers must be 16-byte aligned");
-  OCOCC_HIP(hipFuncSetAttribute((const void*)window_attn_block_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                attn_lds<4>()));
-  hipLaunchKernelGGL(window_attn_block_fwd_kernel, dim3((unsigned)block_grid(num_tiles, 2)), dim3(256), attn_lds<4>(),
-                     (hipStream_t)stream, x, pos, tile_rows, tile_span, num_tiles, wqkv_frag, bqkv, wo_frag, bo,
-                     ln_weight, ln_bias, eps, y, attn_save, lse_save);
+  const OcoccDrop dp = ococc_drop_params(dropout_p);
+  const void* kern = dp.thr ? (const void*)window_attn_block_fwd_kernel<true> : (const void*)window_attn_block_fwd_kernel<false>;
+  OCOCC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, attn_lds<4>()));
+  if (dp.thr)
+    hipLaunchKernelGGL(window_attn_block_fwd_kernel<true>, dim3((unsigned)block_grid(num_tiles, 2)), dim3(256), attn_lds<4>(),
+                       (hipStream_t)stream, x, pos, tile_rows, tile_span, num_tiles, wqkv_frag, bqkv, wo_frag, bo,
+                       ln_weight, ln_bias, eps, y, attn_save, lse_save, dp.thr, dp.scale, seed);
+  else
+    hipLaunchKernelGGL(window_attn_block_fwd_kernel<false>, dim3((unsigned)block_grid(num_tiles, 2)), dim3(256), attn_lds<4>(),
+                       (hipStream_t)stream, x, pos, tile_rows, tile_span, num_tiles, wqkv_frag, bqkv, wo_frag, bo,
+                       ln_weight, ln_bias, eps, y, attn_save, lse_save, dp.thr, dp.scale, seed);
   OCOCC_CHECK_LAUNCH();
   return OCOCC_OK;
 }
@@ -1505,7 +1552,7 @@ extern "C" int ococc_window_attn_block_fwd_bf16(const uint16_t* x, const uint16_
                                                 const uint16_t* wo_frag, const float* bo, const float* ln_weight,
                                                 const float* ln_bias, float eps, uint16_t* y, ococc_stream_t stream) {
   return attn_block_fwd(x, pos, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo, ln_weight,
-                        ln_bias, eps, y, nullptr, nullptr, stream);
+                        ln_bias, eps, y, nullptr, nullptr, 0.f, nullptr, stream);
 }
 
 extern "C" int ococc_window_attn_block_train_fwd_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
@@ -1517,7 +1564,7 @@ extern "C" int ococc_window_attn_block_train_fwd_bf16(const uint16_t* x, const u
   OCOCC_REQUIRE(num_tiles == 0 || (attn_save && lse_save && aligned16(attn_save) && aligned16(lse_save)),
                 "attn_save / lse_save: 16-byte aligned device buffers");
   return attn_block_fwd(x, pos, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo, ln_weight,
-                        ln_bias, eps, y, attn_save, lse_save, stream);
+                        ln_bias, eps, y, attn_save, lse_save, 0.f, nullptr, stream);
 }
 
 namespace {
@@ -1526,8 +1573,10 @@ int attn_block_bwd(const uint16_t* x, const uint16_t* pos, const uint16_t* dy, c
                    const float* bqkv, const uint16_t* wo_frag, const float* bo, const float* ln_weight, float eps,
                    const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag, uint16_t* dx, uint16_t* dqkv, uint16_t* dz,
                    uint16_t* attn_out, float* ln_partial, const uint16_t* attn_saved, const float* lse_saved,
-                   ococc_stream_t stream) {
+                   float dropout_p, const uint64_t* seed, ococc_stream_t stream) {
   OCOCC_BLOCK_DIMS_OK(d_model, num_heads, FF);
+  OCOCC_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0, 1)");
+  OCOCC_REQUIRE(dropout_p == 0.f || seed, "dropout_p > 0 needs the device seed");
   OCOCC_REQUIRE(num_tiles >= 0, "bad sizes");
   if (num_tiles == 0) return OCOCC_OK;
   OCOCC_REQUIRE(x && dy && tile_rows && tile_span && wqkv_frag && bqkv && wo_frag && bo && ln_weight && wo_t_frag &&
@@ -1539,11 +1588,19 @@ int attn_block_bwd(const uint16_t* x, const uint16_t* pos, const uint16_t* dy, c
                     aligned16(attn_out) && aligned16(wqkv_frag) && aligned16(wo_frag) && aligned16(wo_t_frag) &&
                     aligned16(wqkv_t_frag) && aligned16(bqkv) && aligned16(bo) && aligned16(ln_weight),
                 "buffers must be 16-byte aligned");
-  OCOCC_HIP(hipFuncSetAttribute((const void*)window_attn_block_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                attn_lds<8>()));
-  hipLaunchKernelGGL(window_attn_block_bwd_kernel, dim3((unsigned)block_grid(num_tiles, 1)), dim3(512), attn_lds<8>(),
-                     (hipStream_t)stream, x, pos, dy, tile_rows, tile_span, num_tiles, wqkv_frag, bqkv, wo_frag, bo,
-                     ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, attn_out, ln_partial, attn_saved, lse_saved);
+  const OcoccDrop dp = ococc_drop_params(dropout_p);
+  const void* kern = dp.thr ? (const void*)window_attn_block_bwd_kernel<true> : (const void*)window_attn_block_bwd_kernel<false>;
+  OCOCC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, attn_lds<8>()));
+  if (dp.thr)
+    hipLaunchKernelGGL(window_attn_block_bwd_kernel<true>, dim3((unsigned)block_grid(num_tiles, 1)), dim3(512), attn_lds<8>(),
+                       (hipStream_t)stream, x, pos, dy, tile_rows, tile_span, num_tiles, wqkv_frag, bqkv, wo_frag, bo,
+                       ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, attn_out, ln_partial, attn_saved, lse_saved,
+                       dp.thr, dp.scale, seed);
+  else
+    hipLaunchKernelGGL(window_attn_block_bwd_kernel<false>, dim3((unsigned)block_grid(num_tiles, 1)), dim3(512), attn_lds<8>(),
+                       (hipStream_t)stream, x, pos, dy, tile_rows, tile_span, num_tiles, wqkv_frag, bqkv, wo_frag, bo,
+                       ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, attn_out, ln_partial, attn_saved, lse_saved,
+                       dp.thr, dp.scale, seed);
   OCOCC_CHECK_LAUNCH();
   return OCOCC_OK;
 }
@@ -1558,7 +1615,8 @@ extern "C" int ococc_window_attn_block_bwd_bf16(const uint16_t* x, const uint16_
                                                 uint16_t* dqkv, uint16_t* dz, uint16_t* attn_out, float* ln_partial,
                                                 ococc_stream_t stream) {
   return attn_block_bwd(x, pos, dy, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo,
-                        ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, attn_out, ln_partial, nullptr, nullptr, stream);
+                        ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, attn_out, ln_partial, nullptr, nullptr, 0.f,
+                        nullptr, stream);
 }
 
 extern "C" int ococc_window_attn_block_bwd_saved_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
@@ -1573,7 +1631,60 @@ extern "C" int ococc_window_attn_block_bwd_saved_bf16(const uint16_t* x, const u
   OCOCC_REQUIRE(num_tiles == 0 || (attn_saved && lse_saved), "null pointer");
   return attn_block_bwd(x, pos, dy, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo,
                         ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, nullptr, ln_partial, attn_saved, lse_saved,
-                        stream);
+                        0.f, nullptr, stream);
+}
+
+// ---- dropout twins of the four attention-block entry points: their arguments plus dropout_p in [0, 1) and the device seed
+extern "C" int ococc_window_attn_block_fwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
+                                                     const int32_t* tile_span, int64_t num_tiles, int32_t d_model,
+                                                     int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
+                                                     const uint16_t* wo_frag, const float* bo, const float* ln_weight,
+                                                     const float* ln_bias, float eps, uint16_t* y, float dropout_p,
+                                                     const uint64_t* seed, ococc_stream_t stream) {
+  return attn_block_fwd(x, pos, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo, ln_weight,
+                        ln_bias, eps, y, nullptr, nullptr, dropout_p, seed, stream);
+}
+
+extern "C" int ococc_window_attn_block_train_fwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
+                                                           const int32_t* tile_span, int64_t num_tiles, int32_t d_model,
+                                                           int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
+                                                           const uint16_t* wo_frag, const float* bo, const float* ln_weight,
+                                                           const float* ln_bias, float eps, uint16_t* y, uint16_t* attn_save,
+                                                           float* lse_save, float dropout_p, const uint64_t* seed,
+                                                           ococc_stream_t stream) {
+  OCOCC_REQUIRE(num_tiles == 0 || (attn_save && lse_save && aligned16(attn_save) && aligned16(lse_save)),
+                "attn_save / lse_save: 16-byte aligned device buffers");
+  return attn_block_fwd(x, pos, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo, ln_weight,
+                        ln_bias, eps, y, attn_save, lse_save, dropout_p, seed, stream);
+}
+
+extern "C" int ococc_window_attn_block_bwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
+                                                     const int32_t* tile_rows, const int32_t* tile_span,
+                                                     int64_t num_tiles, int32_t d_model, int32_t num_heads,
+                                                     const uint16_t* wqkv_frag, const float* bqkv, const uint16_t* wo_frag,
+                                                     const float* bo, const float* ln_weight, float eps,
+                                                     const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag, uint16_t* dx,
+                                                     uint16_t* dqkv, uint16_t* dz, uint16_t* attn_out, float* ln_partial,
+                                                     float dropout_p, const uint64_t* seed, ococc_stream_t stream) {
+  return attn_block_bwd(x, pos, dy, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo,
+                        ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, attn_out, ln_partial, nullptr, nullptr,
+                        dropout_p, seed, stream);
+}
+
+extern "C" int ococc_window_attn_block_bwd_saved_drop_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
+                                                           const int32_t* tile_rows, const int32_t* tile_span,
+                                                           int64_t num_tiles, int32_t d_model, int32_t num_heads,
+                                                           const uint16_t* wqkv_frag, const float* bqkv,
+                                                           const uint16_t* wo_frag, const float* bo, const float* ln_weight,
+                                                           float eps, const uint16_t* wo_t_frag,
+                                                           const uint16_t* wqkv_t_frag, const uint16_t* attn_saved,
+                                                           const float* lse_saved, uint16_t* dx, uint16_t* dqkv, uint16_t* dz,
+                                                           float* ln_partial, float dropout_p, const uint64_t* seed,
+                                                           ococc_stream_t stream) {
+  OCOCC_REQUIRE(num_tiles == 0 || (attn_saved && lse_saved), "null pointer");
+  return attn_block_bwd(x, pos, dy, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo,
+                        ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, nullptr, ln_partial, attn_saved, lse_saved,
+                        dropout_p, seed, stream);
 }
 
 extern "C" int ococc_token_ffn_block_fwd_bf16(const uint16_t* x, int64_t num_tokens, int32_t d_model, int32_t d_ffn,

@@ -8,7 +8,11 @@ EncoderLayer.forward / WindowAttention.forward (mmdet3d/models/sst/sst_basic_blo
 Windows of up to 64 tokens are packed into tiles of 64 slots (``TilePlan``, built once per batch and window shift by
 ococc_window_tile_plan); windows of drop levels above 64 tokens keep the per-window attention kernels on the rows they
 own (sst_modules.WindowMultiheadAttention.forward_flat) and both halves meet again in the FFN block, which does not
-care about windows.  Nothing but the layer input is saved for backward: the backward kernels recompute."""
+care about windows.  Nothing but the layer input is saved for backward: the backward kernels recompute.
+
+Attention dropout (AttnBlock's ``p`` > 0 with a device int64 ``seed``): the ococc_window_attn_block_*_drop_bf16 twins drop
+and rescale the softmax's probabilities by a hash of (seed, head, flat query row, flat key row) -- the mask the per-window
+gather kernels draw for the same rows -- and the backward regenerates it from the saved seed."""
 import ctypes
 import os
 
@@ -131,7 +135,7 @@ class AttnBlock(torch.autograd.Function):
     """y1 rows of the plan's tokens; every other row of the result is zero (covered=False) or does not exist."""
 
     @staticmethod
-    def forward(ctx, x, pos, plan, in_w, in_b, out_w, out_b, ln_w, ln_b, eps, num_heads, covered):
+    def forward(ctx, x, pos, plan, in_w, in_b, out_w, out_b, ln_w, ln_b, eps, num_heads, covered, p=0.0, seed=None):
         V, E = x.shape
         assert x.dtype == torch.bfloat16 and x.is_contiguous() and (pos is None or (pos.dtype == x.dtype and pos.is_contiguous()))
         wqkv, wo = linear_fragments([in_w.detach(), out_w.detach()])
@@ -148,16 +152,28 @@ class AttnBlock(torch.autograd.Function):
         if keep:
             o_save = (torch.empty if covered else torch.zeros)((V, E), dtype=torch.bfloat16, device=x.device)
             lse_save = torch.empty((V, num_heads), dtype=torch.float32, device=x.device)
-            _run('window_attn_block_fwd', flops, lambda: L.check(L.lib.ococc_window_attn_block_train_fwd_bf16(
+            if p > 0:
+                _run('window_attn_block_fwd', flops, lambda: L.check(L.lib.ococc_window_attn_block_train_fwd_drop_bf16(
+                    L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, num_heads, L.ptr(wqkv),
+                    L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), L.ptr(b1), float(eps), L.ptr(y), L.ptr(o_save),
+                    L.ptr(lse_save), float(p), L.ptr(seed), L.stream()), 'window_attn_block_train_fwd_drop'))
+            else:
+                _run('window_attn_block_fwd', flops, lambda: L.check(L.lib.ococc_window_attn_block_train_fwd_bf16(
+                    L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, num_heads, L.ptr(wqkv),
+                    L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), L.ptr(b1), float(eps), L.ptr(y), L.ptr(o_save),
+                    L.ptr(lse_save), L.stream()), 'window_attn_block_train_fwd'))
+        elif p > 0:
+            _run('window_attn_block_fwd', flops, lambda: L.check(L.lib.ococc_window_attn_block_fwd_drop_bf16(
                 L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, num_heads, L.ptr(wqkv), L.ptr(bq),
-                L.ptr(wo), L.ptr(bo), L.ptr(g1), L.ptr(b1), float(eps), L.ptr(y), L.ptr(o_save), L.ptr(lse_save), L.stream()),
-                'window_attn_block_train_fwd'))
+                L.ptr(wo), L.ptr(bo), L.ptr(g1), L.ptr(b1), float(eps), L.ptr(y), float(p), L.ptr(seed), L.stream()),
+                'window_attn_block_fwd_drop'))
         else:
             _run('window_attn_block_fwd', flops, lambda: L.check(L.lib.ococc_window_attn_block_fwd_bf16(
                 L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, num_heads, L.ptr(wqkv), L.ptr(bq),
                 L.ptr(wo), L.ptr(bo), L.ptr(g1), L.ptr(b1), float(eps), L.ptr(y), L.stream()), 'window_attn_block_fwd'))
         ctx.save_for_backward(x, pos, in_w, in_b, out_w, out_b, ln_w, *([o_save, lse_save] if keep else []))
         ctx.misc = (plan, float(eps), int(num_heads), bool(covered), wqkv, wo, bq, bo, g1)
+        ctx.drop = (float(p), seed)
         return y
 
     @staticmethod
@@ -165,6 +181,7 @@ class AttnBlock(torch.autograd.Function):
         x, pos, in_w, in_b, out_w, out_b, ln_w = ctx.saved_tensors[:7]
         kept = ctx.saved_tensors[7:]
         plan, eps, H, covered, wqkv, wo, bq, bo, g1 = ctx.misc
+        p, seed = ctx.drop
         V, E = x.shape
         dy = dy.to(torch.bfloat16).contiguous()
         wot, wqkvt = linear_fragments([out_w.detach().t(), in_w.detach().t()])
@@ -176,10 +193,23 @@ class AttnBlock(torch.autograd.Function):
         lnp = torch.empty((prow, 2, E), dtype=torch.float32, device=x.device)
         if kept:
             o, lse = kept
-            L.check(L.lib.ococc_window_attn_block_bwd_saved_bf16(
+            if p > 0:
+                L.check(L.lib.ococc_window_attn_block_bwd_saved_drop_bf16(
+                    L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv),
+                    L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), eps, L.ptr(wot), L.ptr(wqkvt), L.ptr(o), L.ptr(lse),
+                    L.ptr(dx), L.ptr(dqkv), L.ptr(dz), L.ptr(lnp), p, L.ptr(seed), L.stream()),
+                    'window_attn_block_bwd_saved_drop')
+            else:
+                L.check(L.lib.ococc_window_attn_block_bwd_saved_bf16(
+                    L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv),
+                    L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), eps, L.ptr(wot), L.ptr(wqkvt), L.ptr(o), L.ptr(lse),
+                    L.ptr(dx), L.ptr(dqkv), L.ptr(dz), L.ptr(lnp), L.stream()), 'window_attn_block_bwd_saved')
+        elif p > 0:
+            o = new((V, E), dtype=torch.bfloat16, device=x.device)
+            L.check(L.lib.ococc_window_attn_block_bwd_drop_bf16(
                 L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv),
-                L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), eps, L.ptr(wot), L.ptr(wqkvt), L.ptr(o), L.ptr(lse), L.ptr(dx),
-                L.ptr(dqkv), L.ptr(dz), L.ptr(lnp), L.stream()), 'window_attn_block_bwd_saved')
+                L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), eps, L.ptr(wot), L.ptr(wqkvt), L.ptr(dx), L.ptr(dqkv), L.ptr(dz),
+                L.ptr(o), L.ptr(lnp), p, L.ptr(seed), L.stream()), 'window_attn_block_bwd_drop')
         else:
             o = new((V, E), dtype=torch.bfloat16, device=x.device)
             L.check(L.lib.ococc_window_attn_block_bwd_bf16(
@@ -189,7 +219,7 @@ class AttnBlock(torch.autograd.Function):
         # rows outside the plan hold zeros in dqkv / dz: they add nothing to the sums below
         (dwqkv, dbqkv), (dwo, dbo), (dg, db) = _wgrad([(dqkv, 3 * E, x, pos, 2 * E), (dz, E, o, None, 0)], V, x.device, lnp, prow)
         return (dx, None, None, dwqkv.to(in_w.dtype), dbqkv.to(in_b.dtype), dwo.to(out_w.dtype), dbo.to(out_b.dtype),
-                dg.to(ln_w.dtype), db.to(ln_w.dtype), None, None, None)
+                dg.to(ln_w.dtype), db.to(ln_w.dtype), None, None, None, None, None)
 
 
 class FfnBlock(torch.autograd.Function):

@@ -5,7 +5,13 @@ and SSTv2 (mmdet3d/models/backbones/sst_v2.py:17-197).  Same constructor argumen
 and parameter names (win_attn.self_attn.in_proj_weight, linear1, norm1, ...).
 
 Device work: window ranks ococc_group_rank_i32; attention core ococc_window_attn_{fwd,bwd}_bf16
-(MFMA QK^T / PV on padded windows); projections / FFN are GEMMs through torch."""
+(MFMA QK^T / PV on padded windows); projections / FFN are GEMMs through torch.
+
+Attention dropout (``dropout`` of WindowAttention / EncoderLayer, nn.MultiheadAttention(dropout=p) upstream) runs inside
+the same kernels (their ``*_drop_bf16`` twins): in training mode with p > 0 every attention call draws one int64 seed on
+the device, the kernels drop a probability iff a hash of (seed, head, query row, key row) falls below p (csrc/
+attn_dropout.hpp) and scale the kept ones by 1 / (1 - p), and the backward regenerates the mask from the saved seed.
+The mask is not torch's random stream; eval mode and p = 0 run the kernels without dropout."""
 import torch
 from torch import nn
 
@@ -211,7 +217,7 @@ class _WindowAttnCore(torch.autograd.Function):
     """softmax(q k^T / sqrt(d) + mask) v on padded windows, bf16 MFMA kernel."""
 
     @staticmethod
-    def forward(ctx, q, k, v, key_len, num_heads):
+    def forward(ctx, q, k, v, key_len, num_heads, p=0.0, seed=None):
         nW, T, C = q.shape
         D = C // num_heads
         qb, kb, vb = (t.to(torch.bfloat16).contiguous() for t in (q, k, v))
@@ -219,6 +225,11 @@ class _WindowAttnCore(torch.autograd.Function):
         lse = torch.empty((nW, num_heads, T), dtype=torch.float32, device=q.device)
         scale = float(D) ** -0.5
         def launch():
+            if p > 0:
+                L.check(L.lib.ococc_window_attn_fwd_drop_bf16(L.ptr(qb), L.ptr(kb), L.ptr(vb), C, C, C, L.ptr(key_len), nW,
+                                                              T, num_heads, D, scale, L.ptr(out), C, L.ptr(lse), p,
+                                                              L.ptr(seed), L.stream()), 'window_attn_fwd_drop')
+                return
             L.check(L.lib.ococc_window_attn_fwd_bf16(L.ptr(qb), L.ptr(kb), L.ptr(vb), C, C, C, L.ptr(key_len), nW, T,
                                                      num_heads, D, scale, L.ptr(out), C, L.ptr(lse), L.stream()),
                     'window_attn_fwd')
@@ -228,19 +239,27 @@ class _WindowAttnCore(torch.autograd.Function):
             launch()
         ctx.save_for_backward(qb, kb, vb, out, lse, key_len)
         ctx.meta = (num_heads, D, scale, q.dtype)
+        ctx.drop = (float(p), seed)
         return out.to(q.dtype)
 
     @staticmethod
     def backward(ctx, dout):
         qb, kb, vb, out, lse, key_len = ctx.saved_tensors
         H, D, scale, dt = ctx.meta
+        p, seed = ctx.drop
         nW, T, C = qb.shape
         do = dout.to(torch.bfloat16).contiguous()
         dq, dk, dv = torch.empty_like(qb), torch.empty_like(kb), torch.empty_like(vb)
-        L.check(L.lib.ococc_window_attn_bwd_bf16(L.ptr(qb), L.ptr(kb), L.ptr(vb), C, C, C, L.ptr(out), L.ptr(do), C,
-                                                 L.ptr(lse), L.ptr(key_len), nW, T, H, D, scale, L.ptr(dq), L.ptr(dk),
-                                                 L.ptr(dv), C, C, C, L.stream()), 'window_attn_bwd')
-        return dq.to(dt), dk.to(dt), dv.to(dt), None, None
+        if p > 0:
+            L.check(L.lib.ococc_window_attn_bwd_drop_bf16(L.ptr(qb), L.ptr(kb), L.ptr(vb), C, C, C, L.ptr(out), L.ptr(do),
+                                                          C, L.ptr(lse), L.ptr(key_len), nW, T, H, D, scale, L.ptr(dq),
+                                                          L.ptr(dk), L.ptr(dv), C, C, C, p, L.ptr(seed), L.stream()),
+                    'window_attn_bwd_drop')
+        else:
+            L.check(L.lib.ococc_window_attn_bwd_bf16(L.ptr(qb), L.ptr(kb), L.ptr(vb), C, C, C, L.ptr(out), L.ptr(do), C,
+                                                     L.ptr(lse), L.ptr(key_len), nW, T, H, D, scale, L.ptr(dq), L.ptr(dk),
+                                                     L.ptr(dv), C, C, C, L.stream()), 'window_attn_bwd')
+        return dq.to(dt), dk.to(dt), dv.to(dt), None, None, None, None
 
 
 class _WindowAttnPacked(torch.autograd.Function):
@@ -248,7 +267,7 @@ class _WindowAttnPacked(torch.autograd.Function):
     per-operand copies, and the backward writes dq | dk | dv into one packed tensor."""
 
     @staticmethod
-    def forward(ctx, qkv, key_len, num_heads):
+    def forward(ctx, qkv, key_len, num_heads, p=0.0, seed=None):
         nW, T, C3 = qkv.shape
         E = C3 // 3
         D = E // num_heads
@@ -259,6 +278,11 @@ class _WindowAttnPacked(torch.autograd.Function):
         base = qkv.data_ptr()
 
         def launch():
+            if p > 0:
+                L.check(L.lib.ococc_window_attn_fwd_drop_bf16(base, base + 2 * E, base + 4 * E, C3, C3, C3, L.ptr(key_len),
+                                                              nW, T, num_heads, D, scale, L.ptr(out), E, L.ptr(lse), p,
+                                                              L.ptr(seed), L.stream()), 'window_attn_fwd_drop')
+                return
             L.check(L.lib.ococc_window_attn_fwd_bf16(base, base + 2 * E, base + 4 * E, C3, C3, C3, L.ptr(key_len), nW,
                                                      T, num_heads, D, scale, L.ptr(out), E, L.ptr(lse), L.stream()),
                     'window_attn_fwd')
@@ -268,21 +292,29 @@ class _WindowAttnPacked(torch.autograd.Function):
             launch()
         ctx.save_for_backward(qkv, out, lse, key_len)
         ctx.meta = (num_heads, D, scale)
+        ctx.drop = (float(p), seed)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse, key_len = ctx.saved_tensors
         H, D, scale = ctx.meta
+        p, seed = ctx.drop
         nW, T, C3 = qkv.shape
         E = C3 // 3
         do = dout.to(torch.bfloat16).contiguous()
         dqkv = torch.empty_like(qkv)
         b, g = qkv.data_ptr(), dqkv.data_ptr()
-        L.check(L.lib.ococc_window_attn_bwd_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(out), L.ptr(do), E,
-                                                 L.ptr(lse), L.ptr(key_len), nW, T, H, D, scale, g, g + 2 * E,
-                                                 g + 4 * E, C3, C3, C3, L.stream()), 'window_attn_bwd')
-        return dqkv, None, None
+        if p > 0:
+            L.check(L.lib.ococc_window_attn_bwd_drop_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(out), L.ptr(do), E,
+                                                          L.ptr(lse), L.ptr(key_len), nW, T, H, D, scale, g, g + 2 * E,
+                                                          g + 4 * E, C3, C3, C3, p, L.ptr(seed), L.stream()),
+                    'window_attn_bwd_drop')
+        else:
+            L.check(L.lib.ococc_window_attn_bwd_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(out), L.ptr(do), E,
+                                                     L.ptr(lse), L.ptr(key_len), nW, T, H, D, scale, g, g + 2 * E,
+                                                     g + 4 * E, C3, C3, C3, L.stream()), 'window_attn_bwd')
+        return dqkv, None, None, None, None
 
 
 class _WindowAttnFlat(torch.autograd.Function):
@@ -292,8 +324,20 @@ class _WindowAttnFlat(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, num_heads, *level_args):
+        return _WindowAttnFlatDrop.forward(ctx, qkv, num_heads, 0.0, None, *level_args)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _WindowAttnFlatDrop.backward(ctx, dout)[:2] + (None,) * (4 * len(ctx.meta[3]))
+
+
+class _WindowAttnFlatDrop(torch.autograd.Function):
+    """_WindowAttnFlat with attention dropout: p, and the device int64 seed the backward regenerates the mask from."""
+
+    @staticmethod
+    def forward(ctx, qkv, num_heads, p, seed, *level_args):
         levels = [level_args[i:i + 4] for i in range(0, len(level_args), 4)]   # (tok, key_len, nW, T)
-        out, lses, meta = _attn_flat_forward(qkv, num_heads, levels)
+        out, lses, meta = _attn_flat_forward(qkv, num_heads, levels, p, seed)
         ctx.save_for_backward(qkv, out, *lses, *[t for lv in levels for t in lv[:2]])
         ctx.meta = meta
         return out
@@ -304,11 +348,12 @@ class _WindowAttnFlat(torch.autograd.Function):
         saved = ctx.saved_tensors
         qkv, out, lses, rest = saved[0], saved[1], saved[2:2 + n], saved[2 + n:]
         dqkv = _attn_flat_backward(qkv, out, dout, lses, rest, ctx.meta)
-        return (dqkv, None) + (None,) * (4 * n)
+        return (dqkv, None, None, None) + (None,) * (4 * n)
 
 
-def _attn_flat_forward(qkv, num_heads, levels):
-    """the gather kernels over every drop level: (out [V, E] bf16, log-sum-exp per level, meta for the backward)"""
+def _attn_flat_forward(qkv, num_heads, levels, p=0.0, seed=None):
+    """the gather kernels over every drop level: (out [V, E] bf16, log-sum-exp per level, meta for the backward);
+    p > 0: attention dropout with the device seed (one int64), the mask over the rows of qkv"""
     V, C3 = qkv.shape
     E = C3 // 3
     D = E // num_heads
@@ -321,6 +366,12 @@ def _attn_flat_forward(qkv, num_heads, levels):
         lse = torch.empty((nW, num_heads, T), dtype=torch.float32, device=qkv.device)
 
         def launch():
+            if p > 0:
+                L.check(L.lib.ococc_window_attn_fwd_gather_drop_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(tok),
+                                                                     L.ptr(key_len), nW, T, num_heads, D, scale,
+                                                                     L.ptr(out), E, L.ptr(lse), p, L.ptr(seed),
+                                                                     L.stream()), 'window_attn_fwd_gather_drop')
+                return
             L.check(L.lib.ococc_window_attn_fwd_gather_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(tok),
                                                             L.ptr(key_len), nW, T, num_heads, D, scale,
                                                             L.ptr(out), E, L.ptr(lse), L.stream()),
@@ -330,12 +381,12 @@ def _attn_flat_forward(qkv, num_heads, levels):
         else:
             launch()
         lses.append(lse)
-    return out, lses, (num_heads, D, scale, [(lv[2], lv[3]) for lv in levels])
+    return out, lses, (num_heads, D, scale, [(lv[2], lv[3]) for lv in levels], float(p), seed)
 
 
 def _attn_flat_backward(qkv, out, dout, lses, tok_and_len, meta):
     """d(q | k | v) [V, 3E] bf16 of _attn_flat_forward; ``tok_and_len`` = (tok, key_len) of every level, flattened"""
-    H, D, scale, shapes = meta
+    H, D, scale, shapes, p, seed = meta
     V, C3 = qkv.shape
     E = C3 // 3
     do = dout.to(torch.bfloat16).contiguous()
@@ -343,6 +394,12 @@ def _attn_flat_backward(qkv, out, dout, lses, tok_and_len, meta):
     b, g = qkv.data_ptr(), dqkv.data_ptr()
     for i, (nW, T) in enumerate(shapes):
         tok, key_len = tok_and_len[2 * i], tok_and_len[2 * i + 1]
+        if p > 0:
+            L.check(L.lib.ococc_window_attn_bwd_gather_drop_bf16(
+                b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(out), L.ptr(do), E, L.ptr(lses[i]), L.ptr(tok), L.ptr(key_len),
+                nW, T, H, D, scale, g, g + 2 * E, g + 4 * E, C3, C3, C3, p, L.ptr(seed), L.stream()),
+                'window_attn_bwd_gather_drop')
+            continue
         L.check(L.lib.ococc_window_attn_bwd_gather_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(out), L.ptr(do), E,
                                                         L.ptr(lses[i]), L.ptr(tok), L.ptr(key_len), nW, T, H, D,
                                                         scale, g, g + 2 * E, g + 4 * E, C3, C3, C3, L.stream()),
@@ -359,10 +416,13 @@ class _BigWindowBlock(torch.autograd.Function):
     that consume it, f32 accumulation of every parameter gradient -- written out on the few rows concerned, so that these
     rows' gradients carry the same roundings as everybody else's (and one oracle, oracle/sst_ref.py
     encoder_layer_backward, describes both).  Autograd over the bf16 operators rounded the gradient at every operator
-    boundary and every weight-gradient slab to bf16: 3e-3 norm-wise on these rows against 7e-4 on the others."""
+    boundary and every weight-gradient slab to bf16: 3e-3 norm-wise on these rows against 7e-4 on the others.
+    Attention dropout (p > 0, device seed): ``spread`` = (rows, V) -- the level arguments then hold the layer's flat rows,
+    and the attention runs on a V-row copy of q | k | v that holds these rows at their flat positions, so that the dropout
+    hash sees the same (query row, key row) pairs as the operator path (the GEMMs stay on the few rows concerned)."""
 
     @staticmethod
-    def forward(ctx, xb, posb, w_in, b_in, w_out, b_out, gamma, beta, eps, num_heads, *level_args):
+    def forward(ctx, xb, posb, w_in, b_in, w_out, b_out, gamma, beta, eps, num_heads, p, seed, spread, *level_args):
         dt = torch.bfloat16
         E = xb.shape[1]
         levels = [level_args[i:i + 4] for i in range(0, len(level_args), 4)]
@@ -371,7 +431,15 @@ class _BigWindowBlock(torch.autograd.Function):
         qkv = torch.empty((xb.shape[0], 3 * E), dtype=dt, device=xb.device)
         torch.addmm(b16[:2 * E], xp, w16[:2 * E].t(), out=qkv[:, :2 * E])
         torch.addmm(b16[2 * E:], xb, w16[2 * E:].t(), out=qkv[:, 2 * E:])
-        o, lses, meta = _attn_flat_forward(qkv, num_heads, levels)
+        ctx.spread = None
+        if spread is not None:
+            rows, V = spread
+            qkv_w = qkv.new_empty((V, 3 * E)).index_copy_(0, rows, qkv)   # (rows outside the windows are never read)
+            o_w, lses, meta = _attn_flat_forward(qkv_w, num_heads, levels, p, seed)
+            o = o_w.index_select(0, rows)
+            ctx.spread = (rows, qkv_w, o_w)
+        else:
+            o, lses, meta = _attn_flat_forward(qkv, num_heads, levels, p, seed)
         wo16 = w_out.to(dt)
         z1 = xb + torch.nn.functional.linear(o, wo16, b_out.to(dt))
         y1 = layer_norm_act(z1, gamma, beta, eps, 'none')
@@ -401,11 +469,16 @@ class _BigWindowBlock(torch.autograd.Function):
         do = _mm_f32(dz1r, wo16)
         g_wo = _mm_f32(dz1r.t(), o)
         g_bo = dz1r.float().sum(0)
-        dqkv = _attn_flat_backward(qkv, o, r16(do), lses, rest, ctx.meta)
+        if ctx.spread is not None:
+            rows, qkv_w, o_w = ctx.spread
+            do_w = o_w.new_empty(o_w.shape).index_copy_(0, rows, r16(do))
+            dqkv = _attn_flat_backward(qkv_w, o_w, do_w, lses, rest, ctx.meta).index_select(0, rows)
+        else:
+            dqkv = _attn_flat_backward(qkv, o, r16(do), lses, rest, ctx.meta)
         dx = r16(_mm_f32(dqkv, w16) + dz1)
         g_w = torch.cat([_mm_f32(dqkv[:, :2 * E].t(), xp), _mm_f32(dqkv[:, 2 * E:].t(), xb)], 0)
         g_b = dqkv.float().sum(0)
-        return (dx, None, g_w, g_b, g_wo, g_bo, g_gamma, g_beta, None, None) + (None,) * (4 * n)
+        return (dx, None, g_w, g_b, g_wo, g_bo, g_gamma, g_beta, None, None, None, None, None) + (None,) * (4 * n)
 
 
 try:   # bf16 operands, f32 result without a rounding in between (torch >= 2.8); else f32 copies of the operands
@@ -570,22 +643,21 @@ def _fused_maps(ind_dict, pos_dict, key_padding_dict, num_tokens, dtype):
             for dl, (slot, pos, nW, T, key_len, tok) in large.items():
                 t2 = torch.where(tok >= 0, inv[tok.clamp(min=0).long()], tok)
                 remapped[dl] = (slot, inv[pos].long(), nW, T, key_len, t2)
-            big = (rows, remapped)
+            big = (rows, remapped, large)   # (large: the levels over the layer's flat rows, for attention dropout)
         hit = ind_dict['_ococc_fused'] = (plan, big, pos_flat)
     return hit
 
 
 class WindowMultiheadAttention(nn.Module):
     """Parameter layout of nn.MultiheadAttention (in_proj_weight [3E,E], in_proj_bias,
-    out_proj.{weight,bias}); batch-first padded windows [nW, T, E]; attention core on the HIP kernel."""
+    out_proj.{weight,bias}); batch-first padded windows [nW, T, E]; attention core on the HIP kernel.
+    ``dropout``: attention-probability dropout in training mode, inside the kernels (see the module docstring)."""
 
     def __init__(self, embed_dim, num_heads, dropout=0.0, cosine=False, tau_min=0.01, non_shared_tau=False):
         super().__init__()
-        if dropout != 0:
-            raise NotImplementedError('attention-probability dropout is not built into the window-attention kernel; the '
-                                      'reference SST configs use dropout=0.0 (sst_basic_block_v2.py:41-75 passes it to '
-                                      'nn.MultiheadAttention)')
-        self.embed_dim, self.num_heads, self.dropout = embed_dim, num_heads, dropout
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError(f'attention dropout must be in [0, 1), got {dropout}')
+        self.embed_dim, self.num_heads, self.dropout = embed_dim, num_heads, float(dropout)
         self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
         self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
         self.out_proj = nn.Linear(embed_dim, embed_dim)
@@ -596,6 +668,13 @@ class WindowMultiheadAttention(nn.Module):
         self.tau_min = tau_min
         self.tau = (nn.Parameter(torch.ones(1, num_heads, 1, 1) if non_shared_tau else torch.ones(1, 1, 1))
                     if cosine else None)
+
+    def drop_args(self, device):
+        """(p, seed) of one attention call: in training mode with p > 0 a fresh int64 seed drawn on the device by torch's
+        generator (a captured graph draws a new one per replay), else (0.0, None)"""
+        if not (self.training and self.dropout > 0):
+            return 0.0, None
+        return self.dropout, torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=device)
 
     def _cosine_q_k(self, q, k):
         """q, k [..., E] -> unit vectors per head, q additionally divided by tau and multiplied by sqrt(d) so
@@ -618,8 +697,9 @@ class WindowMultiheadAttention(nn.Module):
         q_, k_ = qk[:, :E], qk[:, E:]
         if self.tau is not None:
             q_, k_ = self._cosine_q_k(q_, k_)
+        p, seed = self.drop_args(qk_in.device)
         o = _WindowAttnCore.apply(q_.reshape(nW, T, E), k_.reshape(nW, T, E), v.view(nW, T, E),
-                                  key_len, self.num_heads)
+                                  key_len, self.num_heads, p, seed)
         return self.out_proj(o.reshape(nW * T, E)).view(nW, T, E)
 
     def forward_flat(self, x, pos_flat, maps, dtype):
@@ -638,16 +718,17 @@ class WindowMultiheadAttention(nn.Module):
         else:
             qkv = _QkvProjection.apply(x16, pos_flat.to(dtype), w, b)   # q | k | v in one buffer, no concatenation
         covered = sum(int(m[0].numel()) for m in maps.values())
+        p, seed = self.drop_args(x.device)
         if covered == x.shape[0]:   # every token sits in a window (always, after drop_voxel): gather kernels
             args = []
             for dl, (slot, pos, nW, T, key_len, tok) in maps.items():
                 args += [tok, key_len, nW, T]
-            o_flat = _WindowAttnFlat.apply(qkv, H, *args)
+            o_flat = _WindowAttnFlatDrop.apply(qkv, H, p, seed, *args) if p > 0 else _WindowAttnFlat.apply(qkv, H, *args)
         else:
             o_flat = None
             for dl, (slot, pos, nW, T, key_len, tok) in maps.items():
                 packed = _ScatterRows.apply(qkv, pos, slot, nW * T).view(nW, T, 3 * E)
-                o = _WindowAttnPacked.apply(packed, key_len, H).view(nW * T, E)
+                o = _WindowAttnPacked.apply(packed, key_len, H, p, seed).view(nW * T, E)
                 part = _ScatterRows.apply(o, slot, pos, x.shape[0])
                 o_flat = part if o_flat is None else o_flat + part
         return _TokenLinear.apply(o_flat, self.out_proj.weight.to(dtype), self.out_proj.bias.to(dtype))
@@ -724,7 +805,8 @@ class EncoderLayer(nn.Module):
 
     def _fusable(self):
         """The tile kernels of csrc/window_block.hip cover the reference SST configuration (d_model 128, 8 heads, ffn
-        256, LayerNorm, post-norm, no dropout, softmax attention): anything else keeps the per-operator path."""
+        256, LayerNorm, post-norm, softmax attention, with or without attention dropout): anything else -- mlp_dropout in
+        training mode included -- keeps the per-operator path."""
         mha = self.win_attn.self_attn
         drop = self.training and (self.dropout.p > 0 or self.dropout1.p > 0 or self.dropout2.p > 0)
         wanted = FUSED_ENCODER_LAYER and self.compute_dtype == torch.bfloat16
@@ -737,8 +819,8 @@ class EncoderLayer(nn.Module):
                         self.use_bn, mha.tau is None, bool(drop)),
                        f'SST encoder layer (d_model {mha.embed_dim}, {mha.num_heads} heads, ffn {self.linear1.out_features}, '
                        f'{self._act_name}, post_norm={self.post_norm}, use_bn={self.use_bn}, cosine={mha.tau is not None}, '
-                       f'dropout={bool(drop)}) is outside the fused block kernels (128 / 8 / 256, gelu|relu, post-norm '
-                       'LayerNorm, softmax, no dropout): running operator by operator')
+                       f'mlp_dropout={bool(drop)}) is outside the fused block kernels (128 / 8 / 256, gelu|relu, post-norm '
+                       'LayerNorm, softmax, attention dropout only): running operator by operator')
         return ok
 
     def _forward_fused(self, src, pos_dict, ind_dict, key_padding_mask_dict):
@@ -748,20 +830,23 @@ class EncoderLayer(nn.Module):
         x = src.to(dt).contiguous()
         plan, big, pos_flat = _fused_maps(ind_dict, pos_dict, key_padding_mask_dict, x.shape[0], dt)
         covered = plan.tokens == x.shape[0]
+        p, seed = mha.drop_args(x.device)   # one seed for the layer's attention: tiles and big windows alike
         y1 = fb.AttnBlock.apply(x, pos_flat, plan, mha.in_proj_weight, mha.in_proj_bias, mha.out_proj.weight,
                                 mha.out_proj.bias, self.norm1.weight, self.norm1.bias, self.norm1.eps, mha.num_heads,
-                                covered)
+                                covered, p, seed)
         if big is not None:   # windows of more than 64 tokens: per-window kernels on the rows they own
-            rows, maps = big
+            rows, maps, flat_maps = big
             xb = x.index_select(0, rows)
             covered_big = sum(int(m[0].numel()) for m in maps.values()) == xb.shape[0]
             if BIG_WINDOW_BLOCK and mha.tau is None and covered_big:
                 args = []
-                for dl, (slot, pos, nW, T, key_len, tok) in maps.items():
+                # dropout: the kernels see the layer's flat rows (the hash's query / key rows), else the rows of xb
+                for dl, (slot, pos, nW, T, key_len, tok) in (flat_maps if p > 0 else maps).items():
                     args += [tok, key_len, nW, T]
                 y1b = _BigWindowBlock.apply(xb, pos_flat.index_select(0, rows), mha.in_proj_weight, mha.in_proj_bias,
                                             mha.out_proj.weight, mha.out_proj.bias, self.norm1.weight, self.norm1.bias,
-                                            self.norm1.eps, mha.num_heads, *args)
+                                            self.norm1.eps, mha.num_heads, p, seed,
+                                            (rows, x.shape[0]) if p > 0 else None, *args)
             else:
                 ob = mha.forward_flat(xb, pos_flat.index_select(0, rows), maps, dt)
                 y1b = self._ln(self.norm1, xb + ob)

@@ -559,6 +559,20 @@ int ococc_dynamic_point_pool_mixed(const float* rois, const int32_t* rois_key, i
 int ococc_aligned_iou3d_f32(const float* boxes1, const float* boxes2, int64_t n, float* iou,
                             ococc_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * occupancy IoU counts of one chunk of RoIs, replacing the ATen chain of TrackletRoIHeadOCC.test_occ
+ *   (mmdet3d/models/roi_heads/tracklet_roi_head_occ.py:394-486: repeat, inside-box test, *, ==, &, |, two sums).
+ * logits [n, K] f32 (decoder output, cls_dim 1); labels [K] int64 (occupied: == 1);
+ * roi_xyz [n, K, 3] f32 RoI-frame query points and half_sizes [n, 3] f32, both NULL or both set (ignore_outside_occ:
+ *   a cell outside -half <= xyz <= half, bounds inclusive, is predicted empty).
+ * Predicted occupied: 1 / (1 + exp(-logit)) > pos_thresh in f32 (ATen's sigmoid; NaN is empty).
+ * Adds (inter, union) of RoI i to counts[row0 + i, 0:2] of an int64 [rows, 2] device buffer (zeroed by the caller
+ *   once per tracklet): ballots + popcounts per wave, one 64-bit vector atomic per wave, RoI and count.
+ * ------------------------------------------------------------------------ */
+int ococc_occ_iou_count(const float* logits, const int64_t* labels, const float* roi_xyz, const float* half_sizes,
+                        int32_t n, int64_t K, float pos_thresh, int64_t* counts, int64_t row0, int64_t rows,
+                        ococc_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * A12 glue, one launch each (f32; the element-wise chains they replace were 12-35 launches of a few hundred elements):
  * ococc_rotate_z_f32: rotation_3d_in_axis(points [n, m, 3], angles [n], axis=2)

@@ -10,7 +10,7 @@
 
 ``evaluate`` (:315-428) writes the Waymo-format result file (waymo_io.convert_tracklet_to_waymo: the metrics.Objects
 protobuf encoded without the waymo_open_dataset package) and parses the metrics tool's output when the caller names the
-tool's executable; the occupancy-IoU metric is roi_head.occupancy_iou_metrics."""
+tool's executable; WaymoTrackletDatasetWithOcc.evaluate adds metric 'iou' (roi_head.occupancy_iou_metrics)."""
 import os.path as osp
 import pickle
 
@@ -157,6 +157,37 @@ class WaymoTrackletDatasetWithOcc(WaymoTrackletDataset):
     def get_data_info(self, index):
         out = super().get_data_info(index)
         out['occ_infos'] = [self.parse_occ_anno(t) for t in out['ann_info']]
+        return out
+
+    def evaluate(self, results, metric='waymo', logger=None, pklfile_prefix=None, submission_prefix=None, show=False,
+                 out_dir=None, pipeline=None, metrics_main=None):
+        """:586-672 -- results: one model output per tracklet (``out_tracklets``, and ``inters`` / ``unions`` /
+        ``gt_boxes`` with test_occ_iou).  metric 'waymo', 'iou' or both (a list): 'waymo' hands the refined tracklets
+        (``r['out_tracklets'][0]``) to WaymoTrackletDataset.evaluate; 'iou' returns roi_head.occupancy_iou_metrics
+        (iou, miou_track, miou_box, iou_small / medium / large where present) and prints the reference's summary."""
+        metrics = [metric] if isinstance(metric, str) else list(metric)
+        unknown = [m for m in metrics if m not in ('waymo', 'iou')]
+        if unknown:
+            raise KeyError(f'metric {unknown} is not supported (waymo, iou)')
+        out = {}
+        if 'waymo' in metrics:
+            if pklfile_prefix is None:
+                import tempfile
+                pklfile_prefix = osp.join(tempfile.mkdtemp(), 'results')
+            res = super().evaluate([r['out_tracklets'][0] for r in results], 'waymo', logger, pklfile_prefix,
+                                   submission_prefix, show, out_dir, pipeline, metrics_main)
+            out.update(res or {})
+        if 'iou' in metrics:
+            from .roi_head import occupancy_iou_metrics
+            m = occupancy_iou_metrics(results)
+            if m:
+                print(f"\n Overall iou: {m['iou']}, \nmIoU (track): {m['miou_track']}\nmIoU (box): {m['miou_box']}\n")
+                for name in ('small', 'medium', 'large'):
+                    if 'iou_' + name in m:
+                        print(f"{name} box iou: {m['iou_' + name]}")
+            else:
+                print('\n no tracklet with occupancy counts: no IoU')
+            out.update(m)
         return out
 
     def parse_occ_anno(self, trk):

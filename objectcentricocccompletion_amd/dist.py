@@ -219,3 +219,62 @@ def broadcast_parameters(module, src=0):
         return
     for t in list(module.parameters()) + list(module.buffers()):
         dist.broadcast(t.data, src)
+
+
+def collect_results(part, size, tmpdir=None, gpu_collect=False):
+    """The per-rank result lists of a sharded evaluation, joined on rank 0 in dataset order (mmdet3d/apis/test.py:93-183,
+    multi_gpu_test_sequential): every rank holds the results of its contiguous shard_range, so the parts concatenated in
+    rank order ARE the dataset order.  Returns the joined list (cut to ``size``) on rank 0 and None on the others; one
+    process returns ``part`` as it is.
+
+    Default: each rank pickles its part into ``tmpdir`` (a fresh directory made by rank 0 when None, removed after the
+    join), a barrier, rank 0 reads the parts -- CPU files, works under gloo and RCCL alike.  ``gpu_collect``: the parts
+    travel as pickled byte tensors through one all-gather (on the current device under RCCL, in host memory under gloo),
+    padded to the longest."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return list(part)[:size]
+    rank, world = dist.get_rank(), dist.get_world_size()
+    if gpu_collect:
+        return _collect_all_gather(part, size, rank, world)
+    import pickle
+    import shutil
+    import tempfile
+    made = tmpdir is None
+    box = [tempfile.mkdtemp(prefix='ococc_collect_') if rank == 0 and made else tmpdir]
+    dist.broadcast_object_list(box, 0)
+    tmpdir = box[0]
+    os.makedirs(tmpdir, exist_ok=True)
+    with open(os.path.join(tmpdir, f'part_{rank}.pkl'), 'wb') as f:
+        pickle.dump(list(part), f)
+    dist.barrier()
+    if rank != 0:
+        return None
+    out = []
+    for r in range(world):
+        path = os.path.join(tmpdir, f'part_{r}.pkl')
+        with open(path, 'rb') as f:
+            out.extend(pickle.load(f))
+        os.remove(path)
+    if made:
+        shutil.rmtree(tmpdir, ignore_errors=True)
+    return out[:size]
+
+
+def _collect_all_gather(part, size, rank, world):
+    import pickle
+    dev = torch.device('cuda', torch.cuda.current_device()) if dist.get_backend() == 'nccl' else torch.device('cpu')
+    data = torch.frombuffer(bytearray(pickle.dumps(list(part))), dtype=torch.uint8).to(dev)
+    n = torch.tensor([data.numel()], dtype=torch.long, device=dev)
+    sizes = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(sizes, n)
+    sizes = [int(s) for s in sizes]
+    buf = torch.zeros(max(sizes), dtype=torch.uint8, device=dev)
+    buf[:data.numel()] = data
+    bufs = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(bufs, buf)
+    if rank != 0:
+        return None
+    out = []
+    for b, s in zip(bufs, sizes):
+        out.extend(pickle.loads(b[:s].cpu().numpy().tobytes()))
+    return out[:size]

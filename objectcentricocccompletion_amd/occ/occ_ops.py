@@ -64,3 +64,31 @@ def dense_voxel_centers_batched(bbox_sizes, voxel_size, scale_wlh=[1.0, 1.0, 1.0
     coors = torch.stack([local // (ys * zs), (local // zs) % ys, local % zs], 1)
     centers = coors.to(torch.float) * voxel_size + (-size / 2)[box] + voxel_size / 2
     return centers, box, k
+
+
+def occ_iou_count(logits, labels, counts, row0, pos_thresh, roi_xyz=None, half_sizes=None):
+    """Adds the occupancy (inter, union) of n RoIs to rows [row0, row0 + n) of ``counts`` (int64 [R, 2], on the device)
+    in one launch (csrc/occ_iou_count.hip): logits [n*K] or [n, K] f32 of the one-logit decoder, labels [K] int64
+    (occupied: == 1); with roi_xyz [n, K, 3] and half_sizes [n, 3] a cell outside its RoI's box counts as predicted
+    empty.  Predicted occupied is sigmoid(logit) > pos_thresh, decided as ATen decides it.  Nothing is read back."""
+    from .. import _lib as L
+    L.require_device(logits, labels, counts, roi_xyz, half_sizes)
+    K = labels.numel()
+    n = logits.numel() // K if K else 0
+    if logits.dtype != torch.float32 or logits.numel() != n * K:
+        raise L.OcoccError(f'occ_iou_count: logits {tuple(logits.shape)} {logits.dtype} are not f32 [n, {K}]')
+    if labels.dtype != torch.int64 or counts.dtype != torch.int64 or counts.dim() != 2 or counts.size(1) != 2 \
+            or not counts.is_contiguous():
+        raise L.OcoccError('occ_iou_count: labels and counts are int64, counts a contiguous [R, 2] buffer')
+    if (roi_xyz is None) != (half_sizes is None):
+        raise L.OcoccError('occ_iou_count: roi_xyz and half_sizes go together')
+    if roi_xyz is not None:
+        if roi_xyz.dtype != torch.float32 or roi_xyz.numel() != n * K * 3 or half_sizes.dtype != torch.float32 \
+                or half_sizes.numel() != n * 3:
+            raise L.OcoccError(f'occ_iou_count: roi_xyz / half_sizes are not f32 [{n}, {K}, 3] / [{n}, 3]')
+        roi_xyz, half_sizes = roi_xyz.contiguous(), half_sizes.contiguous()
+    logits, labels = logits.contiguous(), labels.contiguous()
+    L.check(L.lib.ococc_occ_iou_count(L.ptr(logits), L.ptr(labels), L.ptr(roi_xyz), L.ptr(half_sizes), n, K,
+                                      float(pos_thresh), L.ptr(counts), int(row0), counts.size(0), L.stream()),
+            'occ_iou_count')
+    return counts

@@ -75,3 +75,35 @@ def ococcnet_train_pipeline(reg_len=32, occ_voxel_size=0.2, class_names=('Car',)
         dict(type='Collect3D', keys=['points', 'pts_frame_inds', 'tracklet', 'gt_tracklet_candidates', 'occ_labels',
                                      'occ_labels_scores']),
     ]
+
+
+def ococcnet_eval_pipeline(occ_voxel_size=0.2, class_names=('Car',)):
+    """eval_pipeline of configs/ococc/ococcnet.py (the pipeline of its data.val / data.test): every labelled cell of
+    every GT candidate is a query point (num_sample_points=-1), no regularisation, noise, flips or rotations."""
+    return [
+        dict(type='LoadTrackletPoints', load_dim=6, use_dim=5, max_points=1024, debug=False),
+        dict(type='LoadTrackletAnnotations'),
+        dict(type='LoadAnnotationsOcc'),
+        dict(type='RandomSampleOccPoints', num_sample_points=-1, pos_sample_weight=0.5, voxel_size=occ_voxel_size,
+             use_unknown=False, use_potential=False, balance_sample=True, weighted_sample=True),
+        dict(type='TrackletPoseTransform', concat=False),
+        dict(type='PointDecoration', properties=['yaw', 'size', 'score'], concat=True),
+        dict(type='PointsRangeFilter', point_cloud_range=[-204.7, -204.7, -3.99, 204.7, 204.7, 7.99]),
+        dict(type='PointShuffle'),
+        dict(type='TrackletOccFormatBundle', class_names=list(class_names)),
+        dict(type='Collect3D', keys=['points', 'pts_frame_inds', 'tracklet', 'gt_tracklet_candidates', 'occ_labels',
+                                     'occ_labels_scores']),
+    ]
+
+
+def ococcnet_test_data(data_root='data/waymo/kitti_format/', pipeline=None, class_names=('Car',)):
+    """data.test of configs/ococc/ococcnet.py: the validation tracklets in the reference's data/waymo layout, every
+    tracklet kept (min_tracklet_points = min_tracklet_length = -1)."""
+    return dict(type='WaymoTrackletDatasetWithOcc', data_root=data_root,
+                occ_anno_root='data/waymo/waymo_occ_gt/waymo_occ_gt/training',
+                ann_file='data/waymo/tracklet_data/fsd_base_1f_vehicle_val_gt_candidates.pkl',
+                tracklet_proposals_file='data/waymo/tracklet_data/fsd_base_1f_vehicle_val.pkl',
+                pose_file=data_root + 'poses.pkl',
+                pipeline=pipeline if pipeline is not None else ococcnet_eval_pipeline(class_names=class_names),
+                load_interval=1, box_type_3d='LiDAR', min_tracklet_points=-1, min_tracklet_length=-1,
+                classes=list(class_names))

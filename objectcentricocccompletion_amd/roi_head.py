@@ -12,11 +12,15 @@ from torch import nn
 
 from ._lib import const_tensor
 from .bbox import points_box_to_box, rotation_3d_in_axis
+from .occ import occ_ops
 from .registry import BBOX_ASSIGNERS, DETECTORS, HEADS, ROI_EXTRACTORS
 from .tracklet import SamplingResult, Tracklet
 
 
 BATCHED_ASSIGN = os.environ.get('OCOCC_BATCHED_ASSIGN', '1') == '1'   # assignment / sampling of all tracklets at once
+# test_occ's per-RoI occupancy counts: one HIP launch per chunk, counts kept on the device (0: the ATen chain and a
+# read-back per chunk, occ_iou_counts_aten -- also what the CPU stand-ins of oracle/cpu_port.py run)
+OCC_IOU_KERNEL = os.environ.get('OCOCC_OCC_IOU_KERNEL', '1') != '0'
 
 
 def bbox3d2roi(bbox_list):
@@ -370,20 +374,37 @@ class TrackletRoIHeadOCC(nn.Module):
         chunk = int(match.numel()) if chunk == -1 else chunk
         pred_boxes, gt_boxes_all, feats = rois[match][:, 1:], gt_rois[match][:, 1:], fused_roi_feats[match]
         decoder = self.bbox_head.occ_ae_head.occ_decoder
+        outside = self.test_cfg.get('ignore_outside_occ', False)
+        if OCC_IOU_KERNEL and decoder.cls_dim == 1 and feats.is_cuda:
+            # the counts stay on the device: one int64 [R, 2] buffer per tracklet, one count launch after each chunk's
+            # decoder launch, ONE read-back at the end (csrc/occ_iou_count.hip)
+            R = gt_boxes_all.size(0)
+            counts = torch.zeros((R, 2), dtype=torch.long, device=feats.device)
+            halves = (pred_boxes[:, 3:6] / 2).contiguous() if outside else None
+            sizes, row0 = [], 0
+            for f, pb, gb in zip(torch.split(feats, chunk), torch.split(pred_boxes, chunk),
+                                 torch.split(gt_boxes_all, chunk)):
+                n = gb.size(0)
+                xyz = to_roi_frame(occ_xyz[None].repeat(n, 1, 1), gb, pb)
+                idx = torch.arange(n, device=xyz.device).repeat_interleave(K)
+                logits = decoder(f, xyz.reshape(n * K, 3), idx)
+                occ_ops.occ_iou_count(logits, occ_label, counts, row0, decoder.pos_thresh,
+                                      xyz if outside else None, halves[row0:row0 + n] if outside else None)
+                sizes.append(n)
+                row0 += n
+            host = counts.cpu().t().contiguous()
+            return dict(inters=[t.clone() for t in host[0].split(sizes)],
+                        unions=[t.clone() for t in host[1].split(sizes)],
+                        gt_boxes=[t.clone() for t in gt_boxes_all.cpu().split(sizes)])
         inters, unions, gt_boxes = [], [], []
         for f, pb, gb in zip(torch.split(feats, chunk), torch.split(pred_boxes, chunk), torch.split(gt_boxes_all, chunk)):
             n = gb.size(0)
             xyz = to_roi_frame(occ_xyz[None].repeat(n, 1, 1), gb, pb)
-            lab = occ_label[None].repeat(n, 1)
-            if self.test_cfg.get('ignore_outside_occ', False):
-                half = pb[:, None, 3:6] / 2
-                inside = (xyz >= -half).all(-1) & (xyz <= half).all(-1)
-            else:
-                inside = torch.ones((n, K), dtype=torch.bool, device=xyz.device)
             idx = torch.arange(n, device=xyz.device).repeat_interleave(K)
-            cls = decoder.get_cls_from_pred(decoder(f, xyz.reshape(n * K, 3), idx)).view(n, K) * inside
-            inters.append(((cls == 1) & (lab == 1)).sum(1).cpu())
-            unions.append(((cls == 1) | (lab == 1)).sum(1).cpu())
+            logits = decoder(f, xyz.reshape(n * K, 3), idx)
+            inter, union = occ_iou_counts_aten(decoder, logits, occ_label, xyz, pb[:, 3:6] / 2 if outside else None)
+            inters.append(inter.cpu())
+            unions.append(union.cpu())
             gt_boxes.append(gb.cpu())
         return dict(inters=inters, unions=unions, gt_boxes=gt_boxes)
 
@@ -496,6 +517,22 @@ class TrackletDetectorOCC(nn.Module):
 
     def forward(self, return_loss=True, **kwargs):
         return self.forward_train(**kwargs) if return_loss else self.forward_test(**kwargs)
+
+
+def occ_iou_counts_aten(decoder, logits, occ_label, xyz, half=None):
+    """The ATen form of one chunk's occupancy counts in test_occ (tracklet_roi_head_occ.py:459-486), kept for
+    OCOCC_OCC_IOU_KERNEL=0, for cls_dim > 1 and as the yardstick of csrc/occ_iou_count.hip: logits [n*K, cls_dim] of
+    the query points xyz [n, K, 3] (RoI frame), occ_label [K] long; with half [n, 3] (ignore_outside_occ) a cell outside
+    -half <= xyz <= half is predicted empty.  -> inter [n], union [n] (int64, on the device)."""
+    n, K = xyz.size(0), xyz.size(1)
+    lab = occ_label[None].repeat(n, 1)
+    if half is not None:
+        half = half[:, None]
+        inside = (xyz >= -half).all(-1) & (xyz <= half).all(-1)
+    else:
+        inside = torch.ones((n, K), dtype=torch.bool, device=xyz.device)
+    cls = decoder.get_cls_from_pred(logits).view(n, K) * inside
+    return ((cls == 1) & (lab == 1)).sum(1), ((cls == 1) | (lab == 1)).sum(1)
 
 
 def occupancy_iou_metrics(results):

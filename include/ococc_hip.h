@@ -606,74 +606,41 @@ int ococc_group_rank_i32(const int32_t* keys, int64_t n, int64_t key_bound, int3
  * B7  window attention core  out = softmax(q k^T * scale + key mask) v  per (window, head)
  * replaces the attention inside nn.MultiheadAttention as WindowAttention calls it on padded
  * [num_windows, max_tokens, C] tensors (mmdet3d/models/sst/sst_basic_block_v2.py:41-75).
- * q, k, v: bf16 rows (window*max_tokens + token) with the given row strides (elements), head h in
- * columns [16h, 16h+16); key_len [num_windows] int32 = valid tokens (a prefix) of each window;
- * out bf16 like q; lse [num_windows, num_heads, max_tokens] f32 (log-sum-exp of the scaled
- * scores, saved for backward).  head_dim must be 16, max_tokens <= 160.
+ * q, k, v: bf16 rows with the given row strides (elements), head h in columns [16h, 16h+16);
+ * key_len [num_windows] int32 = valid tokens (a prefix) of each window; out bf16 like q;
+ * lse [num_windows, num_heads, max_tokens] f32 (log-sum-exp of the scaled scores, saved for
+ * backward).  head_dim must be 16, max_tokens <= 160.
+ *
+ * Layout.  token_index == NULL: padded, the row of window slot t is window * max_tokens + t.
+ * Otherwise flat: q/k/v/out (and dout, dq/dk/dv) are [num_tokens, .] tensors in the model's token
+ * order and token_index [num_windows * max_tokens] int32 names the row of every window slot (-1 =
+ * padding; valid slots are a prefix of each window, key_len of them).  The kernel gathers a
+ * window's tokens itself and writes every output row exactly once, so the padded [nW, T, C] copies
+ * that flat2window / window2flat build in the reference (sst_ops.py:66-148) never exist.  lse
+ * stays [nW, H, T] in both layouts.
+ *
+ * Dropout: nn.MultiheadAttention(dropout=dropout_p) as SST's WindowAttention builds it
+ * (mmdet3d/models/sst/sst_basic_block_v2.py:16-35, 79-81; CosineMultiheadAttention, cosine_msa.py:181-182, 431-433).
+ * dropout_p in [0, 1); seed is a device pointer to one uint64 (required when dropout_p > 0, may be NULL otherwise; read
+ * by the kernel, so a captured graph that redraws it draws a new mask per replay).  After the key mask and the softmax a
+ * probability is kept iff hash24(seed, head, query row, key row) >= floor(dropout_p * 2^24) and then scaled by
+ * 1 / (1 - dropout_p) in f32, rounded to bf16 as the P V operand; rows are the rows of the layout above (token_index
+ * rows, or window * max_tokens + slot).  lse stays that of the undropped softmax; the backward regenerates the mask
+ * (dV = P_drop^T dO, dS = P o (keep dP / (1 - p) - delta), delta = dO . O).  dropout_p = 0 runs no mask at all.
  * ------------------------------------------------------------------------ */
 int ococc_window_attn_fwd_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
-                               int64_t k_stride, int64_t v_stride, const int32_t* key_len,
-                               int64_t num_windows, int32_t max_tokens, int32_t num_heads, int32_t head_dim,
-                               float scale, uint16_t* out, int64_t out_stride, float* lse,
+                               int64_t k_stride, int64_t v_stride, const int32_t* token_index,
+                               const int32_t* key_len, int64_t num_windows, int32_t max_tokens,
+                               int32_t num_heads, int32_t head_dim, float scale, uint16_t* out,
+                               int64_t out_stride, float* lse, float dropout_p, const uint64_t* seed,
                                ococc_stream_t stream);
 int ococc_window_attn_bwd_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
                                int64_t k_stride, int64_t v_stride, const uint16_t* out, const uint16_t* dout,
-                               int64_t o_stride, const float* lse, const int32_t* key_len,
-                               int64_t num_windows, int32_t max_tokens, int32_t num_heads, int32_t head_dim,
-                               float scale, uint16_t* dq, uint16_t* dk, uint16_t* dv, int64_t dq_stride,
-                               int64_t dk_stride, int64_t dv_stride, ococc_stream_t stream);
-
-/* Flat-token forms of the two calls above: q/k/v/out (and dout, dq/dk/dv) are [num_tokens, .] tensors in
- * the model's token order and token_index [num_windows * max_tokens] int32 names the row of every window
- * slot (-1 = padding; valid slots are a prefix of each window, key_len of them).  The kernel gathers a
- * window's tokens itself and writes every output row exactly once, so the padded [nW, T, C] copies that
- * flat2window / window2flat build in the reference (sst_ops.py:66-148) never exist. lse stays [nW, H, T]. */
-int ococc_window_attn_fwd_gather_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
-                                      int64_t k_stride, int64_t v_stride, const int32_t* token_index,
-                                      const int32_t* key_len, int64_t num_windows, int32_t max_tokens,
-                                      int32_t num_heads, int32_t head_dim, float scale, uint16_t* out,
-                                      int64_t out_stride, float* lse, ococc_stream_t stream);
-int ococc_window_attn_bwd_gather_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
-                                      int64_t k_stride, int64_t v_stride, const uint16_t* out, const uint16_t* dout,
-                                      int64_t o_stride, const float* lse, const int32_t* token_index,
-                                      const int32_t* key_len, int64_t num_windows, int32_t max_tokens,
-                                      int32_t num_heads, int32_t head_dim, float scale, uint16_t* dq, uint16_t* dk,
-                                      uint16_t* dv, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
-                                      ococc_stream_t stream);
-
-/* Dropout twins of the four calls above: nn.MultiheadAttention(dropout=dropout_p) as SST's WindowAttention builds it
- * (mmdet3d/models/sst/sst_basic_block_v2.py:16-35, 79-81; CosineMultiheadAttention, cosine_msa.py:181-182, 431-433).
- * Same arguments plus dropout_p in [0, 1) and seed, a device pointer to one uint64 (required when dropout_p > 0; read by
- * the kernel, so a captured graph that redraws it draws a new mask per replay).  After the key mask and the softmax a
- * probability is kept iff hash24(seed, head, query row, key row) >= floor(dropout_p * 2^24) and then scaled by
- * 1 / (1 - dropout_p) in f32, rounded to bf16 as the P V operand; rows are token_index rows (gather forms) or
- * window * max_tokens + slot (padded forms).  lse stays that of the undropped softmax; the backward regenerates the mask
- * (dV = P_drop^T dO, dS = P o (keep dP / (1 - p) - delta), delta = dO . O).  dropout_p = 0: the calls above. */
-int ococc_window_attn_fwd_drop_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
-                                    int64_t k_stride, int64_t v_stride, const int32_t* key_len,
-                                    int64_t num_windows, int32_t max_tokens, int32_t num_heads, int32_t head_dim,
-                                    float scale, uint16_t* out, int64_t out_stride, float* lse, float dropout_p,
-                                    const uint64_t* seed, ococc_stream_t stream);
-int ococc_window_attn_bwd_drop_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
-                                    int64_t k_stride, int64_t v_stride, const uint16_t* out, const uint16_t* dout,
-                                    int64_t o_stride, const float* lse, const int32_t* key_len,
-                                    int64_t num_windows, int32_t max_tokens, int32_t num_heads, int32_t head_dim,
-                                    float scale, uint16_t* dq, uint16_t* dk, uint16_t* dv, int64_t dq_stride,
-                                    int64_t dk_stride, int64_t dv_stride, float dropout_p, const uint64_t* seed,
-                                    ococc_stream_t stream);
-int ococc_window_attn_fwd_gather_drop_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
-                                           int64_t k_stride, int64_t v_stride, const int32_t* token_index,
-                                           const int32_t* key_len, int64_t num_windows, int32_t max_tokens,
-                                           int32_t num_heads, int32_t head_dim, float scale, uint16_t* out,
-                                           int64_t out_stride, float* lse, float dropout_p, const uint64_t* seed,
-                                           ococc_stream_t stream);
-int ococc_window_attn_bwd_gather_drop_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, int64_t q_stride,
-                                           int64_t k_stride, int64_t v_stride, const uint16_t* out, const uint16_t* dout,
-                                           int64_t o_stride, const float* lse, const int32_t* token_index,
-                                           const int32_t* key_len, int64_t num_windows, int32_t max_tokens,
-                                           int32_t num_heads, int32_t head_dim, float scale, uint16_t* dq, uint16_t* dk,
-                                           uint16_t* dv, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
-                                           float dropout_p, const uint64_t* seed, ococc_stream_t stream);
+                               int64_t o_stride, const float* lse, const int32_t* token_index,
+                               const int32_t* key_len, int64_t num_windows, int32_t max_tokens,
+                               int32_t num_heads, int32_t head_dim, float scale, uint16_t* dq, uint16_t* dk,
+                               uint16_t* dv, int64_t dq_stride, int64_t dk_stride, int64_t dv_stride,
+                               float dropout_p, const uint64_t* seed, ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * B7, fused  one SST encoder layer as two tile kernels per direction
@@ -711,70 +678,34 @@ int64_t ococc_window_block_partial_rows(int64_t num_tiles);
 int ococc_window_tile_plan(const int32_t* win_len, const int64_t* win_off, const int32_t* tok, int64_t num_windows,
                            int32_t tile_slots, int64_t cap_tiles, int32_t* tile_rows, int32_t* tile_span,
                            int32_t* num_tiles, void* workspace, int64_t workspace_bytes, ococc_stream_t stream);
+/* Attention block.  Inference: attn_save = lse_save = NULL.  A training step that keeps the attention output and the
+ * softmax's log-sum-exp (round 5) passes both, 16-byte aligned: the forward also writes attn_save [num_tokens, d_model]
+ * bf16 (rows of the plan's tokens) and lse_save [num_tokens, num_heads] f32, and the backward, given attn_saved /
+ * lse_saved and attn_out = NULL, reads them back instead of running the attention forward again (28 % of its time, for
+ * 288 B per token) and no longer writes attn_out -- the weight gradient of the out-projection reads attn_saved.  Without
+ * them (attn_saved = lse_saved = NULL) the backward recomputes the attention and writes attn_out; exactly one of the two
+ * forms must be given.  Same results either way (the attention forward it skips is deterministic).
+ *
+ * Dropout: the attention of EncoderLayer with its reference default dropout=0.1 (sst_basic_block_v2.py:79-81, 133 ->
+ * nn.MultiheadAttention(dropout=...) / CosineMultiheadAttention, cosine_msa.py:181-182).  dropout_p and seed as for
+ * ococc_window_attn_fwd_bf16; the mask is that of the window-attention calls over the flat rows of tile_rows -- the gather
+ * kernels and these make the same decision for the same (seed, head, query row, key row).  lse_save stays the
+ * log-sum-exp of the undropped softmax; attn_save / attn_out is the dropped attention output (the out-projection's
+ * input).  dropout_p = 0 runs no mask at all. */
 int ococc_window_attn_block_fwd_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
                                      const int32_t* tile_span, int64_t num_tiles, int32_t d_model, int32_t num_heads,
                                      const uint16_t* wqkv_frag, const float* bqkv, const uint16_t* wo_frag,
                                      const float* bo, const float* ln_weight, const float* ln_bias, float eps,
-                                     uint16_t* y, ococc_stream_t stream);
+                                     uint16_t* y, uint16_t* attn_save, float* lse_save, float dropout_p,
+                                     const uint64_t* seed, ococc_stream_t stream);
 int ococc_window_attn_block_bwd_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
                                      const int32_t* tile_rows, const int32_t* tile_span, int64_t num_tiles,
                                      int32_t d_model, int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
                                      const uint16_t* wo_frag, const float* bo, const float* ln_weight, float eps,
-                                     const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag, uint16_t* dx,
-                                     uint16_t* dqkv, uint16_t* dz, uint16_t* attn_out, float* ln_partial,
+                                     const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag, const uint16_t* attn_saved,
+                                     const float* lse_saved, uint16_t* dx, uint16_t* dqkv, uint16_t* dz,
+                                     uint16_t* attn_out, float* ln_partial, float dropout_p, const uint64_t* seed,
                                      ococc_stream_t stream);
-/* The same pair for a training step that keeps the attention output and the softmax's log-sum-exp (round 5): the forward
- * also writes attn_save [num_tokens, d_model] bf16 (rows of the plan's tokens) and lse_save [num_tokens, num_heads] f32; the
- * backward reads them back instead of running the attention forward again (28 % of its time, for 288 B per token) and
- * no longer writes attn_out -- the weight gradient of the out-projection reads attn_saved.  Same results as the pair
- * above (the attention forward it skips is deterministic). */
-int ococc_window_attn_block_train_fwd_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
-                                           const int32_t* tile_span, int64_t num_tiles, int32_t d_model, int32_t num_heads,
-                                           const uint16_t* wqkv_frag, const float* bqkv, const uint16_t* wo_frag,
-                                           const float* bo, const float* ln_weight, const float* ln_bias, float eps,
-                                           uint16_t* y, uint16_t* attn_save, float* lse_save, ococc_stream_t stream);
-int ococc_window_attn_block_bwd_saved_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
-                                           const int32_t* tile_rows, const int32_t* tile_span, int64_t num_tiles,
-                                           int32_t d_model, int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
-                                           const uint16_t* wo_frag, const float* bo, const float* ln_weight, float eps,
-                                           const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag,
-                                           const uint16_t* attn_saved, const float* lse_saved, uint16_t* dx, uint16_t* dqkv,
-                                           uint16_t* dz, float* ln_partial, ococc_stream_t stream);
-/* Dropout twins of the four attention-block calls above (the attention of EncoderLayer with its reference default
- * dropout=0.1: sst_basic_block_v2.py:79-81, 133 -> nn.MultiheadAttention(dropout=...) / CosineMultiheadAttention,
- * cosine_msa.py:181-182).  Same arguments plus dropout_p in [0, 1) and seed (device uint64, required when dropout_p > 0).
- * The mask is that of ococc_window_attn_*_drop_bf16 over the flat rows of tile_rows -- the gather kernels and these make
- * the same decision for the same (seed, head, query row, key row).  lse_save stays the log-sum-exp of the undropped
- * softmax; attn_save / attn_out is the dropped attention output (the out-projection's input).  dropout_p = 0: the calls
- * above. */
-int ococc_window_attn_block_fwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
-                                          const int32_t* tile_span, int64_t num_tiles, int32_t d_model, int32_t num_heads,
-                                          const uint16_t* wqkv_frag, const float* bqkv, const uint16_t* wo_frag,
-                                          const float* bo, const float* ln_weight, const float* ln_bias, float eps,
-                                          uint16_t* y, float dropout_p, const uint64_t* seed, ococc_stream_t stream);
-int ococc_window_attn_block_bwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
-                                          const int32_t* tile_rows, const int32_t* tile_span, int64_t num_tiles,
-                                          int32_t d_model, int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
-                                          const uint16_t* wo_frag, const float* bo, const float* ln_weight, float eps,
-                                          const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag, uint16_t* dx,
-                                          uint16_t* dqkv, uint16_t* dz, uint16_t* attn_out, float* ln_partial,
-                                          float dropout_p, const uint64_t* seed, ococc_stream_t stream);
-int ococc_window_attn_block_train_fwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
-                                                const int32_t* tile_span, int64_t num_tiles, int32_t d_model,
-                                                int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
-                                                const uint16_t* wo_frag, const float* bo, const float* ln_weight,
-                                                const float* ln_bias, float eps, uint16_t* y, uint16_t* attn_save,
-                                                float* lse_save, float dropout_p, const uint64_t* seed,
-                                                ococc_stream_t stream);
-int ococc_window_attn_block_bwd_saved_drop_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
-                                                const int32_t* tile_rows, const int32_t* tile_span, int64_t num_tiles,
-                                                int32_t d_model, int32_t num_heads, const uint16_t* wqkv_frag,
-                                                const float* bqkv, const uint16_t* wo_frag, const float* bo,
-                                                const float* ln_weight, float eps, const uint16_t* wo_t_frag,
-                                                const uint16_t* wqkv_t_frag, const uint16_t* attn_saved,
-                                                const float* lse_saved, uint16_t* dx, uint16_t* dqkv, uint16_t* dz,
-                                                float* ln_partial, float dropout_p, const uint64_t* seed,
-                                                ococc_stream_t stream);
 int ococc_token_ffn_block_fwd_bf16(const uint16_t* x, int64_t num_tokens, int32_t d_model, int32_t d_ffn,
                                    const uint16_t* w1_frag, const float* b1, const uint16_t* w2_frag, const float* b2,
                                    const float* ln_weight, const float* ln_bias, float eps, int32_t act, uint16_t* y,

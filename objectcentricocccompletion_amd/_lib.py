@@ -112,50 +112,21 @@ SIGNATURES = {
     'ococc_occ_iou_count': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_vp, c_i64, c_i64, c_vp]),
     'ococc_group_rank_workspace_bytes': (c_i64, [c_i64, c_i64]),
     'ococc_group_rank_i32': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_window_attn_fwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32,
-                                           c_f32, c_vp, c_i64, c_vp, c_vp]),
-    'ococc_window_attn_bwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
-                                           c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
-    'ococc_window_attn_fwd_gather_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32,
-                                                  c_i32, c_f32, c_vp, c_i64, c_vp, c_vp]),
-    'ococc_window_attn_bwd_gather_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp,
-                                                  c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_i64,
-                                                  c_i64, c_vp]),
-    # dropout twins: the arguments of the four above + dropout_p (f32) + device seed pointer, before the stream
-    'ococc_window_attn_fwd_drop_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32,
-                                                c_f32, c_vp, c_i64, c_vp, c_f32, c_vp, c_vp]),
-    'ococc_window_attn_bwd_drop_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp,
-                                                c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
-                                                c_f32, c_vp, c_vp]),
-    'ococc_window_attn_fwd_gather_drop_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i32,
-                                                       c_i32, c_i32, c_f32, c_vp, c_i64, c_vp, c_f32, c_vp, c_vp]),
-    'ococc_window_attn_bwd_gather_drop_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp,
-                                                       c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp,
-                                                       c_i64, c_i64, c_i64, c_f32, c_vp, c_vp]),
+    'ococc_window_attn_fwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32,
+                                           c_f32, c_vp, c_i64, c_vp, c_f32, c_vp, c_vp]),
+    'ococc_window_attn_bwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                           c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
+                                           c_f32, c_vp, c_vp]),
     'ococc_linear_fragments_bf16': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
                                             ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp), c_vp]),
     'ococc_window_tile_plan_workspace_bytes': (c_i64, [c_i64]),
     'ococc_window_block_partial_rows': (c_i64, [c_i64]),
     'ococc_window_tile_plan': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'ococc_window_attn_block_fwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
-                                                 c_vp, c_vp, c_f32, c_vp, c_vp]),
+                                                 c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp]),
     'ococc_window_attn_block_bwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp,
-                                                 c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_window_attn_block_train_fwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
-                                                       c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_window_attn_block_bwd_saved_bf16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp,
-                                                       c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_window_attn_block_fwd_drop_bf16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp,
-                                                      c_vp, c_vp, c_vp, c_f32, c_vp, c_f32, c_vp, c_vp]),
-    'ococc_window_attn_block_bwd_drop_bf16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp,
-                                                      c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                                      c_f32, c_vp, c_vp]),
-    'ococc_window_attn_block_train_fwd_drop_bf16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp,
-                                                            c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_f32, c_vp,
-                                                            c_vp]),
-    'ococc_window_attn_block_bwd_saved_drop_bf16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp,
-                                                            c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                                            c_vp, c_vp, c_vp, c_f32, c_vp, c_vp]),
+                                                 c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                 c_f32, c_vp, c_vp]),
     'ococc_token_ffn_block_fwd_bf16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32,
                                                c_i32, c_vp, c_vp]),
     'ococc_token_ffn_block_bwd_bf16': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32,

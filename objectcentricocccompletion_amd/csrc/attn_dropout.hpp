@@ -4,9 +4,9 @@
 //
 // The mask is a counter-based hash: nothing is stored, the backward kernels regenerate it from the same seed.
 //   keep(seed, head, q, k) = hash24(seed, head, q, k) >= floor(p * 2^24)
-// q, k are the flat token rows of the query and the key (rows of the [V, *] tensors; the padded entry points use the
-// padded row w * T + t), so the tile kernels and the per-window gather kernels make the same decision for the same
-// pair.  The tuple is folded in one word at a time, each fold a full 32-bit finaliser (murmur3 fmix32) of
+// q, k are the flat token rows of the query and the key (rows of the [V, *] tensors; the padded layout, token_index =
+// NULL, uses the padded row w * T + t), so the tile kernels and the per-window gather kernels make the same decision
+// for the same pair.  The tuple is folded in one word at a time, each fold a full 32-bit finaliser (murmur3 fmix32) of
 // (state ^ word) * golden + c: no linear counter over q * N + k that would wrap around at millions of rows, and
 // (q, k) and (k, q) enter in different rounds, so their decisions are independent.
 #pragma once

@@ -1514,12 +1514,14 @@ extern "C" int ococc_window_tile_plan(const int32_t* win_len, const int64_t* win
 #define OCOCC_BLOCK_DIMS_OK(d_model, heads, ffn) \
   OCOCC_REQUIRE((d_model) == E && (heads) == NH && (ffn) == FF, "the fused encoder-layer kernels are built for d_model 128, 8 heads, feed-forward 256")
 
-namespace {
-int attn_block_fwd(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows, const int32_t* tile_span,
-                   int64_t num_tiles, int32_t d_model, int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
-                   const uint16_t* wo_frag, const float* bo, const float* ln_weight, const float* ln_bias, float eps,
-                   uint16_t* y, uint16_t* attn_save, float* lse_save, float dropout_p, const uint64_t* seed,
-                   ococc_stream_t stream) {
+// attn_save / lse_save: both NULL (inference) or both set (training step that keeps them for the backward)
+extern "C" int ococc_window_attn_block_fwd_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
+                                                const int32_t* tile_span, int64_t num_tiles, int32_t d_model,
+                                                int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
+                                                const uint16_t* wo_frag, const float* bo, const float* ln_weight,
+                                                const float* ln_bias, float eps, uint16_t* y, uint16_t* attn_save,
+                                                float* lse_save, float dropout_p, const uint64_t* seed,
+                                                ococc_stream_t stream) {
   OCOCC_BLOCK_DIMS_OK(d_model, num_heads, FF);
   OCOCC_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0, 1)");
   OCOCC_REQUIRE(dropout_p == 0.f || seed, "dropout_p > 0 needs the device seed");
@@ -1530,6 +1532,8 @@ int attn_block_fwd(const uint16_t* x, const uint16_t* pos, const int32_t* tile_r
   OCOCC_REQUIRE(aligned16(x) && aligned16(pos) && aligned16(y) && aligned16(wqkv_frag) && aligned16(wo_frag) &&
                     aligned16(bqkv) && aligned16(bo) && aligned16(ln_weight) && aligned16(ln_bias),
                 "buffers must be 16-byte aligned");
+  OCOCC_REQUIRE((attn_save == nullptr) == (lse_save == nullptr) && aligned16(attn_save) && aligned16(lse_save),
+                "attn_save / lse_save: both NULL, or both 16-byte aligned device buffers");
   const OcoccDrop dp = ococc_drop_params(dropout_p);
   const void* kern = dp.thr ? (const void*)window_attn_block_fwd_kernel<true> : (const void*)window_attn_block_fwd_kernel<false>;
   OCOCC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, attn_lds<4>()));
@@ -1544,44 +1548,26 @@ int attn_block_fwd(const uint16_t* x, const uint16_t* pos, const int32_t* tile_r
   OCOCC_CHECK_LAUNCH();
   return OCOCC_OK;
 }
-}  // namespace
 
-extern "C" int ococc_window_attn_block_fwd_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
-                                                const int32_t* tile_span, int64_t num_tiles, int32_t d_model,
-                                                int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
-                                                const uint16_t* wo_frag, const float* bo, const float* ln_weight,
-                                                const float* ln_bias, float eps, uint16_t* y, ococc_stream_t stream) {
-  return attn_block_fwd(x, pos, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo, ln_weight,
-                        ln_bias, eps, y, nullptr, nullptr, 0.f, nullptr, stream);
-}
-
-extern "C" int ococc_window_attn_block_train_fwd_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
-                                                      const int32_t* tile_span, int64_t num_tiles, int32_t d_model,
-                                                      int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
-                                                      const uint16_t* wo_frag, const float* bo, const float* ln_weight,
-                                                      const float* ln_bias, float eps, uint16_t* y, uint16_t* attn_save,
-                                                      float* lse_save, ococc_stream_t stream) {
-  OCOCC_REQUIRE(num_tiles == 0 || (attn_save && lse_save && aligned16(attn_save) && aligned16(lse_save)),
-                "attn_save / lse_save: 16-byte aligned device buffers");
-  return attn_block_fwd(x, pos, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo, ln_weight,
-                        ln_bias, eps, y, attn_save, lse_save, 0.f, nullptr, stream);
-}
-
-namespace {
-int attn_block_bwd(const uint16_t* x, const uint16_t* pos, const uint16_t* dy, const int32_t* tile_rows,
-                   const int32_t* tile_span, int64_t num_tiles, int32_t d_model, int32_t num_heads, const uint16_t* wqkv_frag,
-                   const float* bqkv, const uint16_t* wo_frag, const float* bo, const float* ln_weight, float eps,
-                   const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag, uint16_t* dx, uint16_t* dqkv, uint16_t* dz,
-                   uint16_t* attn_out, float* ln_partial, const uint16_t* attn_saved, const float* lse_saved,
-                   float dropout_p, const uint64_t* seed, ococc_stream_t stream) {
+// either attn_saved / lse_saved (saved by a training forward; attn_out = NULL) or attn_out (recompute the attention)
+extern "C" int ococc_window_attn_block_bwd_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
+                                                const int32_t* tile_rows, const int32_t* tile_span,
+                                                int64_t num_tiles, int32_t d_model, int32_t num_heads,
+                                                const uint16_t* wqkv_frag, const float* bqkv, const uint16_t* wo_frag,
+                                                const float* bo, const float* ln_weight, float eps,
+                                                const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag,
+                                                const uint16_t* attn_saved, const float* lse_saved, uint16_t* dx,
+                                                uint16_t* dqkv, uint16_t* dz, uint16_t* attn_out, float* ln_partial,
+                                                float dropout_p, const uint64_t* seed, ococc_stream_t stream) {
   OCOCC_BLOCK_DIMS_OK(d_model, num_heads, FF);
   OCOCC_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "dropout_p must be in [0, 1)");
   OCOCC_REQUIRE(dropout_p == 0.f || seed, "dropout_p > 0 needs the device seed");
   OCOCC_REQUIRE(num_tiles >= 0, "bad sizes");
   if (num_tiles == 0) return OCOCC_OK;
   OCOCC_REQUIRE(x && dy && tile_rows && tile_span && wqkv_frag && bqkv && wo_frag && bo && ln_weight && wo_t_frag &&
-                    wqkv_t_frag && dx && dqkv && dz && (attn_out || attn_saved) && ln_partial,
+                    wqkv_t_frag && dx && dqkv && dz && ln_partial,
                 "null pointer");
+  OCOCC_REQUIRE((attn_out == nullptr) != (attn_saved == nullptr), "pass either attn_saved / lse_saved or attn_out");
   OCOCC_REQUIRE((attn_saved == nullptr) == (lse_saved == nullptr) && aligned16(attn_saved) && aligned16(lse_saved),
                 "attn_saved and lse_saved go together, 16-byte aligned");
   OCOCC_REQUIRE(aligned16(x) && aligned16(pos) && aligned16(dy) && aligned16(dx) && aligned16(dqkv) && aligned16(dz) &&
@@ -1603,88 +1589,6 @@ int attn_block_bwd(const uint16_t* x, const uint16_t* pos, const uint16_t* dy, c
                        dp.thr, dp.scale, seed);
   OCOCC_CHECK_LAUNCH();
   return OCOCC_OK;
-}
-}  // namespace
-
-extern "C" int ococc_window_attn_block_bwd_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
-                                                const int32_t* tile_rows, const int32_t* tile_span,
-                                                int64_t num_tiles, int32_t d_model, int32_t num_heads,
-                                                const uint16_t* wqkv_frag, const float* bqkv, const uint16_t* wo_frag,
-                                                const float* bo, const float* ln_weight, float eps,
-                                                const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag, uint16_t* dx,
-                                                uint16_t* dqkv, uint16_t* dz, uint16_t* attn_out, float* ln_partial,
-                                                ococc_stream_t stream) {
-  return attn_block_bwd(x, pos, dy, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo,
-                        ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, attn_out, ln_partial, nullptr, nullptr, 0.f,
-                        nullptr, stream);
-}
-
-extern "C" int ococc_window_attn_block_bwd_saved_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
-                                                      const int32_t* tile_rows, const int32_t* tile_span,
-                                                      int64_t num_tiles, int32_t d_model, int32_t num_heads,
-                                                      const uint16_t* wqkv_frag, const float* bqkv, const uint16_t* wo_frag,
-                                                      const float* bo, const float* ln_weight, float eps,
-                                                      const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag,
-                                                      const uint16_t* attn_saved, const float* lse_saved, uint16_t* dx,
-                                                      uint16_t* dqkv, uint16_t* dz, float* ln_partial,
-                                                      ococc_stream_t stream) {
-  OCOCC_REQUIRE(num_tiles == 0 || (attn_saved && lse_saved), "null pointer");
-  return attn_block_bwd(x, pos, dy, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo,
-                        ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, nullptr, ln_partial, attn_saved, lse_saved,
-                        0.f, nullptr, stream);
-}
-
-// ---- dropout twins of the four attention-block entry points: their arguments plus dropout_p in [0, 1) and the device seed
-extern "C" int ococc_window_attn_block_fwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
-                                                     const int32_t* tile_span, int64_t num_tiles, int32_t d_model,
-                                                     int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
-                                                     const uint16_t* wo_frag, const float* bo, const float* ln_weight,
-                                                     const float* ln_bias, float eps, uint16_t* y, float dropout_p,
-                                                     const uint64_t* seed, ococc_stream_t stream) {
-  return attn_block_fwd(x, pos, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo, ln_weight,
-                        ln_bias, eps, y, nullptr, nullptr, dropout_p, seed, stream);
-}
-
-extern "C" int ococc_window_attn_block_train_fwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const int32_t* tile_rows,
-                                                           const int32_t* tile_span, int64_t num_tiles, int32_t d_model,
-                                                           int32_t num_heads, const uint16_t* wqkv_frag, const float* bqkv,
-                                                           const uint16_t* wo_frag, const float* bo, const float* ln_weight,
-                                                           const float* ln_bias, float eps, uint16_t* y, uint16_t* attn_save,
-                                                           float* lse_save, float dropout_p, const uint64_t* seed,
-                                                           ococc_stream_t stream) {
-  OCOCC_REQUIRE(num_tiles == 0 || (attn_save && lse_save && aligned16(attn_save) && aligned16(lse_save)),
-                "attn_save / lse_save: 16-byte aligned device buffers");
-  return attn_block_fwd(x, pos, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo, ln_weight,
-                        ln_bias, eps, y, attn_save, lse_save, dropout_p, seed, stream);
-}
-
-extern "C" int ococc_window_attn_block_bwd_drop_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
-                                                     const int32_t* tile_rows, const int32_t* tile_span,
-                                                     int64_t num_tiles, int32_t d_model, int32_t num_heads,
-                                                     const uint16_t* wqkv_frag, const float* bqkv, const uint16_t* wo_frag,
-                                                     const float* bo, const float* ln_weight, float eps,
-                                                     const uint16_t* wo_t_frag, const uint16_t* wqkv_t_frag, uint16_t* dx,
-                                                     uint16_t* dqkv, uint16_t* dz, uint16_t* attn_out, float* ln_partial,
-                                                     float dropout_p, const uint64_t* seed, ococc_stream_t stream) {
-  return attn_block_bwd(x, pos, dy, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo,
-                        ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, attn_out, ln_partial, nullptr, nullptr,
-                        dropout_p, seed, stream);
-}
-
-extern "C" int ococc_window_attn_block_bwd_saved_drop_bf16(const uint16_t* x, const uint16_t* pos, const uint16_t* dy,
-                                                           const int32_t* tile_rows, const int32_t* tile_span,
-                                                           int64_t num_tiles, int32_t d_model, int32_t num_heads,
-                                                           const uint16_t* wqkv_frag, const float* bqkv,
-                                                           const uint16_t* wo_frag, const float* bo, const float* ln_weight,
-                                                           float eps, const uint16_t* wo_t_frag,
-                                                           const uint16_t* wqkv_t_frag, const uint16_t* attn_saved,
-                                                           const float* lse_saved, uint16_t* dx, uint16_t* dqkv, uint16_t* dz,
-                                                           float* ln_partial, float dropout_p, const uint64_t* seed,
-                                                           ococc_stream_t stream) {
-  OCOCC_REQUIRE(num_tiles == 0 || (attn_saved && lse_saved), "null pointer");
-  return attn_block_bwd(x, pos, dy, tile_rows, tile_span, num_tiles, d_model, num_heads, wqkv_frag, bqkv, wo_frag, bo,
-                        ln_weight, eps, wo_t_frag, wqkv_t_frag, dx, dqkv, dz, nullptr, ln_partial, attn_saved, lse_saved,
-                        dropout_p, seed, stream);
 }
 
 extern "C" int ococc_token_ffn_block_fwd_bf16(const uint16_t* x, int64_t num_tokens, int32_t d_model, int32_t d_ffn,

@@ -10,9 +10,9 @@ ococc_window_tile_plan); windows of drop levels above 64 tokens keep the per-win
 own (sst_modules.WindowMultiheadAttention.forward_flat) and both halves meet again in the FFN block, which does not
 care about windows.  Nothing but the layer input is saved for backward: the backward kernels recompute.
 
-Attention dropout (AttnBlock's ``p`` > 0 with a device int64 ``seed``): the ococc_window_attn_block_*_drop_bf16 twins drop
-and rescale the softmax's probabilities by a hash of (seed, head, flat query row, flat key row) -- the mask the per-window
-gather kernels draw for the same rows -- and the backward regenerates it from the saved seed."""
+Attention dropout (AttnBlock's ``p`` > 0 with a device int64 ``seed``, the block kernels' dropout_p / seed arguments): the
+kernels drop and rescale the softmax's probabilities by a hash of (seed, head, flat query row, flat key row) -- the mask
+the per-window gather kernels draw for the same rows -- and the backward regenerates it from the saved seed."""
 import ctypes
 import os
 
@@ -152,25 +152,10 @@ class AttnBlock(torch.autograd.Function):
         if keep:
             o_save = (torch.empty if covered else torch.zeros)((V, E), dtype=torch.bfloat16, device=x.device)
             lse_save = torch.empty((V, num_heads), dtype=torch.float32, device=x.device)
-            if p > 0:
-                _run('window_attn_block_fwd', flops, lambda: L.check(L.lib.ococc_window_attn_block_train_fwd_drop_bf16(
-                    L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, num_heads, L.ptr(wqkv),
-                    L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), L.ptr(b1), float(eps), L.ptr(y), L.ptr(o_save),
-                    L.ptr(lse_save), float(p), L.ptr(seed), L.stream()), 'window_attn_block_train_fwd_drop'))
-            else:
-                _run('window_attn_block_fwd', flops, lambda: L.check(L.lib.ococc_window_attn_block_train_fwd_bf16(
-                    L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, num_heads, L.ptr(wqkv),
-                    L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), L.ptr(b1), float(eps), L.ptr(y), L.ptr(o_save),
-                    L.ptr(lse_save), L.stream()), 'window_attn_block_train_fwd'))
-        elif p > 0:
-            _run('window_attn_block_fwd', flops, lambda: L.check(L.lib.ococc_window_attn_block_fwd_drop_bf16(
-                L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, num_heads, L.ptr(wqkv), L.ptr(bq),
-                L.ptr(wo), L.ptr(bo), L.ptr(g1), L.ptr(b1), float(eps), L.ptr(y), float(p), L.ptr(seed), L.stream()),
-                'window_attn_block_fwd_drop'))
-        else:
-            _run('window_attn_block_fwd', flops, lambda: L.check(L.lib.ococc_window_attn_block_fwd_bf16(
-                L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, num_heads, L.ptr(wqkv), L.ptr(bq),
-                L.ptr(wo), L.ptr(bo), L.ptr(g1), L.ptr(b1), float(eps), L.ptr(y), L.stream()), 'window_attn_block_fwd'))
+        _run('window_attn_block_fwd', flops, lambda: L.check(L.lib.ococc_window_attn_block_fwd_bf16(
+            L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, num_heads, L.ptr(wqkv), L.ptr(bq),
+            L.ptr(wo), L.ptr(bo), L.ptr(g1), L.ptr(b1), float(eps), L.ptr(y), L.ptr(o_save), L.ptr(lse_save), float(p),
+            L.ptr(seed), L.stream()), 'window_attn_block_fwd'))
         ctx.save_for_backward(x, pos, in_w, in_b, out_w, out_b, ln_w, *([o_save, lse_save] if keep else []))
         ctx.misc = (plan, float(eps), int(num_heads), bool(covered), wqkv, wo, bq, bo, g1)
         ctx.drop = (float(p), seed)
@@ -191,31 +176,14 @@ class AttnBlock(torch.autograd.Function):
         dz = new((V, E), dtype=torch.bfloat16, device=x.device)
         prow = int(L.lib.ococc_window_block_partial_rows(plan.num_tiles))
         lnp = torch.empty((prow, 2, E), dtype=torch.float32, device=x.device)
-        if kept:
-            o, lse = kept
-            if p > 0:
-                L.check(L.lib.ococc_window_attn_block_bwd_saved_drop_bf16(
-                    L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv),
-                    L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), eps, L.ptr(wot), L.ptr(wqkvt), L.ptr(o), L.ptr(lse),
-                    L.ptr(dx), L.ptr(dqkv), L.ptr(dz), L.ptr(lnp), p, L.ptr(seed), L.stream()),
-                    'window_attn_block_bwd_saved_drop')
-            else:
-                L.check(L.lib.ococc_window_attn_block_bwd_saved_bf16(
-                    L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv),
-                    L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), eps, L.ptr(wot), L.ptr(wqkvt), L.ptr(o), L.ptr(lse),
-                    L.ptr(dx), L.ptr(dqkv), L.ptr(dz), L.ptr(lnp), L.stream()), 'window_attn_block_bwd_saved')
-        elif p > 0:
-            o = new((V, E), dtype=torch.bfloat16, device=x.device)
-            L.check(L.lib.ococc_window_attn_block_bwd_drop_bf16(
-                L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv),
-                L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), eps, L.ptr(wot), L.ptr(wqkvt), L.ptr(dx), L.ptr(dqkv), L.ptr(dz),
-                L.ptr(o), L.ptr(lnp), p, L.ptr(seed), L.stream()), 'window_attn_block_bwd_drop')
-        else:
-            o = new((V, E), dtype=torch.bfloat16, device=x.device)
-            L.check(L.lib.ococc_window_attn_block_bwd_bf16(
-                L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv),
-                L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), eps, L.ptr(wot), L.ptr(wqkvt), L.ptr(dx), L.ptr(dqkv), L.ptr(dz),
-                L.ptr(o), L.ptr(lnp), L.stream()), 'window_attn_block_bwd')
+        # the forward's attention output and log-sum-exp, or (nothing kept) the attention output the kernel writes
+        o_saved, lse_saved = kept or (None, None)
+        o_out = None if kept else new((V, E), dtype=torch.bfloat16, device=x.device)
+        L.check(L.lib.ococc_window_attn_block_bwd_bf16(
+            L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv),
+            L.ptr(bq), L.ptr(wo), L.ptr(bo), L.ptr(g1), eps, L.ptr(wot), L.ptr(wqkvt), L.ptr(o_saved), L.ptr(lse_saved),
+            L.ptr(dx), L.ptr(dqkv), L.ptr(dz), L.ptr(o_out), L.ptr(lnp), p, L.ptr(seed), L.stream()), 'window_attn_block_bwd')
+        o = o_out if o_saved is None else o_saved
         # rows outside the plan hold zeros in dqkv / dz: they add nothing to the sums below
         (dwqkv, dbqkv), (dwo, dbo), (dg, db) = _wgrad([(dqkv, 3 * E, x, pos, 2 * E), (dz, E, o, None, 0)], V, x.device, lnp, prow)
         return (dx, None, None, dwqkv.to(in_w.dtype), dbqkv.to(in_b.dtype), dwo.to(out_w.dtype), dbo.to(out_b.dtype),

@@ -8,8 +8,8 @@ Device work: window ranks ococc_group_rank_i32; attention core ococc_window_attn
 (MFMA QK^T / PV on padded windows); projections / FFN are GEMMs through torch.
 
 Attention dropout (``dropout`` of WindowAttention / EncoderLayer, nn.MultiheadAttention(dropout=p) upstream) runs inside
-the same kernels (their ``*_drop_bf16`` twins): in training mode with p > 0 every attention call draws one int64 seed on
-the device, the kernels drop a probability iff a hash of (seed, head, query row, key row) falls below p (csrc/
+the same kernels (their ``dropout_p`` and ``seed`` arguments): in training mode with p > 0 every attention call draws one
+int64 seed on the device, the kernels drop a probability iff a hash of (seed, head, query row, key row) falls below p (csrc/
 attn_dropout.hpp) and scale the kept ones by 1 / (1 - p), and the backward regenerates the mask from the saved seed.
 The mask is not torch's random stream; eval mode and p = 0 run the kernels without dropout."""
 import torch
@@ -213,6 +213,29 @@ def set_attn_probe(probe):
     _attn_probe = probe
 
 
+def _attn_fwd(q, k, v, qkv_stride, tok, key_len, nW, T, num_heads, D, scale, out, out_stride, lse, p, seed):
+    """one ococc_window_attn_fwd_bf16 launch, through the measurement hook when one is set.  q / k / v: device pointers
+    (row stride ``qkv_stride`` elements); tok None: padded rows (window * T + slot), else the row of every window slot;
+    p = 0 with seed None: no dropout."""
+    def launch():
+        L.check(L.lib.ococc_window_attn_fwd_bf16(q, k, v, qkv_stride, qkv_stride, qkv_stride, L.ptr(tok), L.ptr(key_len),
+                                                 nW, T, num_heads, D, scale, L.ptr(out), out_stride, L.ptr(lse), p,
+                                                 L.ptr(seed), L.stream()), 'window_attn_fwd')
+    if _attn_probe is not None:
+        _attn_probe.wrap(nW, T, num_heads, D, launch)
+    else:
+        launch()
+
+
+def _attn_bwd(q, k, v, qkv_stride, out, dout, o_stride, lse, tok, key_len, nW, T, num_heads, D, scale, dq, dk, dv,
+              grad_stride, p, seed):
+    """one ococc_window_attn_bwd_bf16 launch; q / k / v and dq / dk / dv are device pointers, the rest as _attn_fwd"""
+    L.check(L.lib.ococc_window_attn_bwd_bf16(q, k, v, qkv_stride, qkv_stride, qkv_stride, L.ptr(out), L.ptr(dout),
+                                             o_stride, L.ptr(lse), L.ptr(tok), L.ptr(key_len), nW, T, num_heads, D, scale,
+                                             dq, dk, dv, grad_stride, grad_stride, grad_stride, p, L.ptr(seed),
+                                             L.stream()), 'window_attn_bwd')
+
+
 class _WindowAttnCore(torch.autograd.Function):
     """softmax(q k^T / sqrt(d) + mask) v on padded windows, bf16 MFMA kernel."""
 
@@ -224,19 +247,8 @@ class _WindowAttnCore(torch.autograd.Function):
         out = torch.empty_like(qb)
         lse = torch.empty((nW, num_heads, T), dtype=torch.float32, device=q.device)
         scale = float(D) ** -0.5
-        def launch():
-            if p > 0:
-                L.check(L.lib.ococc_window_attn_fwd_drop_bf16(L.ptr(qb), L.ptr(kb), L.ptr(vb), C, C, C, L.ptr(key_len), nW,
-                                                              T, num_heads, D, scale, L.ptr(out), C, L.ptr(lse), p,
-                                                              L.ptr(seed), L.stream()), 'window_attn_fwd_drop')
-                return
-            L.check(L.lib.ococc_window_attn_fwd_bf16(L.ptr(qb), L.ptr(kb), L.ptr(vb), C, C, C, L.ptr(key_len), nW, T,
-                                                     num_heads, D, scale, L.ptr(out), C, L.ptr(lse), L.stream()),
-                    'window_attn_fwd')
-        if _attn_probe is not None:
-            _attn_probe.wrap(nW, T, num_heads, D, launch)
-        else:
-            launch()
+        _attn_fwd(qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), C, None, key_len, nW, T, num_heads, D, scale, out, C, lse,
+                  p, seed)
         ctx.save_for_backward(qb, kb, vb, out, lse, key_len)
         ctx.meta = (num_heads, D, scale, q.dtype)
         ctx.drop = (float(p), seed)
@@ -250,15 +262,8 @@ class _WindowAttnCore(torch.autograd.Function):
         nW, T, C = qb.shape
         do = dout.to(torch.bfloat16).contiguous()
         dq, dk, dv = torch.empty_like(qb), torch.empty_like(kb), torch.empty_like(vb)
-        if p > 0:
-            L.check(L.lib.ococc_window_attn_bwd_drop_bf16(L.ptr(qb), L.ptr(kb), L.ptr(vb), C, C, C, L.ptr(out), L.ptr(do),
-                                                          C, L.ptr(lse), L.ptr(key_len), nW, T, H, D, scale, L.ptr(dq),
-                                                          L.ptr(dk), L.ptr(dv), C, C, C, p, L.ptr(seed), L.stream()),
-                    'window_attn_bwd_drop')
-        else:
-            L.check(L.lib.ococc_window_attn_bwd_bf16(L.ptr(qb), L.ptr(kb), L.ptr(vb), C, C, C, L.ptr(out), L.ptr(do), C,
-                                                     L.ptr(lse), L.ptr(key_len), nW, T, H, D, scale, L.ptr(dq), L.ptr(dk),
-                                                     L.ptr(dv), C, C, C, L.stream()), 'window_attn_bwd')
+        _attn_bwd(qb.data_ptr(), kb.data_ptr(), vb.data_ptr(), C, out, do, C, lse, None, key_len, nW, T, H, D, scale,
+                  dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), C, p, seed)
         return dq.to(dt), dk.to(dt), dv.to(dt), None, None, None, None
 
 
@@ -275,21 +280,8 @@ class _WindowAttnPacked(torch.autograd.Function):
         out = torch.empty((nW, T, E), dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty((nW, num_heads, T), dtype=torch.float32, device=qkv.device)
         scale = float(D) ** -0.5
-        base = qkv.data_ptr()
-
-        def launch():
-            if p > 0:
-                L.check(L.lib.ococc_window_attn_fwd_drop_bf16(base, base + 2 * E, base + 4 * E, C3, C3, C3, L.ptr(key_len),
-                                                              nW, T, num_heads, D, scale, L.ptr(out), E, L.ptr(lse), p,
-                                                              L.ptr(seed), L.stream()), 'window_attn_fwd_drop')
-                return
-            L.check(L.lib.ococc_window_attn_fwd_bf16(base, base + 2 * E, base + 4 * E, C3, C3, C3, L.ptr(key_len), nW,
-                                                     T, num_heads, D, scale, L.ptr(out), E, L.ptr(lse), L.stream()),
-                    'window_attn_fwd')
-        if _attn_probe is not None:
-            _attn_probe.wrap(nW, T, num_heads, D, launch)
-        else:
-            launch()
+        b = qkv.data_ptr()
+        _attn_fwd(b, b + 2 * E, b + 4 * E, C3, None, key_len, nW, T, num_heads, D, scale, out, E, lse, p, seed)
         ctx.save_for_backward(qkv, out, lse, key_len)
         ctx.meta = (num_heads, D, scale)
         ctx.drop = (float(p), seed)
@@ -305,34 +297,16 @@ class _WindowAttnPacked(torch.autograd.Function):
         do = dout.to(torch.bfloat16).contiguous()
         dqkv = torch.empty_like(qkv)
         b, g = qkv.data_ptr(), dqkv.data_ptr()
-        if p > 0:
-            L.check(L.lib.ococc_window_attn_bwd_drop_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(out), L.ptr(do), E,
-                                                          L.ptr(lse), L.ptr(key_len), nW, T, H, D, scale, g, g + 2 * E,
-                                                          g + 4 * E, C3, C3, C3, p, L.ptr(seed), L.stream()),
-                    'window_attn_bwd_drop')
-        else:
-            L.check(L.lib.ococc_window_attn_bwd_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(out), L.ptr(do), E,
-                                                     L.ptr(lse), L.ptr(key_len), nW, T, H, D, scale, g, g + 2 * E,
-                                                     g + 4 * E, C3, C3, C3, L.stream()), 'window_attn_bwd')
+        _attn_bwd(b, b + 2 * E, b + 4 * E, C3, out, do, E, lse, None, key_len, nW, T, H, D, scale, g, g + 2 * E, g + 4 * E,
+                  C3, p, seed)
         return dqkv, None, None, None, None
 
 
 class _WindowAttnFlat(torch.autograd.Function):
     """Attention over all drop levels on the flat packed [V, 3E] token tensor: the kernels gather each
-    window's tokens through a slot -> row index (ococc_window_attn_*_gather_bf16), so no padded window copy is
-    built and the output / gradients are written straight in token order."""
-
-    @staticmethod
-    def forward(ctx, qkv, num_heads, *level_args):
-        return _WindowAttnFlatDrop.forward(ctx, qkv, num_heads, 0.0, None, *level_args)
-
-    @staticmethod
-    def backward(ctx, dout):
-        return _WindowAttnFlatDrop.backward(ctx, dout)[:2] + (None,) * (4 * len(ctx.meta[3]))
-
-
-class _WindowAttnFlatDrop(torch.autograd.Function):
-    """_WindowAttnFlat with attention dropout: p, and the device int64 seed the backward regenerates the mask from."""
+    window's tokens through a slot -> row index (``token_index`` of ococc_window_attn_{fwd,bwd}_bf16), so no padded
+    window copy is built and the output / gradients are written straight in token order.  p, seed: attention dropout
+    with the device int64 seed the backward regenerates the mask from (0.0, None: none)."""
 
     @staticmethod
     def forward(ctx, qkv, num_heads, p, seed, *level_args):
@@ -364,22 +338,7 @@ def _attn_flat_forward(qkv, num_heads, levels, p=0.0, seed=None):
     lses = []
     for tok, key_len, nW, T in levels:
         lse = torch.empty((nW, num_heads, T), dtype=torch.float32, device=qkv.device)
-
-        def launch():
-            if p > 0:
-                L.check(L.lib.ococc_window_attn_fwd_gather_drop_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(tok),
-                                                                     L.ptr(key_len), nW, T, num_heads, D, scale,
-                                                                     L.ptr(out), E, L.ptr(lse), p, L.ptr(seed),
-                                                                     L.stream()), 'window_attn_fwd_gather_drop')
-                return
-            L.check(L.lib.ococc_window_attn_fwd_gather_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(tok),
-                                                            L.ptr(key_len), nW, T, num_heads, D, scale,
-                                                            L.ptr(out), E, L.ptr(lse), L.stream()),
-                    'window_attn_fwd_gather')
-        if _attn_probe is not None:
-            _attn_probe.wrap(nW, T, num_heads, D, launch)
-        else:
-            launch()
+        _attn_fwd(b, b + 2 * E, b + 4 * E, C3, tok, key_len, nW, T, num_heads, D, scale, out, E, lse, p, seed)
         lses.append(lse)
     return out, lses, (num_heads, D, scale, [(lv[2], lv[3]) for lv in levels], float(p), seed)
 
@@ -394,16 +353,8 @@ def _attn_flat_backward(qkv, out, dout, lses, tok_and_len, meta):
     b, g = qkv.data_ptr(), dqkv.data_ptr()
     for i, (nW, T) in enumerate(shapes):
         tok, key_len = tok_and_len[2 * i], tok_and_len[2 * i + 1]
-        if p > 0:
-            L.check(L.lib.ococc_window_attn_bwd_gather_drop_bf16(
-                b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(out), L.ptr(do), E, L.ptr(lses[i]), L.ptr(tok), L.ptr(key_len),
-                nW, T, H, D, scale, g, g + 2 * E, g + 4 * E, C3, C3, C3, p, L.ptr(seed), L.stream()),
-                'window_attn_bwd_gather_drop')
-            continue
-        L.check(L.lib.ococc_window_attn_bwd_gather_bf16(b, b + 2 * E, b + 4 * E, C3, C3, C3, L.ptr(out), L.ptr(do), E,
-                                                        L.ptr(lses[i]), L.ptr(tok), L.ptr(key_len), nW, T, H, D,
-                                                        scale, g, g + 2 * E, g + 4 * E, C3, C3, C3, L.stream()),
-                'window_attn_bwd_gather')
+        _attn_bwd(b, b + 2 * E, b + 4 * E, C3, out, do, E, lses[i], tok, key_len, nW, T, H, D, scale, g, g + 2 * E,
+                  g + 4 * E, C3, p, seed)
     return dqkv
 
 
@@ -723,7 +674,7 @@ class WindowMultiheadAttention(nn.Module):
             args = []
             for dl, (slot, pos, nW, T, key_len, tok) in maps.items():
                 args += [tok, key_len, nW, T]
-            o_flat = _WindowAttnFlatDrop.apply(qkv, H, p, seed, *args) if p > 0 else _WindowAttnFlat.apply(qkv, H, *args)
+            o_flat = _WindowAttnFlat.apply(qkv, H, p, seed, *args)
         else:
             o_flat = None
             for dl, (slot, pos, nW, T, key_len, tok) in maps.items():

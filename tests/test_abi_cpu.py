@@ -46,6 +46,10 @@ def test_argument_errors_are_reported_not_thrown():
     assert rc == -1 and b'num_features' in L.lib.ococc_last_error()
     with pytest.raises(L.OcoccError):
         L.check(rc, 'dynamic_voxelize')
+    # the merged window-attention argument list: dropout_p is checked before the empty-launch early return
+    rc = L.lib.ococc_window_attn_fwd_bf16(None, None, None, 16, 16, 16, None, None, 0, 16, 8, 16, 0.25, None, 16, None,
+                                          1.0, None, None)
+    assert rc == -1 and b'dropout_p' in L.lib.ococc_last_error()
 
 
 def test_ops_refuse_cpu_tensors():

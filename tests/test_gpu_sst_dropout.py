@@ -1,7 +1,8 @@
-"""Attention dropout in the SST window-attention kernels (csrc/attn_dropout.hpp; ococc_window_attn_*_drop_bf16 and
-ococc_window_attn_block_*_drop_bf16): the mask is the specified hash bit for bit, in the padded, gather and tile kernels
-alike; the kernels match a float64 restatement of the rounded chain with that mask; the fused layer agrees with the
-operator path under the same seed; the statistics, eval mode and graph capture behave as nn.MultiheadAttention's."""
+"""Attention dropout in the SST window-attention kernels (csrc/attn_dropout.hpp; the dropout_p / seed arguments of
+ococc_window_attn_{fwd,bwd}_bf16 and ococc_window_attn_block_{fwd,bwd}_bf16): the mask is the specified hash bit for
+bit, in the padded, gather and tile kernels alike; the kernels match a float64 restatement of the rounded chain with that
+mask; the fused layer agrees with the operator path under the same seed; the statistics, eval mode and graph capture
+behave as nn.MultiheadAttention's."""
 import numpy as np
 import pytest
 import torch
@@ -53,8 +54,8 @@ def test_padded_and_gather_masks_are_the_specified_hash(dev):
     out = torch.empty_like(q)
     lse = torch.empty((nW, H, T), dtype=torch.float32, device=dev)
     seed = _seed(dev, sv)
-    L.check(L.lib.ococc_window_attn_fwd_drop_bf16(L.ptr(q), L.ptr(q), L.ptr(v), E, E, E, L.ptr(key_len), nW, T, H, D,
-                                                  D ** -0.5, L.ptr(out), E, L.ptr(lse), p, L.ptr(seed), L.stream()), 'fwd')
+    L.check(L.lib.ococc_window_attn_fwd_bf16(L.ptr(q), L.ptr(q), L.ptr(v), E, E, E, None, L.ptr(key_len), nW, T, H, D,
+                                             D ** -0.5, L.ptr(out), E, L.ptr(lse), p, L.ptr(seed), L.stream()), 'fwd')
     got = out.float().view(nW, T, H, D).permute(0, 2, 1, 3).cpu().numpy() != 0      # [nW, H, query, key slot]
     exp = _padded_mask(sv, key_len, T, p)
     live = np.arange(T)[None, None, :, None] < key_len.cpu().numpy()[:, None, None, None]
@@ -65,9 +66,9 @@ def test_padded_and_gather_masks_are_the_specified_hash(dev):
     qkv = torch.cat([q, q, v], 2).view(nW * T, 3 * E).contiguous()
     b = qkv.data_ptr()
     out_g = torch.empty((nW * T, E), dtype=torch.bfloat16, device=dev)
-    L.check(L.lib.ococc_window_attn_fwd_gather_drop_bf16(b, b + 2 * E, b + 4 * E, 3 * E, 3 * E, 3 * E, L.ptr(tok),
-                                                         L.ptr(full), nW, T, H, D, D ** -0.5, L.ptr(out_g), E, L.ptr(lse),
-                                                         p, L.ptr(seed), L.stream()), 'gather')
+    L.check(L.lib.ococc_window_attn_fwd_bf16(b, b + 2 * E, b + 4 * E, 3 * E, 3 * E, 3 * E, L.ptr(tok),
+                                             L.ptr(full), nW, T, H, D, D ** -0.5, L.ptr(out_g), E, L.ptr(lse),
+                                             p, L.ptr(seed), L.stream()), 'gather')
     got_g = out_g.float().view(nW, T, H, D).permute(0, 2, 1, 3).cpu().numpy() != 0
     assert np.array_equal(got_g, _padded_mask(sv, full, T, p))
     # gather form with scattered rows: the hash sees token_index rows
@@ -76,22 +77,23 @@ def test_padded_and_gather_masks_are_the_specified_hash(dev):
     qkv_s[perm.long()] = qkv
     b = qkv_s.data_ptr()
     out_s = torch.empty((nW * T, E), dtype=torch.bfloat16, device=dev)
-    L.check(L.lib.ococc_window_attn_fwd_gather_drop_bf16(b, b + 2 * E, b + 4 * E, 3 * E, 3 * E, 3 * E, L.ptr(perm),
-                                                         L.ptr(full), nW, T, H, D, D ** -0.5, L.ptr(out_s), E, L.ptr(lse),
-                                                         p, L.ptr(seed), L.stream()), 'gather')
+    L.check(L.lib.ococc_window_attn_fwd_bf16(b, b + 2 * E, b + 4 * E, 3 * E, 3 * E, 3 * E, L.ptr(perm),
+                                             L.ptr(full), nW, T, H, D, D ** -0.5, L.ptr(out_s), E, L.ptr(lse),
+                                             p, L.ptr(seed), L.stream()), 'gather')
     got_s = out_s[perm.long()].float().view(nW, T, H, D).permute(0, 2, 1, 3).cpu().numpy() != 0
     rows = perm.cpu().numpy().reshape(nW, T)
     w, h, qi, ki = np.meshgrid(np.arange(nW), np.arange(H), np.arange(T), np.arange(T), indexing='ij')
     assert np.array_equal(got_s, keep(sv, h, rows[w, qi], rows[w, ki], p))
     # p out of range / a missing seed: the library's error return
     for bad_p, bad_seed in ((1.0, seed), (-0.1, seed), (0.1, None)):
-        rc = L.lib.ococc_window_attn_fwd_drop_bf16(L.ptr(q), L.ptr(q), L.ptr(v), E, E, E, L.ptr(key_len), nW, T, H, D,
-                                                   D ** -0.5, L.ptr(out), E, L.ptr(lse), bad_p, L.ptr(bad_seed), L.stream())
+        rc = L.lib.ococc_window_attn_fwd_bf16(L.ptr(q), L.ptr(q), L.ptr(v), E, E, E, None, L.ptr(key_len), nW, T, H, D,
+                                              D ** -0.5, L.ptr(out), E, L.ptr(lse), bad_p, L.ptr(bad_seed), L.stream())
         assert rc != 0
 
 
 def test_tile_kernel_mask_is_the_gather_kernels(dev):
-    """..._block_train_fwd_drop_bf16 with Wq = Wk = 0, Wv = I and one-hot x: the saved attention output is P_drop"""
+    """ococc_window_attn_block_fwd_bf16 with attn_save, Wq = Wk = 0, Wv = I and one-hot x: the saved attention output is
+    P_drop"""
     from objectcentricocccompletion_amd import _lib as L
     from objectcentricocccompletion_amd.sst.fused_block import TilePlan, linear_fragments
     g = torch.Generator().manual_seed(5)
@@ -119,7 +121,7 @@ def test_tile_kernel_mask_is_the_gather_kernels(dev):
     o = torch.empty_like(x)
     lse = torch.empty((V, H), dtype=torch.float32, device=dev)
     seed = _seed(dev, sv)
-    L.check(L.lib.ococc_window_attn_block_train_fwd_drop_bf16(
+    L.check(L.lib.ococc_window_attn_block_fwd_bf16(
         L.ptr(x), None, L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv), L.ptr(zb), L.ptr(wo),
         L.ptr(zb), L.ptr(ones), L.ptr(zb), 1e-5, L.ptr(y), L.ptr(o), L.ptr(lse), p, L.ptr(seed), L.stream()), 'tile')
     got = o.float().view(V, H, D).cpu().numpy() != 0                     # [query row, head, key slot]
@@ -134,9 +136,9 @@ def test_tile_kernel_mask_is_the_gather_kernels(dev):
     b = qkv.data_ptr()
     out_g = torch.empty_like(x)
     lse_g = torch.empty((nW, H, T), dtype=torch.float32, device=dev)
-    L.check(L.lib.ococc_window_attn_fwd_gather_drop_bf16(b, b + 2 * E, b + 4 * E, 3 * E, 3 * E, 3 * E, L.ptr(tok),
-                                                         L.ptr(key_len), nW, T, H, D, D ** -0.5, L.ptr(out_g), E,
-                                                         L.ptr(lse_g), p, L.ptr(seed), L.stream()), 'gather')
+    L.check(L.lib.ococc_window_attn_fwd_bf16(b, b + 2 * E, b + 4 * E, 3 * E, 3 * E, 3 * E, L.ptr(tok),
+                                             L.ptr(key_len), nW, T, H, D, D ** -0.5, L.ptr(out_g), E,
+                                             L.ptr(lse_g), p, L.ptr(seed), L.stream()), 'gather')
     assert np.array_equal(out_g.float().view(V, H, D).cpu().numpy() != 0, got)
 
 
@@ -165,7 +167,7 @@ def _core_f64(q, k, v, key_len, dout, keep_m, p):
 
 @pytest.mark.parametrize('p', [0.1, 0.5])
 def test_kernels_vs_float64_with_the_mask(dev, p):
-    from objectcentricocccompletion_amd.sst.sst_modules import _WindowAttnCore, _WindowAttnFlatDrop
+    from objectcentricocccompletion_amd.sst.sst_modules import _WindowAttnCore, _WindowAttnFlat
     g = torch.Generator().manual_seed(11)
     worst = 0.0
     for T in (7, 30, 60, 100, 144):
@@ -194,7 +196,7 @@ def test_kernels_vs_float64_with_the_mask(dev, p):
         for i, t in enumerate((q, k, v)):
             qkv[perm, i * E:(i + 1) * E] = t.detach().reshape(nW * T, E)[valid].bfloat16()
         qkv.requires_grad_(True)
-        of = _WindowAttnFlatDrop.apply(qkv, H, p, seed, tok, key_len, nW, T)
+        of = _WindowAttnFlat.apply(qkv, H, p, seed, tok, key_len, nW, T)
         do_f = torch.empty((full_rows, E), dtype=torch.bfloat16, device=dev)
         do_f[perm] = dout.reshape(nW * T, E)[valid].bfloat16()
         of.backward(do_f)
@@ -251,9 +253,9 @@ def test_dropped_fraction_over_a_million_pairs(dev):
     masks = []
     for sv in (31337, 4242424242):
         out = torch.empty_like(q)
-        L.check(L.lib.ococc_window_attn_fwd_drop_bf16(L.ptr(q), L.ptr(q), L.ptr(v), E, E, E, L.ptr(key_len), nW, T, H, D,
-                                                      D ** -0.5, L.ptr(out), E, L.ptr(lse), p, L.ptr(_seed(dev, sv)),
-                                                      L.stream()), 'fwd')
+        L.check(L.lib.ococc_window_attn_fwd_bf16(L.ptr(q), L.ptr(q), L.ptr(v), E, E, E, None, L.ptr(key_len), nW, T, H, D,
+                                                 D ** -0.5, L.ptr(out), E, L.ptr(lse), p, L.ptr(_seed(dev, sv)),
+                                                 L.stream()), 'fwd')
         masks.append(out.view(nW, T, H, D).permute(0, 2, 1, 3) == 0)     # dropped [w, h, query, key]
     d1, d2 = masks
     n = d1.numel()

@@ -327,9 +327,9 @@ def test_fused_sst_at_the_configs4_per_gpu_share(dev, G):
 @pytest.mark.parametrize('small_only', [True, False])
 def test_kept_attention_output_gives_the_backward_of_the_recomputing_kernel(dev, golden_dir, small_only, monkeypatch):
     """Training keeps the attention output and the softmax's log-sum-exp of the attention block
-    (ococc_window_attn_block_train_fwd_bf16) and the backward kernel reads them back
-    (ococc_window_attn_block_bwd_saved_bf16) instead of running the attention forward again: the same arithmetic on the
-    same values -- output, input gradient and every parameter gradient BIT-identical to the recomputing pair (which is the
+    (ococc_window_attn_block_fwd_bf16 with attn_save / lse_save) and the backward kernel reads them back
+    (ococc_window_attn_block_bwd_bf16 with attn_saved / lse_saved) instead of running the attention forward again: the
+    same arithmetic on the same values -- output, input gradient and every parameter gradient BIT-identical to the recomputing pair (which is the
     one the oracle tests above pin)."""
     from objectcentricocccompletion_amd.sst import fused_block as fb
     from objectcentricocccompletion_amd.sst.sst_modules import SSTInputLayerV2

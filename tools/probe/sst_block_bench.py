@@ -61,7 +61,7 @@ def main():
     attn_flops = V * 8.0 * E * E + 4.0 * E * plan.sum_sq
     timeit('attn_block_fwd', lambda: L.check(L.lib.ococc_window_attn_block_fwd_bf16(
         L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv), L.ptr(bq), L.ptr(wo),
-        L.ptr(bo), L.ptr(gg1), L.ptr(bb1), 1e-5, L.ptr(y1), L.stream())), attn_flops)
+        L.ptr(bo), L.ptr(gg1), L.ptr(bb1), 1e-5, L.ptr(y1), None, None, 0.0, None, L.stream())), attn_flops)
     timeit('ffn_block_fwd', lambda: L.check(L.lib.ococc_token_ffn_block_fwd_bf16(
         L.ptr(y1), V, E, F, L.ptr(f1), L.ptr(c1), L.ptr(f2), L.ptr(c2), L.ptr(gg2), L.ptr(bb2), 1e-5, 0, L.ptr(y2),
         L.stream())), 4.0 * V * E * F)
@@ -80,8 +80,8 @@ def main():
     lnp2 = torch.empty((prow2, 2, E), dtype=torch.float32, device=dev)
     timeit('attn_block_bwd', lambda: L.check(L.lib.ococc_window_attn_block_bwd_bf16(
         L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv), L.ptr(bq),
-        L.ptr(wo), L.ptr(bo), L.ptr(gg1), 1e-5, L.ptr(wot), L.ptr(wqkvt), L.ptr(dx), L.ptr(dqkv), L.ptr(dz), L.ptr(o),
-        L.ptr(lnp2), L.stream())), attn_flops + V * 8.0 * E * E + 8.0 * E * plan.sum_sq + attn_flops * 0)
+        L.ptr(wo), L.ptr(bo), L.ptr(gg1), 1e-5, L.ptr(wot), L.ptr(wqkvt), None, None, L.ptr(dx), L.ptr(dqkv), L.ptr(dz),
+        L.ptr(o), L.ptr(lnp2), 0.0, None, L.stream())), attn_flops + V * 8.0 * E * E + 8.0 * E * plan.sum_sq + attn_flops * 0)
     timeit('wgrad attn (qkv, o)', lambda: fb._wgrad([(dqkv, 3 * E, x, pos, 2 * E), (dz, E, o, None, 0)], V, dev), V * 8.0 * E * E)
     timeit('wgrad ffn (w1, w2)', lambda: fb._wgrad([(dh, F, y1, None, 0), (dz, E, a_, None, 0)], V, dev), V * 4.0 * E * F)
 

@@ -61,22 +61,17 @@ SAVED = os.environ.get('SST_STAMPS_RECOMPUTE', '0') != '1'   # default: the back
 y1 = torch.empty_like(x)
 lse = torch.empty((V, H), dtype=torch.float32, device=dev)
 bb1 = torch.zeros(E, device=dev)
-L.check(L.lib.ococc_window_attn_block_train_fwd_bf16(
+L.check(L.lib.ococc_window_attn_block_fwd_bf16(
     L.ptr(x), L.ptr(pos), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv), L.ptr(bq), L.ptr(wo),
-    L.ptr(bo), L.ptr(gg1), L.ptr(bb1), 1e-5, L.ptr(y1), L.ptr(o), L.ptr(lse), L.stream()), 'train fwd')
+    L.ptr(bo), L.ptr(gg1), L.ptr(bb1), 1e-5, L.ptr(y1), L.ptr(o), L.ptr(lse), 0.0, None, L.stream()), 'train fwd')
+saved, out = ((o, lse), None) if SAVED else ((None, None), o)
 
 
 def run():
-    if SAVED:
-        L.check(L.lib.ococc_window_attn_block_bwd_saved_bf16(
-            L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv), L.ptr(bq),
-            L.ptr(wo), L.ptr(bo), L.ptr(gg1), 1e-5, L.ptr(wot), L.ptr(wqkvt), L.ptr(o), L.ptr(lse), L.ptr(dx), L.ptr(dqkv),
-            L.ptr(dz), L.ptr(lnp2), L.stream()), 'bwd saved')
-    else:
-        L.check(L.lib.ococc_window_attn_block_bwd_bf16(
-            L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv), L.ptr(bq),
-            L.ptr(wo), L.ptr(bo), L.ptr(gg1), 1e-5, L.ptr(wot), L.ptr(wqkvt), L.ptr(dx), L.ptr(dqkv), L.ptr(dz), L.ptr(o),
-            L.ptr(lnp2), L.stream()), 'bwd')
+    L.check(L.lib.ococc_window_attn_block_bwd_bf16(
+        L.ptr(x), L.ptr(pos), L.ptr(dy), L.ptr(plan.rows), L.ptr(plan.span), plan.num_tiles, E, H, L.ptr(wqkv), L.ptr(bq),
+        L.ptr(wo), L.ptr(bo), L.ptr(gg1), 1e-5, L.ptr(wot), L.ptr(wqkvt), L.ptr(saved[0]), L.ptr(saved[1]), L.ptr(dx),
+        L.ptr(dqkv), L.ptr(dz), L.ptr(out), L.ptr(lnp2), 0.0, None, L.stream()), 'bwd saved' if SAVED else 'bwd')
 
 
 for _ in range(3):

@@ -316,12 +316,47 @@ int ococc_rulebook_pairs_to_table(const int32_t* indice_pairs, const int32_t* in
  * table  [kvol, n_out] int32, blockmask [ceil(n_out/16)] (kvol <= 32)
  * bias   [ncols] f32 or NULL
  * out    [n_out, ncols] bf16 (out_dtype OCOCC_BF16) or f32; ncols mult. of 16
+ * ln     NULL (plain convolution) or the LayerNorm epilogue below
+ *
+ * The three convolution kernels (this one, tile, sorted) take an optional
+ * epilogue: the norm/activation pair of make_sparse_convmodule
+ * (mmdet3d/ops/sparse_block.py:216-289: conv -> LayerNorm(eps) -> act).
+ *   backward = 0  out = conv_out [n_out, ncols] bf16 (what the LN backward
+ *                 needs), y = act(LN(conv_out)) bf16, mean_rstd [n_out, 2] f32,
+ *                 as ococc_layernorm_act_fwd writes them: the norm sees the
+ *                 bf16-rounded conv output, as the separate call would.
+ *   backward = 1  the input-gradient pass of layer L+1 (feat = d conv_out of
+ *                 layer L+1, wn = its dgrad operand, table = its table for the
+ *                 backward direction) with the LayerNorm (+ act) BACKWARD of
+ *                 the block in front (layer L) in its epilogue: with layer L's
+ *                 saved conv output block_conv_out and statistics mean_rstd,
+ *                 out = d_conv_out [n_out, ncols] bf16, the gradient of layer
+ *                 L's CONV output (bit-identical to ococc_layernorm_act_bwd on
+ *                 the bf16 dgrad output), plus one row of partial sums
+ *                 [d gamma | d beta] per workgroup into partials [partial_rows,
+ *                 2 ncols] f32, every row written (ococc_layernorm_param_reduce_multi
+ *                 or a column sum finishes them).  ncols in {32, 64}.
+ * With an epilogue, bias must be NULL and out_dtype OCOCC_BF16.  A shape that
+ * has no fused kernel returns OCOCC_EUNSUPPORTED (then make the two calls).
+ * The gather-GEMM kernel has no backward epilogue (OCOCC_EUNSUPPORTED).
  * ------------------------------------------------------------------------ */
+typedef struct ococc_conv_ln {
+  int32_t backward;               /* 0: LN(+act) forward epilogue; 1: LN(+act) backward of the block in front */
+  int32_t act;                    /* 0 none, 1 GELU */
+  float eps;                      /* forward */
+  const float* gamma;             /* [ncols] f32 */
+  const float* beta;              /* [ncols] f32 */
+  uint16_t* y;                    /* forward: act(LN(out)) [n_out, ncols] bf16 */
+  float* mean_rstd;               /* [n_out, 2] f32: written by the forward, read by the backward */
+  const uint16_t* block_conv_out; /* backward: the block's saved conv output [n_out, ncols] bf16 */
+  float* partials;                /* backward: [partial_rows, 2*ncols] f32 */
+  int64_t partial_rows;
+} ococc_conv_ln;
 int ococc_sparse_conv_gather_gemm_bf16(const uint16_t* feat, int64_t n_in, int32_t kd,
                                        const uint16_t* wn, int32_t kvol, int32_t ncols,
                                        const int32_t* table, const uint32_t* blockmask,
                                        int64_t n_out, const float* bias, void* out,
-                                       int32_t out_dtype, ococc_stream_t stream);
+                                       int32_t out_dtype, const ococc_conv_ln* ln, ococc_stream_t stream);
 
 /* The same convolution for SUB-MANIFOLD tables over sparse active sets (a voxel has only a few
  * neighbours): the centre offset dense_k (every row is its own neighbour; -1: none) is a dense pass,
@@ -329,10 +364,15 @@ int ococc_sparse_conv_gather_gemm_bf16(const uint16_t* feat, int64_t n_in, int32
  * gathered and multiplied, with f32 accumulators of a 512-row tile in LDS.  Same operands and the
  * same result (f32 accumulation, centre first, then ascending offsets: deterministic) as
  * ococc_sparse_conv_gather_gemm_bf16; faster below ~2-3 rulebook pairs per output row
- * (tools/density_sweep.py), slower on dense neighbourhoods.  kd in {32, 64, 128}, ncols in {32, 64, 128}; no block masks needed. */
+ * (tools/density_sweep.py), slower on dense neighbourhoods.  kd in {32, 64, 128}, ncols in {32, 64, 128}; no block masks needed.
+ * ln: the LayerNorm epilogue of ococc_sparse_conv_gather_gemm_bf16, applied where the finished f32 row sits in LDS --
+ * forward on shapes up to 64 x 64 channels (OCOCC_EUNSUPPORTED otherwise), backward with ncols in {32, 64} and
+ * partial_rows >= ococc_sparse_conv_tile_lnbwd_partial_rows(n_out, kd, ncols). */
 int ococc_sparse_conv_tile_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn, int32_t kvol,
                                 int32_t ncols, const int32_t* table, int32_t dense_k, int64_t n_out,
-                                const float* bias, void* out, int32_t out_dtype, ococc_stream_t stream);
+                                const float* bias, void* out, int32_t out_dtype, const ococc_conv_ln* ln,
+                                ococc_stream_t stream);
+int64_t ococc_sparse_conv_tile_lnbwd_partial_rows(int64_t n_out, int32_t kd, int32_t ncols);
 /* The same convolution with the OUTPUT rows processed in neighbour-pattern order (sub-manifold tables, kvol <= 32).
  * ococc_subm_row_order buckets the rows of an offset-major gather table by (number of neighbours besides dense_k: 3+,
  * 2, 1, 0; lowest two neighbour offsets) -- rows that share their offsets become neighbours in the order, so a
@@ -349,7 +389,13 @@ int ococc_sparse_conv_tile_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, 
  * result does not (each output row accumulates its own products in ascending offset order, in f32).
  * ococc_sparse_conv_sorted_bf16: operands as ococc_sparse_conv_gather_gemm_bf16 (wn row-major [kvol, ncols, kd]), same
  * result bit for bit; kd, ncols in {32, 64, 128}, not both 128.  Replaces indiceConv's per-offset gather / GEMM /
- * scatter-add (spconv_ops.h:300-354). */
+ * scatter-add (spconv_ops.h:300-354).
+ * ln: the LayerNorm epilogue of ococc_sparse_conv_gather_gemm_bf16, for rulebooks that run in neighbour-pattern order;
+ * the finished f32 row sits in the registers of the four lanes that share a slot, and the norm sums in the order of
+ * ococc_layernorm_act_fwd, so the results equal the two-launch pair's (round 6: the 64 -> 128 forward of configs[1],
+ * whose separate LN launch re-read 32 MB).  Backward: ncols in {32, 64}, partial_rows >=
+ * ococc_sparse_conv_sorted_lnbwd_partial_rows(n_out); it replaces indiceConvBackward's input-gradient loop
+ * (spconv_ops.h:363-456) followed by the LayerNorm backward of sparse_block.py:216-289's norm layer. */
 int64_t ococc_subm_row_order_counter_bytes(void);
 int64_t ococc_subm_row_order_scratch_bytes(int64_t n);
 int ococc_subm_row_order(const int32_t* table, int32_t kvol, int32_t dense_k, int64_t n, int32_t heavy_blocks,
@@ -362,54 +408,9 @@ int ococc_subm_row_order_place(const int32_t* rowrec, int32_t kvol, int32_t dens
                                int32_t mid_blocks, void* counters, int32_t* rec, int32_t* hdr, ococc_stream_t stream);
 int ococc_sparse_conv_sorted_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn, int32_t kvol,
                                   int32_t ncols, const int32_t* table, const int32_t* rec, const int32_t* hdr,
-                                  int64_t n_out, const float* bias, void* out, int32_t out_dtype, ococc_stream_t stream);
-/* ococc_sparse_conv_sorted_bf16 with the LayerNorm (+ GELU) of the enclosing conv -> norm -> act block
- * (make_sparse_convmodule, mmdet3d/ops/sparse_block.py:216-289) in its epilogue: the contract of
- * ococc_sparse_conv_tile_ln_bf16 below (conv_out, y = act(LN(conv_out)), mean_rstd [n_out, 2]) for rulebooks that run in
- * neighbour-pattern order.  The finished f32 row sits in the registers of the four lanes that share a slot; the norm
- * sees the bf16-rounded conv output and sums in the order of ococc_layernorm_act_fwd, so y and mean_rstd equal the
- * two-launch pair's (conv, then LN).  kd, ncols in {32, 64, 128}, not both 128 (round 6: the 64 -> 128 forward of
- * configs[1], whose separate LN launch re-read 32 MB). */
-int ococc_sparse_conv_sorted_ln_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn, int32_t kvol,
-                                     int32_t ncols, const int32_t* table, const int32_t* rec, const int32_t* hdr,
-                                     int64_t n_out, const float* gamma, const float* beta, float eps, int32_t act,
-                                     uint16_t* conv_out, uint16_t* y, float* mean_rstd, ococc_stream_t stream);
-/* ococc_sparse_conv_sorted_bf16 as the input-gradient pass of layer L+1 with the LayerNorm (+ GELU) BACKWARD of the
- * conv -> LN -> act block L in its epilogue -- the contract of ococc_sparse_conv_tile_lnbwd_bf16 below (same operands
- * besides the row order rec / hdr and the row-major dgrad operand wn; d_conv_out bit-identical to it and to
- * ococc_layernorm_act_bwd on the bf16 dgrad output), for rulebooks that run in neighbour-pattern order.  One row of
- * partial sums [d gamma | d beta] per workgroup: partial_rows >= ococc_sparse_conv_sorted_lnbwd_partial_rows(n_out),
- * every row written.  ncols in {32, 64}.  Replaces indiceConvBackward's input-gradient loop (spconv_ops.h:363-456)
- * followed by the LayerNorm backward of sparse_block.py:216-289's norm layer. */
+                                  int64_t n_out, const float* bias, void* out, int32_t out_dtype, const ococc_conv_ln* ln,
+                                  ococc_stream_t stream);
 int64_t ococc_sparse_conv_sorted_lnbwd_partial_rows(int64_t n_out);
-int ococc_sparse_conv_sorted_lnbwd_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn, int32_t kvol,
-                                        int32_t ncols, const int32_t* table, const int32_t* rec, const int32_t* hdr,
-                                        int64_t n_out, const uint16_t* block_conv_out, const float* mean_rstd,
-                                        const float* gamma, const float* beta, int32_t act, uint16_t* d_conv_out,
-                                        float* partials, int64_t partial_rows, ococc_stream_t stream);
-/* The same kernel with the LayerNorm (+ GELU) that follows the convolution in the reference's
- * make_sparse_convmodule block (mmdet3d/ops/sparse_block.py:216-289: conv -> LN(eps) -> GELU) applied in the
- * epilogue, where the finished f32 row sits in LDS: conv_out [n_out, ncols] bf16 (what the LN backward needs), y =
- * act(LN(conv_out)) bf16, mean_rstd [n_out, 2] f32.  The norm sees the bf16-rounded conv output, as the separate
- * ococc_layernorm_act_fwd would.  Shapes up to 64 x 64 channels; OCOCC_EUNSUPPORTED otherwise. */
-int ococc_sparse_conv_tile_ln_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn, int32_t kvol,
-                                   int32_t ncols, const int32_t* table, int32_t dense_k, int64_t n_out,
-                                   const float* gamma, const float* beta, float eps, int32_t act,
-                                   uint16_t* conv_out, uint16_t* y, float* mean_rstd, ococc_stream_t stream);
-/* The same kernel as the input-gradient pass of layer L+1 (feat = d conv_out of layer L+1, wn = its dgrad operand,
- * table = its gather-side table for the backward direction) with the LayerNorm (+ GELU) BACKWARD of the block in
- * front (layer L: conv -> LN -> act, sparse_block.py:216-289) applied in the epilogue: the finished row is the
- * gradient of layer L's block OUTPUT; with layer L's saved conv output block_conv_out [n_out, ncols] bf16, its
- * statistics mean_rstd [n_out, 2] and gamma / beta, d_conv_out [n_out, ncols] bf16 = the gradient of layer L's CONV
- * output leaves instead (bit-identical to ococc_layernorm_act_bwd on the bf16 dgrad output), plus one row of
- * partial sums [d gamma | d beta] per workgroup into partials [partial_rows, 2 ncols] f32 (every row written;
- * ococc_layernorm_param_reduce_multi or a column sum finishes them).  ncols in {32, 64}. */
-int64_t ococc_sparse_conv_tile_lnbwd_partial_rows(int64_t n_out, int32_t kd, int32_t ncols);
-int ococc_sparse_conv_tile_lnbwd_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn, int32_t kvol,
-                                      int32_t ncols, const int32_t* table, int32_t dense_k, int64_t n_out,
-                                      const uint16_t* block_conv_out, const float* mean_rstd, const float* gamma,
-                                      const float* beta, int32_t act, uint16_t* d_conv_out, float* partials,
-                                      int64_t partial_rows, ococc_stream_t stream);
 
 /* weights [kvol, cin, cout] (the reference layout (kD,kH,kW,Cin,Cout),
  * spconv/conv.py:98-99) in f32 or bf16 ->
@@ -422,17 +423,6 @@ int ococc_sparse_conv_tile_lnbwd_bf16(const uint16_t* feat, int64_t n_in, int32_
 int ococc_weight_prepare_multi_bf16(int32_t count, const void* const* w, const int32_t* kvol, const int32_t* cin,
                                     const int32_t* cout, const int32_t* mode, void* const* wn,
                                     ococc_stream_t stream);
-
-/* Forward gather-GEMM with the norm/activation pair of make_sparse_convmodule
- * (mmdet3d/ops/sparse_block.py:216-289: conv -> LayerNorm -> GELU) fused into the epilogue:
- * conv_out [n_out, ncols] bf16 (kept for the backward), y = act(LN(conv_out)) bf16, mean_rstd [n_out,2]
- * f32 as ococc_layernorm_act_fwd writes them.  gamma / beta [ncols] f32.  Returns OCOCC_EUNSUPPORTED
- * when the shape has no fused kernel (then call the two separate entry points). */
-int ococc_sparse_conv_gather_gemm_ln_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn,
-                                          int32_t kvol, int32_t ncols, const int32_t* table,
-                                          const uint32_t* blockmask, int64_t n_out, const float* gamma,
-                                          const float* beta, float eps, int32_t act, uint16_t* conv_out,
-                                          uint16_t* y, float* mean_rstd, ococc_stream_t stream);
 
 int ococc_weight_prepare_bf16(const void* w, int32_t w_dtype, int32_t kvol, int32_t cin,
                               int32_t cout, int32_t mode, uint16_t* wn, ococc_stream_t stream);

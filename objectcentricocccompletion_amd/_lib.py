@@ -21,6 +21,16 @@ _F6 = ctypes.c_float * 6
 _I3 = ctypes.c_int32 * 3
 _I4 = ctypes.c_int32 * 4
 
+
+class ConvLn(ctypes.Structure):
+    """ococc_conv_ln of include/ococc_hip.h: the LayerNorm epilogue of the three convolution exports (pass None for a
+    plain convolution)"""
+    _fields_ = [('backward', c_i32), ('act', c_i32), ('eps', c_f32), ('gamma', c_vp), ('beta', c_vp), ('y', c_vp),
+                ('mean_rstd', c_vp), ('block_conv_out', c_vp), ('partials', c_vp), ('partial_rows', c_i64)]
+
+
+_LN = ctypes.POINTER(ConvLn)
+
 # name -> (restype, argtypes); one entry per function declared in ococc_hip.h
 SIGNATURES = {
     'ococc_last_error': (ctypes.c_char_p, []),
@@ -67,27 +77,17 @@ SIGNATURES = {
     'ococc_sparse_conv_wgrad_multi_bf16': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'ococc_backward_param_reduce_multi': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'ococc_sparse_conv_tile_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp,
-                                            c_i32, c_vp]),
-    'ococc_sparse_conv_tile_ln_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp,
-                                               c_f32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+                                            c_i32, _LN, c_vp]),
     'ococc_sparse_conv_tile_lnbwd_partial_rows': (c_i64, [c_i64, c_i32, c_i32]),
-    'ococc_sparse_conv_tile_lnbwd_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp,
-                                                  c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp]),
     'ococc_sparse_conv_gather_gemm_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp,
-                                                   c_vp, c_i64, c_vp, c_vp, c_i32, c_vp]),
+                                                   c_vp, c_i64, c_vp, c_vp, c_i32, _LN, c_vp]),
     'ococc_subm_row_order_scratch_bytes': (c_i64, [c_i64]),
     'ococc_subm_row_order_counter_bytes': (c_i64, []),
     'ococc_subm_row_order_place': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'ococc_subm_row_order': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'ococc_sparse_conv_sorted_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64,
-                                              c_vp, c_vp, c_i32, c_vp]),
-    'ococc_sparse_conv_sorted_ln_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp,
-                                                 c_f32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+                                              c_vp, c_vp, c_i32, _LN, c_vp]),
     'ococc_sparse_conv_sorted_lnbwd_partial_rows': (c_i64, [c_i64]),
-    'ococc_sparse_conv_sorted_lnbwd_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp,
-                                                    c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_sparse_conv_gather_gemm_ln_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i64,
-                                                      c_vp, c_vp, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'ococc_weight_prepare_multi_bf16': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
                                                 ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_vp), c_vp]),
     'ococc_weight_prepare_bf16': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),

@@ -1,5 +1,6 @@
-// Row arithmetic of the LayerNorm (+ GELU) backward, shared by the stand-alone kernels (layernorm_act.hip) and the
-// epilogue of the tile convolution (sparse_conv_tile.hip) so that both produce the same bits.
+// Row arithmetic of the LayerNorm (+ GELU), shared by the stand-alone kernels (layernorm_act.hip) and the LayerNorm
+// epilogues of the convolution kernels (ococc_conv_ln: sparse_conv.hip, sparse_conv_tile.hip, sparse_conv_sorted.hip)
+// so that both produce the same bits.
 //
 // These kernels are VALU-bound, not HBM-bound: ~45 scalar f32 instructions per element x 16 lanes per clock and SIMD is
 // 20 us for the 126 k x 128 activation of configs[1], against 12 us for its 96 MB at 8 TB/s.  Hence (a) packed f32

@@ -1266,44 +1266,30 @@ extern "C" int ococc_sparse_conv_gather_gemm_bf16(const uint16_t* feat, int64_t 
                                                   const uint16_t* wn, int32_t kvol, int32_t ncols,
                                                   const int32_t* table, const uint32_t* blockmask,
                                                   int64_t n_out, const float* bias, void* out,
-                                                  int32_t out_dtype, ococc_stream_t stream_) {
+                                                  int32_t out_dtype, const ococc_conv_ln* ln, ococc_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  if (ln && ln->backward)
+    return ococc_fail(OCOCC_EUNSUPPORTED, __func__, "no fused LayerNorm backward epilogue on this kernel");
   OCOCC_REQUIRE(n_in >= 0 && n_out >= 0, "negative row count");
   OCOCC_REQUIRE(kvol >= 1 && kvol <= 32, "kernel volume must be 1..32");
   OCOCC_REQUIRE(ncols >= 16 && ncols % 16 == 0, "ncols must be a multiple of 16");
   OCOCC_REQUIRE(out_dtype == OCOCC_BF16 || out_dtype == OCOCC_F32, "out_dtype must be f32/bf16");
+  if (ln) {
+    OCOCC_REQUIRE(!bias && out_dtype == OCOCC_BF16, "LayerNorm epilogue: no bias, bf16 output");
+    OCOCC_REQUIRE(ln->act == 0 || ln->act == 1, "act must be 0 (none) or 1 (gelu)");
+  }
   if (n_out == 0) return OCOCC_OK;
   OCOCC_REQUIRE(wn && table && out, "null pointer");
+  OCOCC_REQUIRE(!ln || (ln->y && ln->mean_rstd && ln->gamma && ln->beta), "null pointer");
   OCOCC_REQUIRE(feat || n_in == 0, "null feat");
+  LnArgs args{};
+  if (ln) args = LnArgs{ln->gamma, ln->beta, ln->eps, (int)ln->act, ln->y, ln->mean_rstd};
+  const LnArgs* lp = ln ? &args : nullptr;
   switch (kd) {
-    case 16: return dispatch_cs<16>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, bias, out, out_dtype, stream);
-    case 32: return dispatch_cs<32>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, bias, out, out_dtype, stream);
-    case 64: return dispatch_cs<64>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, bias, out, out_dtype, stream);
-    case 128: return dispatch_cs<128>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, bias, out, out_dtype, stream);
-    default: return ococc_fail(OCOCC_EUNSUPPORTED, __func__, "kd must be 16/32/64/128");
-  }
-}
-
-extern "C" int ococc_sparse_conv_gather_gemm_ln_bf16(const uint16_t* feat, int64_t n_in, int32_t kd,
-                                                     const uint16_t* wn, int32_t kvol, int32_t ncols,
-                                                     const int32_t* table, const uint32_t* blockmask,
-                                                     int64_t n_out, const float* gamma, const float* beta,
-                                                     float eps, int32_t act, uint16_t* conv_out, uint16_t* y,
-                                                     float* mean_rstd, ococc_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  OCOCC_REQUIRE(n_in >= 0 && n_out >= 0, "negative row count");
-  OCOCC_REQUIRE(kvol >= 1 && kvol <= 32, "kernel volume must be 1..32");
-  OCOCC_REQUIRE(ncols >= 16 && ncols % 16 == 0, "ncols must be a multiple of 16");
-  OCOCC_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (gelu)");
-  if (n_out == 0) return OCOCC_OK;
-  OCOCC_REQUIRE(wn && table && conv_out && y && mean_rstd && gamma && beta, "null pointer");
-  OCOCC_REQUIRE(feat || n_in == 0, "null feat");
-  const LnArgs ln{gamma, beta, eps, (int)act, y, mean_rstd};
-  switch (kd) {
-    case 16: return dispatch_cs<16>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, nullptr, conv_out, OCOCC_BF16, stream, &ln);
-    case 32: return dispatch_cs<32>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, nullptr, conv_out, OCOCC_BF16, stream, &ln);
-    case 64: return dispatch_cs<64>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, nullptr, conv_out, OCOCC_BF16, stream, &ln);
-    case 128: return dispatch_cs<128>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, nullptr, conv_out, OCOCC_BF16, stream, &ln);
+    case 16: return dispatch_cs<16>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, bias, out, out_dtype, stream, lp);
+    case 32: return dispatch_cs<32>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, bias, out, out_dtype, stream, lp);
+    case 64: return dispatch_cs<64>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, bias, out, out_dtype, stream, lp);
+    case 128: return dispatch_cs<128>(feat, n_in, wn, kvol, ncols, table, blockmask, n_out, bias, out, out_dtype, stream, lp);
     default: return ococc_fail(OCOCC_EUNSUPPORTED, __func__, "kd must be 16/32/64/128");
   }
 }

@@ -827,49 +827,33 @@ int sorted_entry(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t*
 }
 }  // namespace
 
-extern "C" int ococc_sparse_conv_sorted_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn,
-                                             int32_t kvol, int32_t ncols, const int32_t* table, const int32_t* rec,
-                                             const int32_t* hdr, int64_t n_out, const float* bias, void* out,
-                                             int32_t out_dtype, ococc_stream_t stream_) {
-  return sorted_entry(feat, n_in, kd, wn, kvol, ncols, table, rec, hdr, n_out, bias, out, out_dtype, (hipStream_t)stream_,
-                      nullptr);
-}
-
-extern "C" int ococc_sparse_conv_sorted_ln_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn,
-                                                int32_t kvol, int32_t ncols, const int32_t* table, const int32_t* rec,
-                                                const int32_t* hdr, int64_t n_out, const float* gamma, const float* beta,
-                                                float eps, int32_t act, uint16_t* conv_out, uint16_t* y, float* mean_rstd,
-                                                ococc_stream_t stream_) {
-  OCOCC_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (gelu)");
-  OCOCC_REQUIRE(n_out == 0 || (gamma && beta && conv_out && y && mean_rstd), "null pointer");
-  SortedLn ln{};
-  ln.gamma = gamma;
-  ln.beta = beta;
-  ln.act = act;
-  ln.eps = eps;
-  ln.act_out = y;
-  ln.stats_out = mean_rstd;
-  return sorted_entry(feat, n_in, kd, wn, kvol, ncols, table, rec, hdr, n_out, nullptr, conv_out, OCOCC_BF16,
-                      (hipStream_t)stream_, &ln);
-}
-
 extern "C" int64_t ococc_sparse_conv_sorted_lnbwd_partial_rows(int64_t n_out) {
   return n_out < 0 ? -1 : (int64_t)sorted_grid(n_out > 0 ? n_out : 1);
 }
 
-extern "C" int ococc_sparse_conv_sorted_lnbwd_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn,
-                                                   int32_t kvol, int32_t ncols, const int32_t* table, const int32_t* rec,
-                                                   const int32_t* hdr, int64_t n_out, const uint16_t* block_conv_out,
-                                                   const float* mean_rstd, const float* gamma, const float* beta,
-                                                   int32_t act, uint16_t* d_conv_out, float* partials,
-                                                   int64_t partial_rows, ococc_stream_t stream_) {
-  OCOCC_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (gelu)");
-  OCOCC_REQUIRE(ncols == 32 || ncols == 64, "fused LayerNorm backward: 32 or 64 output columns");
-  OCOCC_REQUIRE(n_out == 0 || (gamma && beta && block_conv_out && mean_rstd && d_conv_out && partials), "null pointer");
-  OCOCC_REQUIRE(partial_rows >= ococc_sparse_conv_sorted_lnbwd_partial_rows(n_out), "partials too small");
-  const SortedLn ln{block_conv_out, mean_rstd, gamma, beta, act, partials, 0.f, nullptr, nullptr};
-  return sorted_entry(feat, n_in, kd, wn, kvol, ncols, table, rec, hdr, n_out, nullptr, d_conv_out, OCOCC_BF16,
-                      (hipStream_t)stream_, &ln);
+extern "C" int ococc_sparse_conv_sorted_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn,
+                                             int32_t kvol, int32_t ncols, const int32_t* table, const int32_t* rec,
+                                             const int32_t* hdr, int64_t n_out, const float* bias, void* out,
+                                             int32_t out_dtype, const ococc_conv_ln* ln, ococc_stream_t stream_) {
+  if (!ln)
+    return sorted_entry(feat, n_in, kd, wn, kvol, ncols, table, rec, hdr, n_out, bias, out, out_dtype,
+                        (hipStream_t)stream_, nullptr);
+  OCOCC_REQUIRE(!bias && out_dtype == OCOCC_BF16, "LayerNorm epilogue: no bias, bf16 output");
+  OCOCC_REQUIRE(ln->act == 0 || ln->act == 1, "act must be 0 (none) or 1 (gelu)");
+  if (ln->backward) {
+    OCOCC_REQUIRE(ncols == 32 || ncols == 64, "fused LayerNorm backward: 32 or 64 output columns");
+    OCOCC_REQUIRE(n_out == 0 || (ln->gamma && ln->beta && ln->block_conv_out && ln->mean_rstd && out && ln->partials),
+                  "null pointer");
+    OCOCC_REQUIRE(ln->partial_rows >= ococc_sparse_conv_sorted_lnbwd_partial_rows(n_out), "partials too small");
+  } else {
+    OCOCC_REQUIRE(n_out == 0 || (ln->gamma && ln->beta && out && ln->y && ln->mean_rstd), "null pointer");
+  }
+  // (act_out set selects the forward epilogue's kernel, partials the backward's)
+  const SortedLn sln = ln->backward
+      ? SortedLn{ln->block_conv_out, ln->mean_rstd, ln->gamma, ln->beta, ln->act, ln->partials, 0.f, nullptr, nullptr}
+      : SortedLn{nullptr, nullptr, ln->gamma, ln->beta, ln->act, nullptr, ln->eps, ln->y, ln->mean_rstd};
+  return sorted_entry(feat, n_in, kd, wn, kvol, ncols, table, rec, hdr, n_out, nullptr, out, OCOCC_BF16,
+                      (hipStream_t)stream_, &sln);
 }
 
 #ifdef OCOCC_SORTED_STAMPS

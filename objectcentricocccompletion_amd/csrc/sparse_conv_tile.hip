@@ -549,29 +549,9 @@ extern "C" int ococc_tile_set_stamps(long long* dev_buffer) {
 }
 #endif
 
-extern "C" int ococc_sparse_conv_tile_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn,
-                                           int32_t kvol, int32_t ncols, const int32_t* table, int32_t dense_k,
-                                           int64_t n_out, const float* bias, void* out, int32_t out_dtype,
-                                           ococc_stream_t stream_) {
-  return tile_entry(feat, n_in, kd, wn, kvol, ncols, table, dense_k, n_out, bias, out, out_dtype,
-                    (hipStream_t)stream_, nullptr);
-}
-
-extern "C" int ococc_sparse_conv_tile_ln_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn,
-                                              int32_t kvol, int32_t ncols, const int32_t* table, int32_t dense_k,
-                                              int64_t n_out, const float* gamma, const float* beta, float eps,
-                                              int32_t act, uint16_t* conv_out, uint16_t* y, float* mean_rstd,
-                                              ococc_stream_t stream_) {
-  OCOCC_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (gelu)");
-  OCOCC_REQUIRE(n_out == 0 || (gamma && beta && y && mean_rstd), "null pointer");
-  const TileLn ln{gamma, beta, eps, act, y, mean_rstd, nullptr};
-  return tile_entry(feat, n_in, kd, wn, kvol, ncols, table, dense_k, n_out, nullptr, conv_out, OCOCC_BF16,
-                    (hipStream_t)stream_, &ln);
-}
-
 namespace {
 // rows of the tile the launcher picks for a shape (launch_tile above)
-inline int tile_rows_for(int kd, int ncols) { return (ncols >= 128 || kd <= 64) ? 256 : kTileLnbRows; }   // (only the LNB entry asks)
+inline int tile_rows_for(int kd, int ncols) { return (ncols >= 128 || kd <= 64) ? 256 : kTileLnbRows; }   // (only the LNB check asks)
 }  // namespace
 
 extern "C" int64_t ococc_sparse_conv_tile_lnbwd_partial_rows(int64_t n_out, int32_t kd, int32_t ncols) {
@@ -579,17 +559,27 @@ extern "C" int64_t ococc_sparse_conv_tile_lnbwd_partial_rows(int64_t n_out, int3
   return ococc_align_up(ococc_cdiv(n_out > 0 ? n_out : 1, tile_rows_for(kd, ncols)), 8);
 }
 
-extern "C" int ococc_sparse_conv_tile_lnbwd_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn,
-                                                 int32_t kvol, int32_t ncols, const int32_t* table, int32_t dense_k,
-                                                 int64_t n_out, const uint16_t* block_conv_out,
-                                                 const float* mean_rstd, const float* gamma, const float* beta,
-                                                 int32_t act, uint16_t* d_conv_out, float* partials,
-                                                 int64_t partial_rows, ococc_stream_t stream_) {
-  OCOCC_REQUIRE(act == 0 || act == 1, "act must be 0 (none) or 1 (gelu)");
-  OCOCC_REQUIRE(ncols == 32 || ncols == 64, "fused LayerNorm backward: 32 or 64 output columns");
-  OCOCC_REQUIRE(n_out == 0 || (gamma && beta && block_conv_out && mean_rstd && d_conv_out && partials), "null pointer");
-  OCOCC_REQUIRE(partial_rows >= ococc_sparse_conv_tile_lnbwd_partial_rows(n_out, kd, ncols), "partials too small");
-  const TileLn ln{gamma, beta, 0.f, act, const_cast<uint16_t*>(block_conv_out), const_cast<float*>(mean_rstd), partials};
-  return tile_entry(feat, n_in, kd, wn, kvol, ncols, table, dense_k, n_out, nullptr, d_conv_out, OCOCC_BF16,
-                    (hipStream_t)stream_, &ln);
+extern "C" int ococc_sparse_conv_tile_bf16(const uint16_t* feat, int64_t n_in, int32_t kd, const uint16_t* wn,
+                                           int32_t kvol, int32_t ncols, const int32_t* table, int32_t dense_k,
+                                           int64_t n_out, const float* bias, void* out, int32_t out_dtype,
+                                           const ococc_conv_ln* ln, ococc_stream_t stream_) {
+  if (!ln)
+    return tile_entry(feat, n_in, kd, wn, kvol, ncols, table, dense_k, n_out, bias, out, out_dtype,
+                      (hipStream_t)stream_, nullptr);
+  OCOCC_REQUIRE(!bias && out_dtype == OCOCC_BF16, "LayerNorm epilogue: no bias, bf16 output");
+  OCOCC_REQUIRE(ln->act == 0 || ln->act == 1, "act must be 0 (none) or 1 (gelu)");
+  if (ln->backward) {
+    OCOCC_REQUIRE(ncols == 32 || ncols == 64, "fused LayerNorm backward: 32 or 64 output columns");
+    OCOCC_REQUIRE(n_out == 0 || (ln->gamma && ln->beta && ln->block_conv_out && ln->mean_rstd && out && ln->partials),
+                  "null pointer");
+    OCOCC_REQUIRE(ln->partial_rows >= ococc_sparse_conv_tile_lnbwd_partial_rows(n_out, kd, ncols), "partials too small");
+  } else {
+    OCOCC_REQUIRE(n_out == 0 || (ln->gamma && ln->beta && ln->y && ln->mean_rstd), "null pointer");
+  }
+  // (backward: y / mean_rstd are the block's saved conv output and statistics, read; partials set selects the LNB kernel)
+  const TileLn tln = ln->backward
+      ? TileLn{ln->gamma, ln->beta, 0.f, ln->act, const_cast<uint16_t*>(ln->block_conv_out), ln->mean_rstd, ln->partials}
+      : TileLn{ln->gamma, ln->beta, ln->eps, ln->act, ln->y, ln->mean_rstd, nullptr};
+  return tile_entry(feat, n_in, kd, wn, kvol, ncols, table, dense_k, n_out, nullptr, out, OCOCC_BF16,
+                    (hipStream_t)stream_, &tln);
 }

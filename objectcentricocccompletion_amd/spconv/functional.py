@@ -17,9 +17,9 @@ class LnBackwardLink(object):
 class chain_ln_backward(object):
     """Inside this context the output of a conv -> LN -> act block (``indice_conv_ln``) that goes STRAIGHT into the next
     block's convolution, and nowhere else, has its LayerNorm backward fused into that convolution's input-gradient
-    kernel (ococc_sparse_conv_tile_lnbwd_bf16): the gradient that travels between the two autograd nodes is then the
-    gradient of the block's CONV output, not of its activation output -- hooks on the tensor in between would see
-    that.  The promise "nowhere else" is the caller's (occ_encoder.SubMOccEncoder: a plain stack); a second consumer
+    kernel (the backward epilogue of ococc_sparse_conv_tile_bf16 / _sorted_bf16): the gradient that travels between
+    the two autograd nodes is then the gradient of the block's CONV output, not of its activation output -- hooks on
+    the tensor in between would see that.  The promise "nowhere else" is the caller's (occ_encoder.SubMOccEncoder: a plain stack); a second consumer
     is detected in the backward pass (the incoming gradient is not the buffer the fused kernel wrote) and raises."""
     active = False
 

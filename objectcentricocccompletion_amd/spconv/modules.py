@@ -19,7 +19,7 @@ def is_spconv_module(module):
 
 
 # Run the LayerNorm (+GELU) that follows a sparse conv inside the conv kernel's epilogue
-# (ococc_sparse_conv_gather_gemm_ln_bf16).  Off by default: measured on configs[1] the fused epilogue costs
+# (the LayerNorm epilogue of ococc_sparse_conv_gather_gemm_bf16).  Off by default: measured on configs[1] the fused epilogue costs
 # what the separate LN kernel costs (the workgroups of the conv kernel reach their epilogue together, so the
 # extra erf / statistics work is not hidden behind anyone's MFMA phase) -- 560 vs 551 us of kernels per step.
 FUSE_CONV_LN = os.environ.get('OCOCC_FUSE_CONV_LN', '0') == '1'

@@ -2,7 +2,8 @@
 (get_indice_pairs, indice_conv, indice_conv_backward with the same argument order).
 
 Device work: ococc_subm_rulebook_build, ococc_rulebook_pairs_to_table,
-ococc_weight_prepare_bf16, ococc_sparse_conv_gather_gemm_bf16 (forward and dgrad),
+ococc_weight_prepare_bf16, ococc_sparse_conv_{gather_gemm,tile,sorted}_bf16 (forward and dgrad,
+optionally with a LayerNorm epilogue: _conv_family picks the kernel, _conv launches it),
 ococc_sparse_conv_wgrad_bf16.  The reference's per-offset gather/GEMM/scatter loop
 (include/spconv/spconv_ops.h:260-456) does not exist here.
 """
@@ -523,11 +524,11 @@ def prepare_weights(items):
             continue
         kd, nc = (cin, cout) if mode == 0 else (cout, cin)
         if mode in (0, 1) and current_density() is not None:
-            # the layer will go through the tile kernel (same test as in indice_conv / indice_conv_backward for a
-            # rulebook built under the current default density): fragment-major order
+            # the layer will go through the tile kernel (the family indice_conv / indice_conv_backward pick for a
+            # rulebook built under the current default density; the tile test reads no row count): fragment-major order
             probe_rb = RulebookTables(True, filters.numel() // (cin * cout))
             probe_rb.pairs_per_row = current_density()
-            if _fragment_major(probe_rb, kd, nc):
+            if _conv_family(probe_rb, kd, nc, 0) == 'tile':
                 mode += 4
         kvol = filters.numel() // (cin * cout)
         key = (filters.data_ptr(), mode, kd, nc)
@@ -865,13 +866,49 @@ def row_order(rb, table, rows, rowrec=None):
     return hit[0], hit[1]
 
 
-def _fragment_major(rb, kd, ncols):
-    """the tile kernel loads its weight fragments straight from L2 and wants them in fragment-major order (prepare
-    mode + 4)"""
-    return _use_tile_kernel(rb, kd, ncols)
+def _conv_family(rb, kd, ncols, rows, epilogue=None):
+    """The kernel family a convolution launch runs on: 'tile', 'sorted' or 'stationary' (rb None: not a sub-manifold
+    layer).  ``epilogue``: None (plain), 'ln' (the LayerNorm(+act) forward of its block: a family without that epilogue
+    for the shape leaves it to 'stationary') or 'lnbwd' (a dgrad with the LayerNorm backward of the block in front: None
+    when no kernel fuses it).  The one place these conditions meet: the weight layout (fragment-major, prepare mode + 4,
+    exactly for 'tile'), the launch and the decision to fuse all ask here."""
+    if _use_tile_kernel(rb, kd, ncols):
+        family = 'tile'
+    elif _use_sorted_kernel(rb, kd, ncols) and 0 < rows < ORDER_MAX_ROWS:
+        family = 'sorted'
+    else:
+        family = 'stationary'
+    if epilogue == 'ln':
+        if (family == 'tile' and not (kd in (32, 64) and ncols in (32, 64))) or (family == 'sorted' and not SORTED_CONV_LN):
+            return 'stationary'
+    elif epilogue == 'lnbwd':
+        return family if FUSE_LN_BACKWARD and ncols in (32, 64) and family != 'stationary' else None
+    return family
 
 
-def _gather_gemm(x_bf16, wn, table, mask, rows, bias, out_dtype, rb=None):
+def _conv(family, x, wn, table, mask, rows, out, out_dtype=torch.bfloat16, bias=None, rb=None, ln=None):
+    """One launch of ``family``'s kernel (ococc_sparse_conv_{tile,sorted,gather_gemm}_bf16) into ``out``, counted and
+    timed as family, family_ln or family_lnbwd.  ``ln``: an L.ConvLn epilogue, None for a plain convolution.  Returns
+    ``out``, or None when a LayerNorm forward epilogue has no kernel for the shape (the caller runs the two ops)."""
+    kvol, ncols, kd = wn.shape
+    if family == 'tile':
+        fn, where = L.lib.ococc_sparse_conv_tile_bf16, (L.ptr(table), kvol // 2)
+    elif family == 'sorted':
+        rec, hdr = row_order(rb, table, rows)
+        fn, where = L.lib.ococc_sparse_conv_sorted_bf16, (L.ptr(table), L.ptr(rec), L.ptr(hdr))
+    else:
+        fn, where = L.lib.ococc_sparse_conv_gather_gemm_bf16, (L.ptr(table), L.ptr(mask))
+    key = family if ln is None else family + ('_lnbwd' if ln.backward else '_ln')
+    rc = _launch(key, kd, ncols, lambda: fn(L.ptr(x), x.size(0), kd, L.ptr(wn), kvol, ncols, *where, rows, L.ptr(bias),
+                                            L.ptr(out), L.dtype_code(out_dtype), ln, L.stream()))
+    if rc == -3 and ln is not None and not ln.backward:  # OCOCC_EUNSUPPORTED: no fused kernel for this shape
+        launches[key] -= 1
+        return None
+    L.check(rc, 'sparse_conv ' + key)
+    return out
+
+
+def _gather_gemm(x_bf16, wn, table, mask, rows, bias, out_dtype, family='stationary', rb=None):
     kvol, ncols, kd = wn.shape
     if kvol > 32:
         # Kernel volumes above 32 offsets (5 x 5 x 5, 1 x 7 x 7, ...: the reference's indiceConv loops over any number,
@@ -884,31 +921,12 @@ def _gather_gemm(x_bf16, wn, table, mask, rows, bias, out_dtype, rb=None):
             L.check(L.lib.ococc_sparse_conv_gather_gemm_bf16(L.ptr(x_bf16), x_bf16.size(0), kd, L.ptr(wn[k0:k0 + 32]),
                                                              min(32, kvol - k0), ncols, L.ptr(table[k0:k0 + 32]), None, rows,
                                                              L.ptr(bias) if k0 == 0 else None, L.ptr(part),
-                                                             L.dtype_code(torch.float32), L.stream()),
+                                                             L.dtype_code(torch.float32), None, L.stream()),
                     'sparse_conv_gather_gemm')
             acc = part if acc is None else acc.add_(part)
         return acc if out_dtype == torch.float32 else acc.to(out_dtype)
     out = torch.empty((rows, ncols), dtype=out_dtype, device=x_bf16.device)
-    if _use_tile_kernel(rb, kd, ncols):  # (the caller prepared wn in fragment-major order under the same test)
-        _launch('tile', kd, ncols, lambda: L.check(
-            L.lib.ococc_sparse_conv_tile_bf16(L.ptr(x_bf16), x_bf16.size(0), kd, L.ptr(wn), kvol, ncols,
-                                              L.ptr(table), kvol // 2, rows, L.ptr(bias), L.ptr(out),
-                                              L.dtype_code(out_dtype), L.stream()), 'sparse_conv_tile'))
-        return out
-    if _use_sorted_kernel(rb, kd, ncols) and 0 < rows < ORDER_MAX_ROWS:
-        rec, hdr = row_order(rb, table, rows)
-        _launch('sorted', kd, ncols, lambda: L.check(
-            L.lib.ococc_sparse_conv_sorted_bf16(L.ptr(x_bf16), x_bf16.size(0), kd, L.ptr(wn), kvol, ncols,
-                                                L.ptr(table), L.ptr(rec), L.ptr(hdr), rows,
-                                                L.ptr(bias), L.ptr(out), L.dtype_code(out_dtype), L.stream()),
-            'sparse_conv_sorted'))
-        return out
-    _launch('stationary', kd, ncols, lambda: L.check(
-        L.lib.ococc_sparse_conv_gather_gemm_bf16(L.ptr(x_bf16), x_bf16.size(0), kd, L.ptr(wn),
-                                                 kvol, ncols, L.ptr(table), L.ptr(mask), rows,
-                                                 L.ptr(bias), L.ptr(out),
-                                                 L.dtype_code(out_dtype), L.stream()), 'sparse_conv_gather_gemm'))
-    return out
+    return _conv(family, x_bf16, wn, table, mask, rows, out, out_dtype, bias, rb)
 
 
 # The kernels contract over at most 128 channels and write at most 128 columns per launch.  Wider layers (the
@@ -973,14 +991,15 @@ def indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_o
     kd = _round_kd(cin)
     nc = (cout + 15) // 16 * 16
     x = _to_bf16_padded(features, kd)
-    tile = _fragment_major(rb if subm else None, kd, nc)
-    wn = _prep_weights(filters, 4 if tile else 0, kd, nc)  # +4: fragment-major order for the tile kernel
+    rb = rb if subm else None
+    family = _conv_family(rb, kd, nc, rows)
+    wn = _prep_weights(filters, 4 if family == 'tile' else 0, kd, nc)  # +4: fragment-major order for the tile kernel
     b = None
     if bias is not None:
         b = torch.zeros((nc,), dtype=torch.float32, device=features.device)
         b[:cout] = bias.float()
     out_dtype = torch.bfloat16 if features.dtype == torch.bfloat16 else torch.float32
-    out = _gather_gemm(x, wn, table, mask, rows, b, out_dtype, rb if subm else None)
+    out = _gather_gemm(x, wn, table, mask, rows, b, out_dtype, family, rb)
     if _saved is not None:
         _saved['x_bf16'] = x
     return out if nc == cout else out[:, :cout].contiguous()
@@ -989,31 +1008,18 @@ def indice_conv(features, filters, indice_pairs, indice_pair_num, num_activate_o
 SORTED_CONV_LN = os.environ.get('OCOCC_SORTED_CONV_LN', '1') == '1'
 
 
-def _sorted_ln_shape(rb, cin, cout, rows):
-    return _use_sorted_kernel(rb, cin, cout) and 0 < rows < ORDER_MAX_ROWS
-
-
-def _tile_ln_shape(cin, cout):
-    return cin in (32, 64) and cout in (32, 64)  # instantiations of ococc_sparse_conv_tile_ln_bf16
-
-
 def ln_fusion_kind(indice_pairs, indice_pair_num, num_activate_out, inverse, subm, cin, cout):
     """Which kernel a conv -> LayerNorm(+GELU) block would fuse into: 'tile' (the compact-then-multiply kernel has
-    the finished f32 row in LDS: the epilogue is nearly free and the separate LN launch disappears), 'first' (the
-    16 -> 32 input layer, measured ahead fused) or 'stationary' (the other output-stationary kernels: measured no
-    faster than the two launches, opt-in)."""
+    the finished f32 row in LDS: the epilogue is nearly free and the separate LN launch disappears), 'sorted' (round 6:
+    rows in neighbour-pattern order, the finished row in the registers of four lanes -- the 64 -> 128 forward of
+    configs[1], whose separate LN launch read 32 MB straight back), 'first' (the 16 -> 32 input layer, measured ahead
+    fused) or 'stationary' (the other output-stationary kernels: measured no faster than the two launches, opt-in)."""
     if (cin, cout) == (16, 32):
         return 'first'  # the resident-weights kernel at two 16-row blocks per wave: 19.9 us against 15.5 + 7.4 us
     if not subm:
         return 'stationary'
     rb, _ = _tables_for(indice_pairs, indice_pair_num, inverse, 'fwd', int(num_activate_out), subm)
-    if _tile_ln_shape(cin, cout) and _use_tile_kernel(rb, cin, cout):
-        return 'tile'
-    # 'sorted' (round 6): rows in neighbour-pattern order, the finished row in the registers of four lanes -- the
-    # 64 -> 128 forward of configs[1], whose separate LN launch read 32 MB straight back
-    if SORTED_CONV_LN and _sorted_ln_shape(rb, cin, cout, int(num_activate_out)):
-        return 'sorted'
-    return 'stationary'
+    return _conv_family(rb, cin, cout, int(num_activate_out), 'ln')
 
 
 def indice_conv_ln(features, filters, gamma, beta, eps, act, indice_pairs, indice_pair_num, num_activate_out,
@@ -1028,38 +1034,17 @@ def indice_conv_ln(features, filters, gamma, beta, eps, act, indice_pairs, indic
     rb, (table, mask, rows) = _tables_for(indice_pairs, indice_pair_num, inverse, 'fwd',
                                           int(num_activate_out), subm)
     x = _to_bf16_padded(features, cin)
-    tile = subm and _tile_ln_shape(cin, cout) and _use_tile_kernel(rb, cin, cout)
-    in_order = (not tile) and subm and SORTED_CONV_LN and _sorted_ln_shape(rb, cin, cout, rows)
-    wn = _prep_weights(filters, 4 if tile else 0, cin, cout)
+    rb = rb if subm else None
+    family = _conv_family(rb, cin, cout, rows, 'ln')
+    wn = _prep_weights(filters, 4 if family == 'tile' else 0, cin, cout)
     conv_out = torch.empty((rows, cout), dtype=torch.bfloat16, device=x.device)
     y = torch.empty_like(conv_out)
     stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
     g32, b32 = gamma.float().contiguous(), beta.float().contiguous()
-    kvol = wn.shape[0]
-    if tile:
-        def run():
-            return L.lib.ococc_sparse_conv_tile_ln_bf16(L.ptr(x), x.size(0), cin, L.ptr(wn), kvol, cout, L.ptr(table),
-                                                        kvol // 2, rows, L.ptr(g32), L.ptr(b32), float(eps), int(act),
-                                                        L.ptr(conv_out), L.ptr(y), L.ptr(stats), L.stream())
-    elif in_order:
-        rec, hdr = row_order(rb, table, rows)
-
-        def run():
-            return L.lib.ococc_sparse_conv_sorted_ln_bf16(L.ptr(x), x.size(0), cin, L.ptr(wn), kvol, cout, L.ptr(table),
-                                                          L.ptr(rec), L.ptr(hdr), rows, L.ptr(g32), L.ptr(b32), float(eps),
-                                                          int(act), L.ptr(conv_out), L.ptr(y), L.ptr(stats), L.stream())
-    else:
-        def run():
-            return L.lib.ococc_sparse_conv_gather_gemm_ln_bf16(L.ptr(x), x.size(0), cin, L.ptr(wn), kvol, cout,
-                                                               L.ptr(table), L.ptr(mask), rows, L.ptr(g32), L.ptr(b32),
-                                                               float(eps), int(act), L.ptr(conv_out), L.ptr(y),
-                                                               L.ptr(stats), L.stream())
-    family = 'tile_ln' if tile else ('sorted_ln' if in_order else 'stationary_ln')
-    rc = _launch(family, cin, cout, run)
-    if rc == -3:  # OCOCC_EUNSUPPORTED: no fused kernel for this shape
-        launches[family] -= 1
+    ln = L.ConvLn(backward=0, act=int(act), eps=float(eps), gamma=L.ptr(g32), beta=L.ptr(b32), y=L.ptr(y),
+                  mean_rstd=L.ptr(stats))
+    if _conv(family, x, wn, table, mask, rows, conv_out, rb=rb, ln=ln) is None:
         return None
-    L.check(rc, 'sparse_conv_gather_gemm_ln')
     if _saved is not None:
         _saved['x_bf16'] = x
         _saved['g32'], _saved['b32'] = g32, b32
@@ -1177,43 +1162,28 @@ def indice_conv_backward(features, filters, out_bp, indice_pairs, indice_pair_nu
                                               subm)
         nc = (cin + 15) // 16 * 16
         mode = 1 if (rb.subm and subm) else 2
-        if mode == 1 and _fragment_major(rb, kd_out, nc):
+        rb = rb if mode == 1 else None
+        family = _conv_family(rb, kd_out, nc, rows)
+        if family == 'tile':
             mode = 5  # fragment-major order for the tile kernel
         wn = _prep_weights(filters, mode, kd_out, nc)
         out_dtype = torch.bfloat16 if features.dtype == torch.bfloat16 else torch.float32
-        if (_ln_link is not None and FUSE_LN_BACKWARD and mode == 5 and nc == cin and nc in (32, 64)
-                and out_dtype == torch.bfloat16 and _ln_link.conv_out is not None
-                and tuple(_ln_link.conv_out.shape) == (rows, nc)):
+        fuse = (_ln_link is not None and nc == cin and out_dtype == torch.bfloat16 and _ln_link.conv_out is not None
+                and tuple(_ln_link.conv_out.shape) == (rows, nc) and _conv_family(rb, kd_out, nc, rows, 'lnbwd'))
+        if fuse:
             # the block in front (conv -> LN -> act) gets its LayerNorm backward in this kernel's epilogue: what
             # leaves is the gradient of ITS conv output (functional.LnBackwardLink)
-            prows = int(L.lib.ococc_sparse_conv_tile_lnbwd_partial_rows(rows, kd_out, nc))
+            prows = int(L.lib.ococc_sparse_conv_tile_lnbwd_partial_rows(rows, kd_out, nc) if fuse == 'tile'
+                        else L.lib.ococc_sparse_conv_sorted_lnbwd_partial_rows(rows))
             partials = L.empty((prows, 2 * nc), torch.float32, features.device)
             gin = L.empty((rows, nc), torch.bfloat16, features.device)
-            kvol = wn.shape[0]
-            _launch('tile_lnbwd', kd_out, nc, lambda: L.check(L.lib.ococc_sparse_conv_tile_lnbwd_bf16(
-                L.ptr(dy), dy.size(0), kd_out, L.ptr(wn), kvol, nc, L.ptr(table), kvol // 2, rows,
-                L.ptr(_ln_link.conv_out), L.ptr(_ln_link.stats), L.ptr(_ln_link.g32), L.ptr(_ln_link.b32),
-                int(_ln_link.act), L.ptr(gin), L.ptr(partials), prows, L.stream()), 'sparse_conv_tile_lnbwd'))
+            ln = L.ConvLn(backward=1, act=int(_ln_link.act), gamma=L.ptr(_ln_link.g32), beta=L.ptr(_ln_link.b32),
+                          mean_rstd=L.ptr(_ln_link.stats), block_conv_out=L.ptr(_ln_link.conv_out),
+                          partials=L.ptr(partials), partial_rows=prows)
+            _conv(fuse, dy, wn, table, None, rows, gin, rb=rb, ln=ln)
             _ln_link.fused, _ln_link.partials, _ln_link.rows = True, partials, prows
             _ln_link.expect = (gin.data_ptr(), gin._version)   # (the engine may add a second consumer's gradient in place)
             return gin, filters_bp
-        if (_ln_link is not None and FUSE_LN_BACKWARD and mode == 1 and nc == cin and nc in (32, 64)
-                and out_dtype == torch.bfloat16 and _ln_link.conv_out is not None
-                and tuple(_ln_link.conv_out.shape) == (rows, nc) and _use_sorted_kernel(rb, kd_out, nc)
-                and 0 < rows < ORDER_MAX_ROWS):
-            # the same fusion on the neighbour-pattern-order kernel (the finished f32 row sits in four lanes' accumulators)
-            rec, hdr = row_order(rb, table, rows)
-            prows = int(L.lib.ococc_sparse_conv_sorted_lnbwd_partial_rows(rows))
-            partials = L.empty((prows, 2 * nc), torch.float32, features.device)
-            gin = L.empty((rows, nc), torch.bfloat16, features.device)
-            kvol = wn.shape[0]
-            _launch('sorted_lnbwd', kd_out, nc, lambda: L.check(L.lib.ococc_sparse_conv_sorted_lnbwd_bf16(
-                L.ptr(dy), dy.size(0), kd_out, L.ptr(wn), kvol, nc, L.ptr(table), L.ptr(rec), L.ptr(hdr), rows,
-                L.ptr(_ln_link.conv_out), L.ptr(_ln_link.stats), L.ptr(_ln_link.g32), L.ptr(_ln_link.b32),
-                int(_ln_link.act), L.ptr(gin), L.ptr(partials), prows, L.stream()), 'sparse_conv_sorted_lnbwd'))
-            _ln_link.fused, _ln_link.partials, _ln_link.rows = True, partials, prows
-            _ln_link.expect = (gin.data_ptr(), gin._version)
-            return gin, filters_bp
-        gin = _gather_gemm(dy, wn, table, mask, rows, None, out_dtype, rb if mode in (1, 5) else None)
+        gin = _gather_gemm(dy, wn, table, mask, rows, None, out_dtype, family, rb)
         input_bp = gin if nc == cin else gin[:, :cin].contiguous()
     return input_bp, filters_bp

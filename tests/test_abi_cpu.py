@@ -52,6 +52,31 @@ def test_argument_errors_are_reported_not_thrown():
     assert rc == -1 and b'dropout_p' in L.lib.ococc_last_error()
 
 
+def test_conv_layernorm_descriptor_layout():
+    """The LayerNorm epilogue descriptor of the three convolution exports (ococc_conv_ln, _lib.ConvLn), pinned field by
+    field through argument errors: every call has n_out = 0, so the checks run and nothing touches a device."""
+    from objectcentricocccompletion_amd import _lib as L
+
+    def tile(ncols, ln):
+        return L.lib.ococc_sparse_conv_tile_bf16(None, 0, 64, None, 27, ncols, None, 13, 0, None, None, L.BF16, ln, None)
+
+    def sorted_(partial_rows):
+        return L.lib.ococc_sparse_conv_sorted_bf16(None, 0, 64, None, 27, 64, None, None, None, 0, None, None, L.BF16,
+                                                   L.ConvLn(backward=1, act=1, partial_rows=partial_rows), None)
+
+    assert tile(64, L.ConvLn(act=1)) == 0
+    rc = tile(64, L.ConvLn(act=2))
+    assert rc == -1 and b'act' in L.lib.ococc_last_error()
+    assert tile(128, L.ConvLn(backward=0, act=1)) == 0
+    rc = tile(128, L.ConvLn(backward=1, act=1, partial_rows=1 << 20))
+    assert rc == -1 and b'32 or 64 output columns' in L.lib.ococc_last_error()
+    assert sorted_(L.lib.ococc_sparse_conv_sorted_lnbwd_partial_rows(0)) == 0
+    rc = sorted_(0)
+    assert rc == -1 and b'partials too small' in L.lib.ococc_last_error()
+    assert L.lib.ococc_sparse_conv_gather_gemm_bf16(None, 0, 64, None, 27, 64, None, None, 0, None, None, L.BF16,
+                                                    L.ConvLn(backward=1), None) == -3
+
+
 def test_ops_refuse_cpu_tensors():
     from objectcentricocccompletion_amd import _lib as L
     from objectcentricocccompletion_amd.voxel import dynamic_scatter, voxelization

@@ -178,7 +178,7 @@ def test_density_selects_the_order(dev):
 
 @pytest.mark.parametrize('static', [False, True])
 def test_layernorm_backward_in_the_pattern_order_dgrad(dev, static):
-    """ococc_sparse_conv_sorted_lnbwd_bf16: the LayerNorm (+ GELU) backward of block L in the epilogue of block L+1's
+    """ococc_sparse_conv_sorted_bf16's backward epilogue: the LayerNorm (+ GELU) backward of block L in the epilogue of block L+1's
     input-gradient pass, on the neighbour-pattern-order kernel (128 -> 64 and 64 -> 32 gathered -> written channels, the
     two LNB shapes of the configs[1] encoder).  Against (a) the same pass with the separate LN-backward launches: the
     gradients of the conv outputs are bit-identical, hence the conv weight gradients; d gamma / d beta are sums of the
@@ -232,9 +232,9 @@ def test_layernorm_backward_in_the_pattern_order_dgrad(dev, static):
 @pytest.mark.parametrize('density', [0.04, 0.12, 0.45])
 @pytest.mark.parametrize('act', [0, 1])
 def test_pattern_order_kernel_layernorm_epilogue(dev, cin, cout, density, act):
-    """ococc_sparse_conv_sorted_ln_bf16 (round 6: the conv -> LayerNorm -> GELU block of make_sparse_convmodule,
-    sparse_block.py:216-289, in ONE launch on the neighbour-pattern-order kernel) = ococc_sparse_conv_sorted_bf16 followed
-    by ococc_layernorm_act_fwd: the conv output bit for bit; the epilogue rounds to bf16 where the pair stores bf16 and
+    """ococc_sparse_conv_sorted_bf16 with the LayerNorm forward epilogue (round 6: the conv -> LayerNorm -> GELU block
+    of make_sparse_convmodule, sparse_block.py:216-289, in ONE launch on the neighbour-pattern-order kernel) = the plain
+    call followed by ococc_layernorm_act_fwd: the conv output bit for bit; the epilogue rounds to bf16 where the pair stores bf16 and
     sums in the LayerNorm kernel's order, so the statistics agree to f32 rounding and the activation except where a
     rounding tie flips.  Densities: tiles of all three classes (256-, 128- and 64-row tiles: four, two, one block per
     wave); a row count that is no multiple of anything; fixed-capacity padding rows (-1 coordinates) behind the live ones."""
@@ -277,7 +277,7 @@ def test_pattern_order_kernel_layernorm_epilogue(dev, cin, cout, density, act):
 @pytest.mark.parametrize('cin,cout', [(64, 128), (32, 64), (128, 64)])
 @pytest.mark.parametrize('act', [0, 1])
 def test_pattern_order_kernel_layernorm_epilogue_vs_oracle(dev, cin, cout, act):
-    """ococc_sparse_conv_sorted_ln_bf16 against the oracle's indiceConv (spconv_ops.h:300-354) followed by a float64
+    """ococc_sparse_conv_sorted_bf16's LayerNorm forward epilogue against the oracle's indiceConv (spconv_ops.h:300-354) followed by a float64
     LayerNorm(+GELU) on the bf16 conv output (what oracle/encoder_ref.py does for a make_sparse_convmodule block): conv
     output = RNE bf16 of the oracle's f32 result up to summation order, activation within a bf16 rounding of the float64
     value, row statistics to f32 accuracy."""

@@ -96,10 +96,10 @@ def test_density_hint_selects_the_kernel(dev):
 
 @pytest.mark.parametrize('cin,cout', [(32, 64), (64, 32), (32, 32), (64, 64)])
 @pytest.mark.parametrize('act', [0, 1])
-def test_tile_kernel_layernorm_epilogue(dev, cin, cout, act):
-    """ococc_sparse_conv_tile_ln_bf16 = ococc_sparse_conv_tile_bf16 followed by ococc_layernorm_act_fwd: the conv
-    output bit for bit, the statistics to f32 rounding, the activated output within one bf16 step; rows past the
-    last full tile and a row count that is no multiple of anything."""
+def test_tile_kernel_layernorm_forward_epilogue(dev, cin, cout, act):
+    """ococc_sparse_conv_tile_bf16 with the LayerNorm forward epilogue = the plain call followed by
+    ococc_layernorm_act_fwd: the conv output bit for bit, the statistics to f32 rounding, the activated output within
+    one bf16 step; rows past the last full tile and a row count that is no multiple of anything."""
     from objectcentricocccompletion_amd import _lib as L
     from objectcentricocccompletion_amd.spconv import ops
     shape = [12, 10, 11]
@@ -130,9 +130,9 @@ def test_tile_kernel_layernorm_epilogue(dev, cin, cout, act):
     assert float(d.max()) <= 2e-2 * float(y_ref.float().abs().max())          # <= one bf16 step at the top value
     assert float((d > 0).float().mean()) < 0.02                                # and only where a rounding tie flips
     # refused outside its shapes
-    assert L.lib.ococc_sparse_conv_tile_ln_bf16(L.ptr(x), n, 128, L.ptr(x), 27, 64, L.ptr(x), 13, n, L.ptr(gamma),
-                                                L.ptr(beta), 1e-3, act, L.ptr(conv_out), L.ptr(y), L.ptr(stats),
-                                                L.stream()) == -3
+    ln = L.ConvLn(backward=0, act=act, eps=1e-3, gamma=L.ptr(gamma), beta=L.ptr(beta), y=L.ptr(y), mean_rstd=L.ptr(stats))
+    assert L.lib.ococc_sparse_conv_tile_bf16(L.ptr(x), n, 128, L.ptr(x), 27, 64, L.ptr(x), 13, n, None, L.ptr(conv_out),
+                                             L.BF16, ln, L.stream()) == -3
 
 
 def test_block_fuses_layernorm_only_on_the_tile_kernel(dev):
@@ -242,7 +242,7 @@ def test_tile_kernel_forward_backward_vs_oracle(dev, cin, cout, density):
 @pytest.mark.parametrize('cin,cout', [(32, 64), (64, 32), (32, 32), (64, 64)])
 @pytest.mark.parametrize('act', [0, 1])
 def test_tile_kernel_layernorm_epilogue_vs_oracle(dev, cin, cout, act):
-    """ococc_sparse_conv_tile_ln_bf16 against the oracle's indiceConv followed by a float64 LayerNorm(+GELU)
+    """ococc_sparse_conv_tile_bf16's LayerNorm forward epilogue against the oracle's indiceConv followed by a float64 LayerNorm(+GELU)
     (sparse_block.py:216-289 builds conv -> LN -> act; the norm reads the bf16 conv output, as the two-launch path
     and oracle/encoder_ref.py do): conv output = RNE bf16 of the oracle's f32 result up to summation order,
     activated output within a bf16 rounding of the float64 value, row statistics to f32 accuracy."""
@@ -276,7 +276,7 @@ def test_tile_kernel_layernorm_epilogue_vs_oracle(dev, cin, cout, act):
 @pytest.mark.parametrize('static', [False, True])
 def test_layernorm_backward_inside_the_next_layers_dgrad(dev, static):
     """SubMOccEncoder declares its blocks a chain (functional.chain_ln_backward): the LayerNorm (+ GELU) backward of
-    block L runs in the epilogue of block L+1's input-gradient kernel (ococc_sparse_conv_tile_lnbwd_bf16).  Against the
+    block L runs in the epilogue of block L+1's input-gradient kernel (ococc_sparse_conv_tile_bf16, backward epilogue).  Against the
     same backward pass with the separate LN-backward launches: the conv-output gradients are bit-identical, hence the
     weight gradients too; d gamma / d beta are sums of the same terms grouped by other workgroups (tolerance)."""
     from objectcentricocccompletion_amd.occ_encoder import SubMOccEncoder, synthetic_object_grids

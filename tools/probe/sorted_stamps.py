@@ -41,12 +41,12 @@ lib.ococc_sorted_set_stamps.argtypes = [ctypes.c_void_p]
 assert lib.ococc_sorted_set_stamps(stamps.data_ptr()) == 0
 vp = ctypes.c_void_p
 lib.ococc_sparse_conv_sorted_bf16.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp,
-                                              ctypes.c_int64, vp, vp, ctypes.c_int32, vp]
+                                              ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.POINTER(L.ConvLn), vp]
 
 
 def run():
     rc = lib.ococc_sparse_conv_sorted_bf16(x.data_ptr(), n, kd, wn.data_ptr(), 27, nc, table.data_ptr(), rec.data_ptr(),
-                                           hdr.data_ptr(), n, None, out.data_ptr(), L.BF16, None)
+                                           hdr.data_ptr(), n, None, out.data_ptr(), L.BF16, None, None)
     assert rc == 0, rc
 
 

@@ -38,7 +38,7 @@ lib.ococc_tile_set_stamps.argtypes = [ctypes.c_void_p]
 assert lib.ococc_tile_set_stamps(stamps.data_ptr()) == 0
 vp = ctypes.c_void_p
 lib.ococc_sparse_conv_tile_bf16.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int32,
-                                            ctypes.c_int64, vp, vp, ctypes.c_int32, vp]
+                                            ctypes.c_int64, vp, vp, ctypes.c_int32, ctypes.POINTER(L.ConvLn), vp]
 
 
 LNB = len(sys.argv) > 3 and sys.argv[3] == 'lnbwd'   # the input-gradient instantiation with the LayerNorm-backward epilogue
@@ -51,19 +51,13 @@ if LNB:
     lib.ococc_sparse_conv_tile_lnbwd_partial_rows.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]
     prows = lib.ococc_sparse_conv_tile_lnbwd_partial_rows(n, kd, nc)
     partials = torch.empty((prows, 2 * nc), dtype=torch.float32, device=dev)
-    lib.ococc_sparse_conv_tile_lnbwd_bf16.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int32, vp,
-                                                      ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp, ctypes.c_int32, vp, vp,
-                                                      ctypes.c_int64, vp]
+ln = L.ConvLn(backward=1, act=1, gamma=gamma.data_ptr(), beta=beta.data_ptr(), mean_rstd=stats.data_ptr(),
+              block_conv_out=conv_out.data_ptr(), partials=partials.data_ptr(), partial_rows=prows) if LNB else None
 
 
 def run():
-    if LNB:
-        rc = lib.ococc_sparse_conv_tile_lnbwd_bf16(x.data_ptr(), n, kd, wn.data_ptr(), 27, nc, table.data_ptr(), 13, n,
-                                                   conv_out.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), 1,
-                                                   out.data_ptr(), partials.data_ptr(), prows, None)
-    else:
-        rc = lib.ococc_sparse_conv_tile_bf16(x.data_ptr(), n, kd, wn.data_ptr(), 27, nc, table.data_ptr(), 13, n, None,
-                                             out.data_ptr(), L.BF16, None)
+    rc = lib.ococc_sparse_conv_tile_bf16(x.data_ptr(), n, kd, wn.data_ptr(), 27, nc, table.data_ptr(), 13, n, None,
+                                         out.data_ptr(), L.BF16, ln, None)
     assert rc == 0, rc
 
 

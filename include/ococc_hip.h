@@ -550,6 +550,42 @@ int ococc_aligned_iou3d_f32(const float* boxes1, const float* boxes2, int64_t n,
                             ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * CTRL tracklet data preparation, host layer: objectcentricocccompletion_amd/ctrl_prep.py
+ *
+ * Max IoU of every (predicted, ground-truth) tracklet pair of one segment
+ * replaces the per-pair loop of tools/ctrl/generate_candidates.py:61-65 over LiDARTracklet.max_iou
+ *   (mmdet3d/core/bbox/structures/lidar_tracklet.py:210-229: timestamp intersection, two uploads, one
+ *   aligned_iou_3d launch and an .item() per pair) by ONE launch per segment.
+ * pd_boxes [sum Lp, 7] f32 the boxes of the P predicted tracklets back to back, pd_offsets [P+1] i32,
+ * pd_frames [sum Lp] i32: index of the box's timestamp in the segment's sorted timestamp list, strictly increasing
+ * within a tracklet; gt_* the same for the G ground-truth tracklets.  max_iou [P, G] f32: the maximum over the common
+ * frames of the one-to-one IoU (the arithmetic of ococc_aligned_iou3d_f32, bit for bit), 0 without a common frame.
+ * ------------------------------------------------------------------------ */
+int ococc_tracklet_max_iou_f32(const float* pd_boxes, const int32_t* pd_offsets, const int32_t* pd_frames,
+                               int32_t num_pd, const float* gt_boxes, const int32_t* gt_offsets,
+                               const int32_t* gt_frames, int32_t num_gt, float* max_iou, ococc_stream_t stream);
+
+/* Points of many frames into the boxes of their frames, the cloud's order kept
+ * replaces the per-frame, per-box loop of tools/ctrl/generate_track_input.py:84-99 (box upload, points_in_boxes over
+ *   the whole cloud, mask compaction, device-to-host copy, each per box) by one count launch, one read-back of
+ *   counts and one fill launch per batch of frames.  Membership: check_pt_in_box3d
+ *   (mmdet3d/ops/roiaware_pool3d/src/points_in_boxes_cuda.cu:24-49), every box on its own (a point may be in several).
+ * points [N, point_dim] f32 (point_dim >= 3, xyz read) of `frames` frames back to back, point_offsets [frames+1] i64;
+ * boxes [B, 7] f32 (x, y, z_bottom, w, l, h, yaw; already enlarged) grouped by frame, box_offsets [frames+1] i64;
+ * max_frame_points: the largest frame's point count (the host made the offsets).  frames <= 65535.
+ * workspace: ceil(max_frame_points / 4096) * 4 * B * 4 bytes, written by _count and read by _fill of the SAME input.
+ * _count: counts [B] i64.  _fill: scan [B+1] i64 = exclusive scan of counts (made by the host after the read-back),
+ * out_index [scan[B]] i64: the frame-local point indices of box b at [scan[b], scan[b+1]) in ASCENDING order. */
+int ococc_tracklet_crop_count(const float* points, int64_t num_points, int32_t point_dim,
+                              const int64_t* point_offsets, const float* boxes, int64_t num_boxes,
+                              const int64_t* box_offsets, int32_t frames, int64_t max_frame_points, int64_t* counts,
+                              void* workspace, int64_t workspace_bytes, ococc_stream_t stream);
+int ococc_tracklet_crop_fill(const float* points, int64_t num_points, int32_t point_dim, const int64_t* point_offsets,
+                             const float* boxes, int64_t num_boxes, const int64_t* box_offsets, int32_t frames,
+                             int64_t max_frame_points, const int64_t* scan, const void* workspace,
+                             int64_t workspace_bytes, int64_t* out_index, ococc_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * occupancy IoU counts of one chunk of RoIs, replacing the ATen chain of TrackletRoIHeadOCC.test_occ
  *   (mmdet3d/models/roi_heads/tracklet_roi_head_occ.py:394-486: repeat, inside-box test, *, ==, &, |, two sums).
  * logits [n, K] f32 (decoder output, cls_dim 1); labels [K] int64 (occupied: == 1);

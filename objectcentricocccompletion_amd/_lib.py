@@ -109,6 +109,10 @@ SIGNATURES = {
     'ococc_dynamic_point_pool_mixed': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, _F3, c_i32, c_i64, c_vp,
                                                c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'ococc_aligned_iou3d_f32': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    'ococc_tracklet_max_iou_f32': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    'ococc_tracklet_crop_count': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    'ococc_tracklet_crop_fill': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp,
+                                         c_vp]),
     'ococc_occ_iou_count': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_vp, c_i64, c_i64, c_vp]),
     'ococc_group_rank_workspace_bytes': (c_i64, [c_i64, c_i64]),
     'ococc_group_rank_i32': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),

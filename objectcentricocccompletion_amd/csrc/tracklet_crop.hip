@@ -1,0 +1,172 @@
+// Points of many frames into the (enlarged) tracklet boxes of their frames, the cloud's order kept: the crop of CTRL's
+// track-input generation (tools/ctrl/generate_track_input.py:84-99).  The reference does, per frame and per box, one
+// upload of the box, one points_in_boxes launch over the whole cloud, one boolean-mask compaction and one
+// device-to-host copy.  Here: one count launch, one read-back of counts [B], one fill launch per batch of frames.
+//
+// Membership is check_pt_in_box3d (mmdet3d/ops/roiaware_pool3d/src/points_in_boxes_cuda.cu:24-49), each box on its
+// own, so a point may fall into several (overlapping, enlarged) boxes:
+//   |z - (z_bottom + h/2)| <= h/2;  (dx, dy) turned by yaw + pi/2;  -l/2 < local_x < l/2,  -w/2 < local_y < w/2.
+//
+// Work split: blockIdx.y = frame, a workgroup of 4 waves takes 4096 consecutive points of the frame, each wave 1024
+// consecutive ones ("wave tile": 16 rounds of 64, lane = point, kept in registers, every point read ONCE per pass
+// however many boxes the frame has).  The frame's boxes are staged 64 at a time in LDS once per workgroup (centre,
+// half sizes, cos / sin, a conservative BEV radius for a cheap reject) and read as broadcasts.  Per box and round one
+// ballot: its popcount is the count, the popcount below the lane the rank -- (wave tile, round, lane) IS ascending
+// point order, so no sort.  Two levels: the count pass leaves the per-(wave tile, box) counts in the workspace
+// [wave tiles per frame, B] i32 (box-minor: the fill pass reads 64 boxes of one wave tile as one 256 B line); the fill
+// pass sums the earlier wave tiles of its frame in front of its own ranks.
+//
+// Algorithmic bytes per pass: N * 12 B of xyz (the rows are C * 4 B apart, so N * C * 4 B of cache lines move: 24 B
+// at C = 6), B * 28 B of boxes per workgroup (L2);  count: + T * B * 4 B workspace out, B * 8 B counts;
+// fill: + about T/2 * B * 4 B workspace in per wave tile (L2) and sum(counts) * 8 B of indices out.
+// T = wave tiles of the largest frame.  Vector stores only.
+#include "common.hpp"
+
+namespace {
+
+constexpr int kRounds = 16;                 // points per lane
+constexpr int kWaveTile = 64 * kRounds;     // 1024 points per wave
+constexpr int kWaves = 4;
+constexpr int kBlockTile = kWaveTile * kWaves;
+constexpr int kChunk = 64;                  // boxes staged at a time: one per lane
+
+template <bool FILL>
+__global__ void __launch_bounds__(64 * kWaves)
+tracklet_crop_kernel(const float* __restrict__ points, int32_t C, const int64_t* __restrict__ point_offsets,
+                     const float* __restrict__ boxes, const int64_t* __restrict__ box_offsets, int64_t B,
+                     int32_t* __restrict__ tile_counts, unsigned long long* __restrict__ counts,
+                     const int64_t* __restrict__ scan, int64_t* __restrict__ out_index) {
+  __shared__ float sb[9][kChunk];   // cx, cy, cz, hl, hw, hh, cos, sin, r^2
+  const int f = blockIdx.y;
+  const int64_t p0 = point_offsets[f], n = point_offsets[f + 1] - p0;
+  const int64_t tile0 = (int64_t)blockIdx.x * kBlockTile;
+  if (tile0 >= n) return;
+  const int64_t b0 = box_offsets[f];
+  const int nb = (int)(box_offsets[f + 1] - b0);
+  if (nb <= 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t w0 = tile0 + (int64_t)wave * kWaveTile;   // frame-local index of this wave's first point
+  const int64_t wt = (int64_t)blockIdx.x * kWaves + wave;  // wave tile of the frame
+
+  float px[kRounds], py[kRounds], pz[kRounds];
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+    const int64_t i = w0 + r * 64 + lane;
+    if (i < n) {
+      const float* q = points + (p0 + i) * C;
+      px[r] = q[0], py[r] = q[1], pz[r] = q[2];
+    } else {
+      px[r] = 0.f, py[r] = 0.f, pz[r] = INFINITY;   // fails the height test of every box
+    }
+  }
+
+  for (int c0 = 0; c0 < nb; c0 += kChunk) {
+    const int cn = min(kChunk, nb - c0);
+    __syncthreads();
+    if (tid < cn) {
+      const float* b = boxes + (b0 + c0 + tid) * 7;
+      const float hh = b[5] * 0.5f, hl = b[4] * 0.5f, hw = b[3] * 0.5f;
+      const float rot = (float)((double)b[6] + 1.5707963267948966);
+      sb[0][tid] = b[0], sb[1][tid] = b[1], sb[2][tid] = b[2] + hh;
+      sb[3][tid] = hl, sb[4][tid] = hw, sb[5][tid] = hh;
+      sb[6][tid] = cosf(rot), sb[7][tid] = sinf(rot);
+      sb[8][tid] = (hl * hl + hw * hw) * 1.001f + 1e-6f;   // |local|^2 < hl^2 + hw^2 inside; the slack covers rounding
+    }
+    __syncthreads();
+
+    int64_t base = 0, end = 0;   // lane j: where box c0 + j's points of this wave tile start / the box's end
+    if (FILL) {
+      if (lane < cn) {
+        const int64_t b = b0 + c0 + lane;
+        base = scan[b], end = scan[b + 1];
+        for (int64_t k = 0; k < wt; ++k) base += tile_counts[k * B + b];
+      }
+    }
+    int mine = 0;                // lane j: count of box c0 + j in this wave tile
+    for (int j = 0; j < cn; ++j) {
+      const float cx = sb[0][j], cy = sb[1][j], cz = sb[2][j], hl = sb[3][j], hw = sb[4][j], hh = sb[5][j];
+      const float ca = sb[6][j], sa = sb[7][j], r2 = sb[8][j];
+      const int64_t base_j = FILL ? __shfl(base, j, 64) : 0, end_j = FILL ? __shfl(end, j, 64) : 0;
+      int cnt = 0;               // wave-uniform
+#pragma unroll
+      for (int r = 0; r < kRounds; ++r) {
+        const float dx = px[r] - cx, dy = py[r] - cy;
+        bool in = !(fabsf(pz[r] - cz) > hh) && !(dx * dx + dy * dy > r2);
+        if (in) {
+          const float lx = dx * ca + dy * (-sa), ly = dx * sa + dy * ca;
+          in = (lx > -hl) & (lx < hl) & (ly > -hw) & (ly < hw);
+        }
+        const unsigned long long bal = __ballot(in);
+        if (FILL && in) {
+          const int64_t pos = base_j + cnt + __popcll(bal & ((1ull << lane) - 1ull));
+          if (pos < end_j) out_index[pos] = w0 + r * 64 + lane;   // (pos < end_j: counts and scan of the same input)
+        }
+        cnt += __popcll(bal);
+      }
+      if (lane == j) mine = cnt;
+    }
+    if (!FILL && lane < cn) {
+      const int64_t b = b0 + c0 + lane;
+      tile_counts[wt * B + b] = mine;   // zeros too: the fill pass reads every earlier wave tile of the frame
+      if (mine) atomicAdd(&counts[b], (unsigned long long)mine);
+    }
+  }
+}
+
+int crop_check(const float* points, int64_t n, int32_t c, const int64_t* point_offsets, const float* boxes, int64_t b,
+               const int64_t* box_offsets, int32_t frames, int64_t max_frame_points, const void* workspace,
+               int64_t workspace_bytes, const char* fn) {
+  if (n < 0 || b < 0 || frames < 0 || max_frame_points < 0 || max_frame_points > n)
+    return ococc_fail(OCOCC_EINVAL, fn, "negative size, or max_frame_points > num_points");
+  if (c < 3) return ococc_fail(OCOCC_EINVAL, fn, "points need at least 3 columns");
+  if (frames > 65535) return ococc_fail(OCOCC_EINVAL, fn, "at most 65535 frames per call");
+  if (b == 0 || n == 0 || frames == 0) return 1;
+  if (!points || !point_offsets || !boxes || !box_offsets || !workspace)
+    return ococc_fail(OCOCC_EINVAL, fn, "null pointer");
+  const int64_t tiles = ococc_cdiv(max_frame_points, kBlockTile) * kWaves;
+  if (workspace_bytes < tiles * b * (int64_t)sizeof(int32_t))
+    return ococc_fail(OCOCC_EINVAL, fn, "workspace too small: ceil(max_frame_points / 4096) * 4 * num_boxes * 4 bytes");
+  return OCOCC_OK;
+}
+
+}  // namespace
+
+extern "C" int ococc_tracklet_crop_count(const float* points, int64_t num_points, int32_t point_dim,
+                                         const int64_t* point_offsets, const float* boxes, int64_t num_boxes,
+                                         const int64_t* box_offsets, int32_t frames, int64_t max_frame_points,
+                                         int64_t* counts, void* workspace, int64_t workspace_bytes,
+                                         ococc_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const int rc = crop_check(points, num_points, point_dim, point_offsets, boxes, num_boxes, box_offsets, frames,
+                            max_frame_points, workspace, workspace_bytes, __func__);
+  if (rc < 0) return rc;
+  if (num_boxes > 0) {
+    OCOCC_REQUIRE(counts, "null counts");
+    OCOCC_HIP(hipMemsetAsync(counts, 0, num_boxes * sizeof(int64_t), stream));
+  }
+  if (rc == 1 || max_frame_points == 0) return OCOCC_OK;
+  const dim3 grid((unsigned)ococc_cdiv(max_frame_points, kBlockTile), (unsigned)frames);
+  hipLaunchKernelGGL(tracklet_crop_kernel<false>, grid, dim3(64 * kWaves), 0, stream, points, point_dim, point_offsets,
+                     boxes, box_offsets, num_boxes, (int32_t*)workspace, (unsigned long long*)counts,
+                     (const int64_t*)nullptr, (int64_t*)nullptr);
+  OCOCC_CHECK_LAUNCH();
+  return OCOCC_OK;
+}
+
+extern "C" int ococc_tracklet_crop_fill(const float* points, int64_t num_points, int32_t point_dim,
+                                        const int64_t* point_offsets, const float* boxes, int64_t num_boxes,
+                                        const int64_t* box_offsets, int32_t frames, int64_t max_frame_points,
+                                        const int64_t* scan, const void* workspace, int64_t workspace_bytes,
+                                        int64_t* out_index, ococc_stream_t stream_) {
+  const int rc = crop_check(points, num_points, point_dim, point_offsets, boxes, num_boxes, box_offsets, frames,
+                            max_frame_points, workspace, workspace_bytes, __func__);
+  if (rc < 0) return rc;
+  if (rc == 1 || max_frame_points == 0) return OCOCC_OK;
+  OCOCC_REQUIRE(scan && out_index, "null scan or out_index");
+  const dim3 grid((unsigned)ococc_cdiv(max_frame_points, kBlockTile), (unsigned)frames);
+  hipLaunchKernelGGL(tracklet_crop_kernel<true>, grid, dim3(64 * kWaves), 0, (hipStream_t)stream_, points, point_dim,
+                     point_offsets, boxes, box_offsets, num_boxes, (int32_t*)const_cast<void*>(workspace),
+                     (unsigned long long*)nullptr, scan, out_index);
+  OCOCC_CHECK_LAUNCH();
+  return OCOCC_OK;
+}

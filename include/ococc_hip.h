@@ -586,6 +586,34 @@ int ococc_tracklet_crop_fill(const float* points, int64_t num_points, int32_t po
                              int64_t workspace_bytes, int64_t* out_index, ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * Detection matching of the native Waymo metric: per frame, the full 3-D IoU of every (prediction, ground truth)
+ * pair of equal type and the score-first greedy assignment
+ * replaces the matching stage of compute_detection_metrics_main, the compiled waymo-open-dataset tool that
+ *   WaymoTrackletDataset.evaluate runs (mmdet3d/datasets/waymo_tracklet_dataset.py:352-366) and the reference ships
+ *   no source for; the protocol is the one DESIGN.md states (score-first matcher, not the tool's Hungarian default).
+ * ococc_frame_match_workspace_bytes: the overlap matrix of `num_pairs` pairs (pure host arithmetic).
+ * ------------------------------------------------------------------------ */
+int64_t ococc_frame_match_workspace_bytes(int64_t num_pairs);
+/* replaces the same stage of compute_detection_metrics_main (see above): two launches per call, whatever the number
+ *   of frames.
+ * pd_boxes [P, 7] f32 (centre x, y, z, length, width, height, heading) grouped by frame and, inside a frame, sorted by
+ * (type, descending score, file order); pd_type / pd_eligible [P] i32; pd_offsets [F+1] i32.  gt_* the same for the G
+ * ground-truth boxes, grouped by frame in file order.  pair_offsets [F+1] i64: the running sum of n_pd(f) * n_gt(f).
+ * The call handles the frames [frame_begin, frame_end), whose pairs are [pair_begin, pair_end) =
+ * pair_offsets[frame_begin], pair_offsets[frame_end] (host copies); max_frame_gt: the largest n_gt among them
+ * (<= 4096).  host_iou_thresh[5]: threshold per type 0..4 (entry 0 unused; 1..4 in (0, 1]).
+ * match_gt [P] i32: the index into gt_boxes of the box the prediction took, or -1; match_iou [P] f32: its IoU, or 0.
+ * Written for the predictions of the frames of the call only.  A prediction takes the not-yet-taken eligible
+ * ground-truth box of its type with the largest IoU >= threshold (equal IoU: the lower index); ineligible, degenerate
+ * (extent <= 0, non-finite) and unknown-type boxes never match.  No atomics: the same input gives the same bytes. */
+int ococc_frame_match_f32(const float* pd_boxes, const int32_t* pd_type, const int32_t* pd_eligible,
+                          const int32_t* pd_offsets, int64_t num_pd, const float* gt_boxes, const int32_t* gt_type,
+                          const int32_t* gt_eligible, const int32_t* gt_offsets, int64_t num_gt,
+                          const int64_t* pair_offsets, int32_t frame_begin, int32_t frame_end, int64_t pair_begin,
+                          int64_t pair_end, int32_t max_frame_gt, const float host_iou_thresh[5], int32_t* match_gt,
+                          float* match_iou, void* workspace, int64_t workspace_bytes, ococc_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * occupancy IoU counts of one chunk of RoIs, replacing the ATen chain of TrackletRoIHeadOCC.test_occ
  *   (mmdet3d/models/roi_heads/tracklet_roi_head_occ.py:394-486: repeat, inside-box test, *, ==, &, |, two sums).
  * logits [n, K] f32 (decoder output, cls_dim 1); labels [K] int64 (occupied: == 1);

@@ -12,7 +12,9 @@ Apache 2.0) is absent from this image, so the messages are encoded and decoded h
   metrics.Objects { repeated Object objects = 1; }
   metrics.Object  { Label object = 1; float score = 2; bool overlap_with_nlz = 3; string context_name = 4;
                     int64 frame_timestamp_micros = 5; }
-  label.Label     { Box box = 1; Metadata metadata = 2; Type type = 3; string id = 4; ...
+  label.Label     { Box box = 1; Metadata metadata = 2; Type type = 3; string id = 4;
+                    DifficultyLevel detection_difficulty_level = 5 (UNKNOWN = 0, LEVEL_1 = 1, LEVEL_2 = 2); ...
+                    int32 num_lidar_points_in_box = 7; ...
                     enum Type { TYPE_UNKNOWN = 0; TYPE_VEHICLE = 1; TYPE_PEDESTRIAN = 2; TYPE_SIGN = 3; TYPE_CYCLIST = 4; } }
   label.Label.Box { double center_x = 1; center_y = 2; center_z = 3; width = 4; length = 5; height = 6; heading = 7; }
 
@@ -21,7 +23,8 @@ pinned to the protobuf LIBRARY for exactly this schema (tests/test_waymo_io_cpu.
 google.protobuf's descriptor pool and compares bytes), the box / heading arithmetic to the reference's call sites.
 The metrics binary (mmdet3d/core/evaluation/waymo_utils/compute_detection_metrics_main, a compiled Waymo tool the
 reference ships no source for) is not built: `evaluate` writes the .bin and stops there with a clear error unless the
-caller names an executable."""
+caller names an executable.  The same table computed here, on HIP kernels and with a stated protocol of its own: waymo_metrics.py
+(metric 'waymo_native'; tools/waymo_detection_metrics.py has the tool's argv shape and can be that executable)."""
 import os
 import struct
 import subprocess
@@ -99,10 +102,14 @@ def _fields(buf):
 
 
 # ------------------------------------------------------------------------------------------------ writer
-def lidar2waymo_box(in_box, score, waymo_type, context_name, timestamp, object_id=None):
+def lidar2waymo_box(in_box, score, waymo_type, context_name, timestamp, object_id=None, overlap_with_nlz=None,
+                    detection_difficulty_level=None, num_lidar_points_in_box=None):
     """One box [7] (x, y, z_bottom, w, l, h, yaw; LiDAR box convention of the reference) -> the serialised
     metrics.Object, following waymo_tracklet_dataset.py:455-484 number for number (including its 3.1415926 / 3.141593 /
-    3.141592 constants)."""
+    3.141592 constants).  The three optional fields (Object.overlap_with_nlz = 3, Label.detection_difficulty_level = 5,
+    Label.num_lidar_points_in_box = 7: what a ground-truth file carries for waymo_metrics) are written in field-number
+    order whenever given (proto2 presence: an explicit 0 / False is on the wire, as the protobuf library writes a set
+    optional field); left out, the bytes are the reference's."""
     b = [float(v) for v in in_box]
     height = b[5]
     heading = -b[6] - 0.5 * 3.1415926
@@ -115,21 +122,31 @@ def lidar2waymo_box(in_box, score, waymo_type, context_name, timestamp, object_i
     label = _f_bytes(1, box) + _f_varint(3, waymo_type)
     if object_id is not None:
         label += _f_bytes(4, str(object_id).encode())
-    return (_f_bytes(1, label) + _f_float(2, score) + _f_bytes(4, str(context_name).encode()) +
+    if detection_difficulty_level is not None:
+        label += _f_varint(5, int(detection_difficulty_level))
+    if num_lidar_points_in_box is not None:
+        label += _f_varint(7, int(num_lidar_points_in_box))
+    nlz = b'' if overlap_with_nlz is None else _f_varint(3, bool(overlap_with_nlz))
+    return (_f_bytes(1, label) + _f_float(2, score) + nlz + _f_bytes(4, str(context_name).encode()) +
             _f_varint(5, int(timestamp)))
 
 
-def convert_tracklet_to_waymo(tracklets, pkl_path, classes=('Car', 'Pedestrian', 'Cyclist')):
+def convert_tracklet_to_waymo(tracklets, pkl_path, classes=('Car', 'Pedestrian', 'Cyclist'), overlap_with_nlz=None,
+                              detection_difficulty_level=None, num_lidar_points_in_box=None):
     """tracklets (tracklet.Tracklet with ``type`` = index into ``classes``, string ``id``, ``segment_name``) -> the
-    metrics.Objects file ``pkl_path`` (+ '.bin'), waymo_tracklet_dataset.py:430-453.  Returns the path written."""
+    metrics.Objects file ``pkl_path`` (+ '.bin'), waymo_tracklet_dataset.py:430-453.  Returns the path written.
+    The three optional arguments (see lidar2waymo_box) are one sequence per tracklet with one value per box, or None."""
+    per_box = lambda seq, k, i: None if seq is None else seq[k][i]
     chunks = []
-    for trk in tracklets:
+    for k, trk in enumerate(tracklets):
         assert isinstance(trk.id, str)
         wtype = K2W_CLS_MAP[classes[trk.type]]
         boxes = trk.boxes.detach().cpu().numpy()
         scores = trk.scores.detach().cpu().numpy()
         for i in range(len(trk)):
-            chunks.append(_f_bytes(1, lidar2waymo_box(boxes[i], scores[i], wtype, trk.segment_name, trk.ts_list[i], trk.id)))
+            chunks.append(_f_bytes(1, lidar2waymo_box(
+                boxes[i], scores[i], wtype, trk.segment_name, trk.ts_list[i], trk.id, per_box(overlap_with_nlz, k, i),
+                per_box(detection_difficulty_level, k, i), per_box(num_lidar_points_in_box, k, i))))
     if not pkl_path.endswith('.bin'):
         pkl_path += '.bin'
     with open(pkl_path, 'wb') as f:
@@ -139,7 +156,8 @@ def convert_tracklet_to_waymo(tracklets, pkl_path, classes=('Car', 'Pedestrian',
 
 # ------------------------------------------------------------------------------------------------ reader
 def read_bin(file_path):
-    """tools/ctrl/utils.py:12-16 -> list of dicts (box fields, type, id, score, context_name, frame_timestamp_micros)"""
+    """tools/ctrl/utils.py:12-16 -> list of dicts (box fields, type, id, score, context_name, frame_timestamp_micros,
+    and overlap_with_nlz / detection_difficulty_level / num_lidar_points_in_box, False / 0 / 0 where absent)"""
     with open(file_path, 'rb') as f:
         buf = f.read()
     out = []
@@ -147,7 +165,8 @@ def read_bin(file_path):
         if field != 1 or wire != 2:
             continue
         rec = dict(score=0.0, context_name='', frame_timestamp_micros=0, type=0, id='', center_x=0.0, center_y=0.0,
-                   center_z=0.0, width=0.0, length=0.0, height=0.0, heading=0.0)
+                   center_z=0.0, width=0.0, length=0.0, height=0.0, heading=0.0, overlap_with_nlz=False,
+                   detection_difficulty_level=0, num_lidar_points_in_box=0)
         for f2, w2, v2 in _fields(obj):
             if f2 == 1 and w2 == 2:
                 for f3, w3, v3 in _fields(v2):
@@ -160,8 +179,14 @@ def read_bin(file_path):
                         rec['type'] = v3
                     elif f3 == 4 and w3 == 2:
                         rec['id'] = v3.decode()
+                    elif f3 == 5 and w3 == 0:
+                        rec['detection_difficulty_level'] = v3
+                    elif f3 == 7 and w3 == 0:
+                        rec['num_lidar_points_in_box'] = (v3 & 0xffffffff) - (1 << 32) if v3 & 0x80000000 else v3 & 0xffffffff
             elif f2 == 2 and w2 == 5:
                 rec['score'] = struct.unpack('<f', v2)[0]
+            elif f2 == 3 and w2 == 0:
+                rec['overlap_with_nlz'] = bool(v2)
             elif f2 == 4 and w2 == 2:
                 rec['context_name'] = v2.decode()
             elif f2 == 5 and w2 == 0:

@@ -1,7 +1,9 @@
 """Write a small synthetic tracklet dataset in the reference's on-disk formats (what WaymoTrackletDatasetWithOcc
 reads, mmdet3d/datasets/waymo_tracklet_dataset.py:491-584): <root>/tracklet_data/synth_training.pkl (proposals),
 synth_training_gt_candidates.pkl, synth_training_database/<segment>--<id>.npy (per-frame [n,6] points),
-<root>/poses.pkl, <root>/occ_gt/<segment>/<id>.npz (key 'occ', X x Y x Z in {0,1,2}).
+<root>/poses.pkl, <root>/occ_gt/<segment>/<id>.npz (key 'occ', X x Y x Z in {0,1,2}), and the detection ground truth
+<root>/waymo_format/gt.bin (metrics.Objects with lidar point counts and difficulty levels, so that LEVEL_1, LEVEL_2 and
+ignored objects all occur: what dataset.evaluate(metric='waymo_native') scores against).
 
 usage: python tools/make_synthetic_dataset.py <root> [--tracklets 6] [--frames 40]"""
 import argparse
@@ -19,6 +21,23 @@ def rot_z(a):
     return np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
 
 
+def write_gt_bin(waymo_dir, gt_tracklets):
+    """<waymo_dir>/gt.bin from (segment, id, boxes [n, 7] LiDAR convention, timestamps, points per box).  No random draw:
+    every tenth frame of an object is made LEVEL_2 by its difficulty level (frame 5, 15, ...), LEVEL_2 by a count of 3
+    points (7, 17, ...) or ignored by a count of 0 (9, 19, ...); the other frames keep their point count (LEVEL_1)."""
+    import torch
+    from objectcentricocccompletion_amd import waymo_io
+    from objectcentricocccompletion_amd.tracklet import Tracklet
+    os.makedirs(waymo_dir, exist_ok=True)
+    trks, points, levels = [], [], []
+    for seg, tid, boxes, ts, num_pts in gt_tracklets:
+        trks.append(Tracklet(torch.from_numpy(np.asarray(boxes, np.float32)), list(ts), torch.ones(len(ts)), 0, seg, tid))
+        points.append([3 if f % 10 == 7 else 0 if f % 10 == 9 else int(n) for f, n in enumerate(num_pts)])
+        levels.append([2 if f % 10 == 5 else 1 for f in range(len(ts))])
+    return waymo_io.convert_tracklet_to_waymo(trks, os.path.join(waymo_dir, 'gt.bin'), ('Car', 'Pedestrian', 'Cyclist'),
+                                              None, levels, points)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('root')
@@ -30,7 +49,7 @@ def main(argv=None):
     tdir = os.path.join(a.root, 'tracklet_data')
     db = os.path.join(tdir, 'synth_training_database')
     os.makedirs(db, exist_ok=True)
-    proposals, candidates, poses = [], [], {}
+    proposals, candidates, poses, gt_tracklets = [], [], {}, []
     for t in range(a.tracklets):
         seg, tid = f'segment-{t // 3:03d}', f'obj{t:03d}'
         ts = [1_000_000 * (t + 1) + 100_000 * f for f in range(a.frames)]
@@ -56,6 +75,7 @@ def main(argv=None):
         proposals.append((seg, tid, 1, False, [b[None] for b in boxes], ts, rng.uniform(0.3, 1.0, a.frames).tolist(), num_pts))
         candidates.append([(seg, tid + '_far', 1, False, [b[None] for b in far], ts, [1.0] * a.frames, num_pts),
                            (seg, tid + '_gt', 1, False, [b[None] for b in gt], ts, [1.0] * a.frames, num_pts)])
+        gt_tracklets.append((seg, tid + '_gt', np.stack(gt), ts, num_pts))
         arr = np.empty(len(pts), dtype=object)
         for i, p in enumerate(pts):
             arr[i] = p
@@ -71,6 +91,7 @@ def main(argv=None):
         pickle.dump(candidates, f)
     with open(os.path.join(a.root, 'poses.pkl'), 'wb') as f:
         pickle.dump(poses, f)
+    write_gt_bin(os.path.join(a.root, 'waymo_format'), gt_tracklets)
     print('wrote', a.tracklets, 'tracklets x', a.frames, 'frames under', a.root)
 
 

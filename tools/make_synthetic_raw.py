@@ -3,6 +3,8 @@ tools/ctrl/generate_candidates.py), so that the chain raw -> track input -> cand
 runs without Waymo data:
 
     <out>/waymo_format/pred.bin, train_gt.bin      tracking result and ground truth (waymo_io's own writer)
+    <out>/waymo_format/gt.bin                      the same ground truth with lidar point counts and difficulty levels
+                                                   (LEVEL_1, LEVEL_2 and ignored objects: tools/waymo_detection_metrics.py)
     <out>/kitti_format/idx2timestamp.pkl, idx2contextname.pkl, training/velodyne/<idx>.bin   ([n, 6] float32 clouds)
     <out>/synthetic_vehicle.yaml                   tools/ctrl/data_configs/synthetic_vehicle.yaml with this tree's paths
     <out>/poses.pkl, <out>/occ_gt/<segment>/<gt id>.npz    what the dataset class needs besides (as make_synthetic_dataset.py)
@@ -45,7 +47,7 @@ def main(argv=None):
     velo = os.path.join(out, 'kitti_format', 'training', 'velodyne')
     for d in (velo, os.path.join(out, 'waymo_format'), os.path.join(out, 'tracklet_data')):
         os.makedirs(d, exist_ok=True)
-    idx2ts, idx2seg, poses, preds, gts = {}, {}, {}, [], []
+    idx2ts, idx2seg, poses, preds, gts, gt_points, gt_levels = {}, {}, {}, [], [], [], []
     for s in range(a.segments):
         seg = f'segment-{s:03d}'
         ts = [10_000_000 * (s + 1) + 100_000 * f for f in range(a.frames)]
@@ -59,12 +61,13 @@ def main(argv=None):
         for t in range(a.tracklets):
             size = np.array([rng.uniform(1.7, 2.2), rng.uniform(4.0, 5.2), rng.uniform(1.4, 1.9)])
             first = int(rng.integers(0, 4)) if t else 0       # objects appear at different frames
-            boxes = []
+            boxes, counts = [], []
             for f in range(first, a.frames):
                 yaw = 0.02 * f + rng.normal(0, 0.01) + 0.7 * t
                 ctr = np.array([12 + 0.3 * f, -14 + 12 * t + 0.1 * f, 0.1])    # in that frame's ego coordinates
                 boxes.append(np.concatenate([ctr, size, [yaw]]))
                 n = int(rng.integers(150, 400))
+                counts.append(n)
                 local = (rng.random((n, 3)) - 0.5) * size
                 # (box convention of the kernels: w along x at yaw 0, turned CLOCKWISE by yaw, as make_synthetic_dataset.py)
                 clouds[f].append(local @ rot_z(yaw).T + ctr + [0, 0, size[2] / 2])
@@ -72,6 +75,9 @@ def main(argv=None):
             pd = (gt + rng.normal(0, [0.05, 0.05, 0.02, 0.02, 0.02, 0.02, 0.01], gt.shape)).astype(np.float32)
             stamps = ts[first:]
             gts.append(Tracklet(torch.from_numpy(gt), stamps, None, 0, seg, f'gt{s}_{t:02d}'))
+            # gt.bin only: every tenth frame LEVEL_2 by difficulty, LEVEL_2 by 3 points, ignored by 0 points
+            gt_points.append([3 if f % 10 == 7 else 0 if f % 10 == 9 else c for f, c in enumerate(counts)])
+            gt_levels.append([2 if f % 10 == 5 else 1 for f in range(len(counts))])
             preds.append(Tracklet(torch.from_numpy(pd), stamps, torch.from_numpy(rng.uniform(0.3, 1.0, len(pd)).astype(np.float32)),
                                   0, seg, f'trk{s}_{t:02d}'))
             dims = np.ceil(size / 0.2).astype(int)
@@ -87,6 +93,8 @@ def main(argv=None):
             np.concatenate([xyz, attrs(len(xyz))], 1).astype(np.float32).tofile(os.path.join(velo, idx + '.bin'))
     waymo_io.convert_tracklet_to_waymo(preds, os.path.join(out, 'waymo_format', 'pred.bin'))
     waymo_io.convert_tracklet_to_waymo(gts, os.path.join(out, 'waymo_format', 'train_gt.bin'))
+    waymo_io.convert_tracklet_to_waymo(gts, os.path.join(out, 'waymo_format', 'gt.bin'), detection_difficulty_level=gt_levels,
+                                       num_lidar_points_in_box=gt_points)
     for name, obj in (('idx2timestamp.pkl', idx2ts), ('idx2contextname.pkl', idx2seg)):
         with open(os.path.join(out, 'kitti_format', name), 'wb') as f:
             pickle.dump(obj, f)

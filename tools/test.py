@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Test / evaluation entry point with the CLI of the reference's tools/test.py (:23-87):
-    python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--eval iou waymo] [--format-only]
+    python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--eval iou waymo waymo_native] [--format-only]
                          [--eval-options k=v ...] [--cfg-options k=v ...] [--launcher {none,pytorch}]
                          [--tmpdir DIR] [--gpu-collect] [--local_rank N]
 The test dataset is the config's data.test (the reference's data/waymo layout); with --data-root DIR it reads the tree
@@ -28,7 +28,7 @@ import warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-METRICS = ('iou', 'waymo')
+METRICS = ('iou', 'waymo', 'waymo_native')
 
 
 def parse_args(argv=None):
@@ -38,7 +38,8 @@ def parse_args(argv=None):
     ap.add_argument('--out', help='output result file in pickle format: one result per tracklet, in dataset order')
     ap.add_argument('--fuse-conv-bn', action='store_true', help='ignored: the model has no conv + BN pair')
     ap.add_argument('--format-only', action='store_true', help='write the Waymo result file without evaluating it')
-    ap.add_argument('--eval', type=str, nargs='+', choices=METRICS, help='metrics: iou (occupancy), waymo (detection)')
+    ap.add_argument('--eval', type=str, nargs='+', choices=METRICS, help='metrics: iou (occupancy), waymo (detection, needs the Waymo tool), waymo_native (detection, '
+                    'HIP matching kernels: objectcentricocccompletion_amd/waymo_metrics.py)')
     ap.add_argument('--show', action='store_true', help='ignored: no visualisation here')
     ap.add_argument('--show-dir', help='ignored: no visualisation here')
     ap.add_argument('--gpu-collect', action='store_true', help='collect the ranks\' results by an all-gather')

@@ -585,6 +585,42 @@ int ococc_tracklet_crop_fill(const float* points, int64_t num_points, int32_t po
                              int64_t max_frame_points, const int64_t* scan, const void* workspace,
                              int64_t workspace_bytes, int64_t* out_index, ococc_stream_t stream);
 
+/* Which boxes hold at least one point of their frame: the third mode of the same kernel
+ * replaces the per-box loop of tools/ctrl/remove_empty.py:115-134 (group_size 1: box upload, points_in_boxes over the
+ *   whole cloud, torch.unique and a device-to-host copy, each per box) by one launch per batch of frames.
+ * Arguments as ococc_tracklet_crop_count (the bottom lift of remove_empty is applied to the boxes by the caller);
+ * no workspace.  flags [B] i32: 1 where ococc_tracklet_crop_count would count at least one point (the same
+ * arithmetic, bit for bit), else 0.  The call zero-fills flags; plain stores of 1, no atomics. */
+int ococc_tracklet_nonempty(const float* points, int64_t num_points, int32_t point_dim, const int64_t* point_offsets,
+                            const float* boxes, int64_t num_boxes, const int64_t* box_offsets, int32_t frames,
+                            int64_t max_frame_points, int32_t* flags, ococc_stream_t stream);
+
+/* Track extension by a constant-velocity model, all tracklets of a call in one launch
+ * replaces the per-tracklet loop of tools/ctrl/extend_tracks.py:156-190 over LiDARTracklet.frame_transform,
+ *   set_velocity, extend / extend_all and shared2ego (mmdet3d/core/bbox/structures/lidar_tracklet.py:345-387, 452-498,
+ *   638-652, 669-791): a dozen small torch operators and a 4x4 inverse per tracklet.
+ * boxes [num_boxes, 7] f32 (x, y, z_bottom, w, l, h, yaw) of the tracklets back to back, each in its frame's ego frame;
+ * offsets [num_tracklets+1] i32; frames [num_boxes] i32: index of the box's timestamp in its SEGMENT's sorted
+ * timestamp list, strictly increasing within a tracklet; segments [num_tracklets] i32; scores [num_boxes] f64.
+ * poses [num_frames, 16] f32 (ego -> world, row major) and timestamps [num_frames] i64 (microseconds) of all segments
+ * back to back, seg_offsets [num_segments+1] i32.
+ * The plan is the host's (integer arithmetic on timestamps): num_back / num_fwd [num_tracklets] i32, the frames added
+ * in front of the first and behind the last observed box (the frames frames[first] - num_back ... and
+ * frames[last] + 1 ...), and out_offsets [num_tracklets+1] i32 with out_offsets[t+1] - out_offsets[t] =
+ * num_back[t] + length(t) + num_fwd[t], out_offsets[num_tracklets] = num_out.  A tracklet whose plan leaves its
+ * segment's frame table or the output is skipped.
+ * out_boxes [num_out, 7] f32 in each output frame's own ego frame, out_scores [num_out] f64, out_frames [num_out] i32;
+ * per tracklet: the added frames in front in ascending time (score s_first * m^(i+1), i counted from the EARLIEST),
+ * the observed boxes (through the shared frame and back), the added frames behind (s_last * m^(i+1) outward).
+ * float64 inside, one rounding to float32 on store; every output word has one writer. */
+int ococc_track_extend_f64(const float* boxes, const int32_t* offsets, const int32_t* frames, const int32_t* segments,
+                           const double* scores, int32_t num_tracklets, int64_t num_boxes, const float* poses,
+                           const int64_t* timestamps, const int32_t* seg_offsets, int32_t num_segments,
+                           int64_t num_frames, const int32_t* num_back, const int32_t* num_fwd,
+                           const int32_t* out_offsets, int64_t num_out, double score_multiplier,
+                           int32_t velo_window_size, float* out_boxes, double* out_scores, int32_t* out_frames,
+                           ococc_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * Detection matching of the native Waymo metric: per frame, the full 3-D IoU of every (prediction, ground truth)
  * pair of equal type and the score-first greedy assignment

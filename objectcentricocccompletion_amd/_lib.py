@@ -113,6 +113,9 @@ SIGNATURES = {
     'ococc_tracklet_crop_count': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
     'ococc_tracklet_crop_fill': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp,
                                          c_vp]),
+    'ococc_tracklet_nonempty': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp]),
+    'ococc_track_extend_f64': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp,
+                                       c_vp, c_i64, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'ococc_frame_match_workspace_bytes': (c_i64, [c_i64]),
     'ococc_frame_match_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32,
                                       c_i64, c_i64, c_i32, ctypes.c_float * 5, c_vp, c_vp, c_vp, c_i64, c_vp]),

@@ -20,6 +20,12 @@
 // at C = 6), B * 28 B of boxes per workgroup (L2);  count: + T * B * 4 B workspace out, B * 8 B counts;
 // fill: + about T/2 * B * 4 B workspace in per wave tile (L2) and sum(counts) * 8 B of indices out.
 // T = wave tiles of the largest frame.  Vector stores only.
+//
+// Third mode, non-empty flags (tools/ctrl/remove_empty.py:115-134 with group_size 1: one upload, one points_in_boxes
+// launch, one torch.unique and one read-back per box): the same membership test, but per box and round the ballot is
+// only tested against zero, the rounds of a box stop at its first hit, and one lane stores 1 into flags [B] i32
+// (zero-filled by the caller side of the export; a plain store of the same value from every wave tile that hits).
+// No workspace, no second pass.  Algorithmic bytes: N * 12 B of xyz in, B * 4 B out.
 #include "common.hpp"
 
 namespace {
@@ -30,7 +36,10 @@ constexpr int kWaves = 4;
 constexpr int kBlockTile = kWaveTile * kWaves;
 constexpr int kChunk = 64;                  // boxes staged at a time: one per lane
 
-template <bool FILL>
+enum CropMode { kCount = 0, kFill = 1, kFlag = 2 };
+
+// tile_counts: the workspace of kCount / kFill; the flags [B] of kFlag
+template <int MODE>
 __global__ void __launch_bounds__(64 * kWaves)
 tracklet_crop_kernel(const float* __restrict__ points, int32_t C, const int64_t* __restrict__ point_offsets,
                      const float* __restrict__ boxes, const int64_t* __restrict__ box_offsets, int64_t B,
@@ -74,6 +83,7 @@ tracklet_crop_kernel(const float* __restrict__ points, int32_t C, const int64_t*
     }
     __syncthreads();
 
+    constexpr bool FILL = MODE == kFill;
     int64_t base = 0, end = 0;   // lane j: where box c0 + j's points of this wave tile start / the box's end
     if (FILL) {
       if (lane < cn) {
@@ -97,6 +107,13 @@ tracklet_crop_kernel(const float* __restrict__ points, int32_t C, const int64_t*
           in = (lx > -hl) & (lx < hl) & (ly > -hw) & (ly < hw);
         }
         const unsigned long long bal = __ballot(in);
+        if (MODE == kFlag) {
+          if (bal) {
+            cnt = 1;
+            break;
+          }
+          continue;
+        }
         if (FILL && in) {
           const int64_t pos = base_j + cnt + __popcll(bal & ((1ull << lane) - 1ull));
           if (pos < end_j) out_index[pos] = w0 + r * 64 + lane;   // (pos < end_j: counts and scan of the same input)
@@ -105,7 +122,9 @@ tracklet_crop_kernel(const float* __restrict__ points, int32_t C, const int64_t*
       }
       if (lane == j) mine = cnt;
     }
-    if (!FILL && lane < cn) {
+    if (MODE == kFlag) {
+      if (lane < cn && mine) tile_counts[b0 + c0 + lane] = 1;
+    } else if (!FILL && lane < cn) {
       const int64_t b = b0 + c0 + lane;
       tile_counts[wt * B + b] = mine;   // zeros too: the fill pass reads every earlier wave tile of the frame
       if (mine) atomicAdd(&counts[b], (unsigned long long)mine);
@@ -115,14 +134,15 @@ tracklet_crop_kernel(const float* __restrict__ points, int32_t C, const int64_t*
 
 int crop_check(const float* points, int64_t n, int32_t c, const int64_t* point_offsets, const float* boxes, int64_t b,
                const int64_t* box_offsets, int32_t frames, int64_t max_frame_points, const void* workspace,
-               int64_t workspace_bytes, const char* fn) {
+               int64_t workspace_bytes, const char* fn, bool needs_workspace = true) {
   if (n < 0 || b < 0 || frames < 0 || max_frame_points < 0 || max_frame_points > n)
     return ococc_fail(OCOCC_EINVAL, fn, "negative size, or max_frame_points > num_points");
   if (c < 3) return ococc_fail(OCOCC_EINVAL, fn, "points need at least 3 columns");
   if (frames > 65535) return ococc_fail(OCOCC_EINVAL, fn, "at most 65535 frames per call");
   if (b == 0 || n == 0 || frames == 0) return 1;
-  if (!points || !point_offsets || !boxes || !box_offsets || !workspace)
+  if (!points || !point_offsets || !boxes || !box_offsets || (needs_workspace && !workspace))
     return ococc_fail(OCOCC_EINVAL, fn, "null pointer");
+  if (!needs_workspace) return OCOCC_OK;
   const int64_t tiles = ococc_cdiv(max_frame_points, kBlockTile) * kWaves;
   if (workspace_bytes < tiles * b * (int64_t)sizeof(int32_t))
     return ococc_fail(OCOCC_EINVAL, fn, "workspace too small: ceil(max_frame_points / 4096) * 4 * num_boxes * 4 bytes");
@@ -146,7 +166,7 @@ extern "C" int ococc_tracklet_crop_count(const float* points, int64_t num_points
   }
   if (rc == 1 || max_frame_points == 0) return OCOCC_OK;
   const dim3 grid((unsigned)ococc_cdiv(max_frame_points, kBlockTile), (unsigned)frames);
-  hipLaunchKernelGGL(tracklet_crop_kernel<false>, grid, dim3(64 * kWaves), 0, stream, points, point_dim, point_offsets,
+  hipLaunchKernelGGL(tracklet_crop_kernel<kCount>, grid, dim3(64 * kWaves), 0, stream, points, point_dim, point_offsets,
                      boxes, box_offsets, num_boxes, (int32_t*)workspace, (unsigned long long*)counts,
                      (const int64_t*)nullptr, (int64_t*)nullptr);
   OCOCC_CHECK_LAUNCH();
@@ -164,9 +184,30 @@ extern "C" int ococc_tracklet_crop_fill(const float* points, int64_t num_points,
   if (rc == 1 || max_frame_points == 0) return OCOCC_OK;
   OCOCC_REQUIRE(scan && out_index, "null scan or out_index");
   const dim3 grid((unsigned)ococc_cdiv(max_frame_points, kBlockTile), (unsigned)frames);
-  hipLaunchKernelGGL(tracklet_crop_kernel<true>, grid, dim3(64 * kWaves), 0, (hipStream_t)stream_, points, point_dim,
+  hipLaunchKernelGGL(tracklet_crop_kernel<kFill>, grid, dim3(64 * kWaves), 0, (hipStream_t)stream_, points, point_dim,
                      point_offsets, boxes, box_offsets, num_boxes, (int32_t*)const_cast<void*>(workspace),
                      (unsigned long long*)nullptr, scan, out_index);
+  OCOCC_CHECK_LAUNCH();
+  return OCOCC_OK;
+}
+
+extern "C" int ococc_tracklet_nonempty(const float* points, int64_t num_points, int32_t point_dim,
+                                       const int64_t* point_offsets, const float* boxes, int64_t num_boxes,
+                                       const int64_t* box_offsets, int32_t frames, int64_t max_frame_points,
+                                       int32_t* flags, ococc_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const int rc = crop_check(points, num_points, point_dim, point_offsets, boxes, num_boxes, box_offsets, frames,
+                            max_frame_points, nullptr, 0, __func__, false);
+  if (rc < 0) return rc;
+  if (num_boxes > 0) {
+    OCOCC_REQUIRE(flags, "null flags");
+    OCOCC_HIP(hipMemsetAsync(flags, 0, num_boxes * sizeof(int32_t), stream));
+  }
+  if (rc == 1 || max_frame_points == 0) return OCOCC_OK;
+  const dim3 grid((unsigned)ococc_cdiv(max_frame_points, kBlockTile), (unsigned)frames);
+  hipLaunchKernelGGL(tracklet_crop_kernel<kFlag>, grid, dim3(64 * kWaves), 0, stream, points, point_dim, point_offsets,
+                     boxes, box_offsets, num_boxes, flags, (unsigned long long*)nullptr, (const int64_t*)nullptr,
+                     (int64_t*)nullptr);
   OCOCC_CHECK_LAUNCH();
   return OCOCC_OK;
 }

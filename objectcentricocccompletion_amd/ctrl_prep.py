@@ -10,7 +10,13 @@ The two hot paths are HIP kernels (csrc/tracklet_crop.hip, csrc/tracklet_iou.hip
 points_in_boxes launch, one mask compaction and one device-to-host copy PER BOX of every frame
 (generate_track_input.py:84-99) and scores with one upload, launch and ``.item()`` PER PAIR of tracklets
 (generate_candidates.py:61-65, lidar_tracklet.py:210-229); here a batch of frames is one count launch, one read-back and
-one fill launch, a segment's P x G affinity matrix one launch and one read-back."""
+one fill launch, a segment's P x G affinity matrix one launch and one read-back.
+
+Two more tools of the same family run between the tracker and step 4 (and again on the refined result):
+tools/ctrl/extend_tracks.py (extend_tracks: every tracklet extended backward in time by a constant-velocity model, all
+tracklets of a file in one launch of csrc/track_extend.hip, the plan made on the host) and tools/ctrl/remove_empty.py
+(remove_empty: boxes without a lidar point dropped; the non-empty mode of csrc/tracklet_crop.hip, one launch and one
+read-back per batch of frames where the reference has them per box)."""
 import os
 import os.path as osp
 import pickle
@@ -404,3 +410,319 @@ def generate_candidates(config, gt_bin_path='./data/waymo/waymo_format/train_gt.
     with open(paths['candidates'], 'wb') as fw:
         pickle.dump(out, fw)
     return paths['candidates']
+
+
+# ------------------------------------------------------------------------------------------------ track extension
+MAX_FIRST_GAP_MICROS = 500_000    # extend / extend_all give up when the first two boxes are further apart than this
+EXTEND_KEYS = ('bin_path', 'direction', 'extend_length', 'min_length_to_extend', 'score_multiplier', 'velo_window_size')
+
+
+def load_extend_config(config):
+    """a YAML file of the reference's tools/ctrl/data_configs/extend.yaml shape (or the mapping itself, with key
+    ``name``) -> (mapping, config name).  Optional keys: extend_all, min_length_to_extend_all, mm_data_root,
+    poses_path (default <mm_data_root>/poses.pkl)."""
+    if isinstance(config, (str, os.PathLike)):
+        import yaml
+        with open(config, 'r') as f:
+            cfg = yaml.safe_load(f)
+        name = osp.basename(str(config)).split('.')[0]
+    else:
+        cfg = dict(config)
+        name = cfg.get('name')
+        if not name:
+            raise KeyError("a config given as a mapping needs a 'name' (the YAML file's base name)")
+    missing = [k for k in EXTEND_KEYS if k not in cfg]
+    if missing:
+        raise KeyError(f'extend config misses {missing}')
+    if cfg['direction'] not in ('forward', 'backward'):
+        raise ValueError(f"direction must be 'forward' or 'backward', got {cfg['direction']!r}")
+    if cfg['direction'] == 'forward':
+        raise NotImplementedError('direction: forward (LiDARTracklet.extend raises for it too; the tracker extends forward)')
+    if cfg.get('extend_all', False) and 'min_length_to_extend_all' not in cfg:
+        raise KeyError('extend_all needs min_length_to_extend_all')
+    if int(cfg['extend_length']) < 0 or int(cfg['velo_window_size']) < 1:
+        raise ValueError('extend_length must not be negative and velo_window_size at least 1')
+    return cfg, name
+
+
+def plan_extension(offsets, frames, segments, seg_ts, extend_length, min_length, extend_all=False, min_length_all=0,
+                   direction='backward'):
+    """Who is extended and by how much -- the integer part of LiDARTracklet.extend / extend_all and of the choice
+    between them (tools/ctrl/extend_tracks.py:171-188), on the host.  offsets [n + 1], frames [sum L] (index of every
+    box in its segment's sorted timestamps), segments [n], seg_ts: per segment its sorted timestamps (microseconds)
+    -> (num_back [n], num_fwd [n], out_offsets [n + 1]) int32 arrays.
+
+    extend_all is taken when set and L > min_length_all, else plain extend.  Not extended: fewer boxes than the
+    minimum length of the branch taken; a first gap ts[1] - ts[0] above 500 000 microseconds (for extend_all this
+    cancels the forward part too) -- the reference tests delta_t > 0.5 on float32 seconds, which for integer
+    microseconds is this integer test (0.5 is exact in float32 and rounding is monotone); a tracklet of ONE box, where
+    the reference would raise on ts_in_sec[1], is never extended.  backward: min(extend_length, first frame index)
+    frames; extend_all: every frame of the segment before the first and after the last box."""
+    if direction != 'backward':
+        raise NotImplementedError(f'direction {direction!r}: only backward extension exists (as upstream)')
+    offsets, frames, segments = (np.asarray(v, dtype=np.int64) for v in (offsets, frames, segments))
+    n = len(segments)
+    back, fwd = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    for t in range(n):
+        lo, hi = offsets[t], offsets[t + 1]
+        length, stamps = hi - lo, seg_ts[segments[t]]
+        use_all = bool(extend_all) and length > min_length_all
+        if length < (min_length_all if use_all else min_length) or length < 2:
+            continue
+        if stamps[frames[lo + 1]] - stamps[frames[lo]] > MAX_FIRST_GAP_MICROS:
+            continue
+        if use_all:
+            back[t], fwd[t] = frames[lo], len(stamps) - 1 - frames[hi - 1]
+        else:
+            back[t] = min(int(extend_length), frames[lo])
+    out_offsets = np.zeros(n + 1, np.int32)
+    np.cumsum(np.diff(offsets) + back + fwd, out=out_offsets[1:])
+    return back, fwd, out_offsets
+
+
+def extend_tracks_packed(boxes, offsets, frames, segments, scores, poses, timestamps, seg_offsets, num_back, num_fwd,
+                         out_offsets, score_multiplier, velo_window_size):
+    """The boxes of n tracklets back to back [sum L, 7] f32 (each in its frame's ego frame) with their scores [sum L]
+    f64, the poses [sum T, 16] f32 (ego -> world) and timestamps [sum T] int64 of all segments back to back, on the
+    device; offsets [n + 1], frames [sum L], segments [n], seg_offsets [S + 1] and the plan of plan_extension as HOST
+    integer sequences -> (boxes [sum L', 7] f32 in each output frame's own ego frame, scores [sum L'] f64, frame indices
+    [sum L'] i32) on the device.  One launch, no read-back between the plan and the launch."""
+    L.require_device(boxes, scores, poses, timestamps)
+    if boxes.dim() != 2 or boxes.size(1) < 7 or boxes.dtype != torch.float32:
+        raise L.OcoccError(f'boxes must be [N, >= 7] float32, got {tuple(boxes.shape)} {boxes.dtype}')
+    if scores.dtype != torch.float64 or scores.numel() != boxes.size(0):
+        raise L.OcoccError('extend_tracks: one float64 score per box')
+    if timestamps.dtype != torch.int64 or poses.dtype != torch.float32 or poses.numel() != timestamps.numel() * 16:
+        raise L.OcoccError('extend_tracks: poses [T, 16] float32 (or [T, 4, 4]) and timestamps [T] int64')
+    off, fr, seg, so, nb, nf, oo = (np.asarray(v, dtype=np.int64).reshape(-1) for v in
+                                   (offsets, frames, segments, seg_offsets, num_back, num_fwd, out_offsets))
+    n, total, num_frames = len(seg), boxes.size(0), timestamps.numel()
+    if len(off) != n + 1 or len(nb) != n or len(nf) != n or len(oo) != n + 1 or len(fr) != total or len(so) < 1:
+        raise L.OcoccError('extend_tracks: table lengths do not fit the number of tracklets / boxes')
+    lens = np.diff(off)
+    if off[0] != 0 or off[-1] != total or (lens < 1).any() or so[0] != 0 or so[-1] != num_frames or (np.diff(so) < 0).any() \
+            or oo[0] != 0 or (np.diff(oo) != lens + nb + nf).any() or (nb < 0).any() or (nf < 0).any() \
+            or (n and (seg.min() < 0 or seg.max() >= len(so) - 1)) or oo[-1] >= 2 ** 31:
+        raise L.OcoccError('extend_tracks: offsets must start at 0 and end at the row counts, every tracklet needs a box, '
+                           'and out_offsets must be the running sum of num_back + length + num_fwd')
+    if n:
+        frames_of = np.diff(so)[seg]
+        inner = np.ones(total, bool)
+        inner[off[:-1]] = False
+        if (fr < 0).any() or (fr >= np.repeat(frames_of, lens)).any() or (np.diff(fr, prepend=-1)[inner] <= 0).any():
+            raise L.OcoccError('extend_tracks: frame indices must lie in their segment and increase within a tracklet')
+        if (fr[off[:-1]] - nb < 0).any() or (fr[off[1:] - 1] + nf >= frames_of).any():
+            raise L.OcoccError('extend_tracks: the plan leaves the segment')
+    if not int(velo_window_size) >= 1:
+        raise L.OcoccError('extend_tracks: velo_window_size must be at least 1')
+    dev = boxes.device
+    num_out = int(oo[-1]) if n else 0
+    out_boxes = torch.empty((num_out, 7), dtype=torch.float32, device=dev)
+    out_scores = torch.empty((num_out,), dtype=torch.float64, device=dev)
+    out_frames = torch.empty((num_out,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return out_boxes, out_scores, out_frames
+    tables = [off, fr, seg, so, nb, nf, oo]
+    flat = torch.from_numpy(np.concatenate(tables).astype(np.int32)).to(dev)              # one upload
+    d_off, d_fr, d_seg, d_so, d_nb, d_nf, d_oo = flat.split([len(v) for v in tables])
+    boxes7 = boxes[:, :7].contiguous()
+    L.check(L.lib.ococc_track_extend_f64(L.ptr(boxes7), L.ptr(d_off), L.ptr(d_fr), L.ptr(d_seg), L.ptr(scores.contiguous()), n,
+                                         total, L.ptr(poses.contiguous()), L.ptr(timestamps.contiguous()), L.ptr(d_so),
+                                         len(so) - 1, num_frames, L.ptr(d_nb), L.ptr(d_nf), L.ptr(d_oo), num_out,
+                                         float(score_multiplier), int(velo_window_size), L.ptr(out_boxes), L.ptr(out_scores),
+                                         L.ptr(out_frames), L.stream()), 'track_extend')
+    return out_boxes, out_scores, out_frames
+
+
+def pack_for_extension(tracklets, seg_ts, ts2pose):
+    """host side of extend_tracks_packed: tracklets (ego-frame boxes, ``segment_name``) -> dict of CPU tensors / arrays
+    (boxes, scores, offsets, frames, segments, poses, timestamps, seg_offsets, names: the segments in table order)"""
+    names, seg_of, ts2frame_of = [], {}, {}
+    offsets, frames, segments = [0], [], []
+    for t in tracklets:
+        if t.segment_name not in seg_of:
+            if t.segment_name not in seg_ts:
+                raise KeyError(f'segment {t.segment_name!r} has no frames in idx2contextname.pkl')
+            seg_of[t.segment_name] = len(names)
+            names.append(t.segment_name)
+            ts2frame_of[t.segment_name] = {ts: i for i, ts in enumerate(seg_ts[t.segment_name])}
+        ts2frame = ts2frame_of[t.segment_name]
+        missing = [ts for ts in t.ts_list if ts not in ts2frame]
+        if missing:
+            raise KeyError(f'tracklet {t.id!r}: timestamp {missing[0]} is not a frame of {t.segment_name!r}')
+        frames += frame_indices(t.ts_list, ts2frame)
+        offsets.append(len(frames))
+        segments.append(seg_of[t.segment_name])
+    stamps = [ts for s in names for ts in seg_ts[s]]
+    lost = [ts for ts in stamps if ts not in ts2pose]
+    if lost:
+        raise KeyError(f'{len(lost)} frames have no pose in poses.pkl (e.g. {lost[0]})')
+    poses = np.stack([np.asarray(ts2pose[ts], dtype=np.float32).reshape(16) for ts in stamps], 0) if stamps else np.zeros((0, 16), np.float32)
+    boxes = torch.cat([t.boxes[:, :7].float() for t in tracklets], 0) if len(tracklets) else torch.zeros((0, 7))
+    scores = torch.cat([t.scores.double() for t in tracklets], 0) if len(tracklets) else torch.zeros((0,), dtype=torch.float64)
+    return dict(boxes=boxes, scores=scores, offsets=np.asarray(offsets), frames=np.asarray(frames, dtype=np.int64),
+                segments=np.asarray(segments, dtype=np.int64), poses=torch.from_numpy(poses),
+                timestamps=torch.tensor(stamps, dtype=torch.int64),
+                seg_offsets=np.concatenate([[0], np.cumsum([len(seg_ts[s]) for s in names])]).astype(np.int64), names=names)
+
+
+def extend_tracks(config, device=None):
+    """tools/ctrl/extend_tracks.py as a function: the tracker's result (.bin) -> every tracklet extended backward by a
+    constant-velocity model (over the whole segment with ``extend_all``) -> <bin stem>_<config name>.bin, objects in the
+    reference's order (tracklets in order of first appearance, frames ascending), the tracklet's Waymo type written as
+    it is, the score a 32-bit float on the wire.  The frame lists come from idx2timestamp.pkl / idx2contextname.pkl
+    (load_frame_index), the poses from ``poses_path`` (default <mm_data_root>/poses.pkl).  All tracklets of the file
+    are one launch.  Returns the path written."""
+    cfg, name = load_extend_config(config)
+    device = _device(device)
+    save_path = osp.splitext(cfg['bin_path'])[0] + f'_{name}.bin'
+    print(f'Result will be saved to {save_path}')
+    objects = waymo_io.read_bin(cfg['bin_path'])
+    print(f'Got {len(objects)} objects before extending')
+    tracklets = waymo_io.generate_tracklets(objects)
+    mm_root = cfg.get('mm_data_root', MM_DATA_ROOT)
+    _, seg_ts = load_frame_index(mm_root)
+    with open(cfg.get('poses_path') or osp.join(mm_root, 'poses.pkl'), 'rb') as fr:
+        ts2pose = pickle.load(fr)
+    pk = pack_for_extension(tracklets, seg_ts, ts2pose)
+    use_all = bool(cfg.get('extend_all', False))
+    print(f'Extend all timestamps? {use_all}')
+    back, fwd, out_offsets = plan_extension(pk['offsets'], pk['frames'], pk['segments'], [seg_ts[s] for s in pk['names']],
+                                            cfg['extend_length'], cfg['min_length_to_extend'], use_all,
+                                            cfg.get('min_length_to_extend_all', 0), cfg['direction'])
+    boxes, scores, frames = extend_tracks_packed(pk['boxes'].to(device), pk['offsets'], pk['frames'], pk['segments'],
+                                                 pk['scores'].to(device), pk['poses'].to(device), pk['timestamps'].to(device),
+                                                 pk['seg_offsets'], back, fwd, out_offsets, cfg['score_multiplier'],
+                                                 cfg['velo_window_size'])
+    boxes, scores, frames = boxes.cpu().numpy(), scores.cpu().numpy(), frames.cpu().numpy()
+    chunks = []
+    for k, t in enumerate(tracklets):
+        assert t.type in (1, 2, 4) and isinstance(t.id, str)
+        stamps = seg_ts[t.segment_name]
+        for q in range(out_offsets[k], out_offsets[k + 1]):
+            chunks.append(waymo_io._f_bytes(1, waymo_io.lidar2waymo_box(boxes[q], scores[q], t.type, t.segment_name,
+                                                                         stamps[frames[q]], t.id)))
+    with open(save_path, 'wb') as f:
+        f.write(b''.join(chunks))
+    print(f'Convert finished, got {len(chunks)} objects. Saved to {save_path}')
+    return save_path
+
+
+# ------------------------------------------------------------------------------------------------ empty-box removal
+BOTTOM_LIFT = {'vehicle': 0.2, 'pedestrian': 0.1, 'cyclist': 0.1}     # tools/ctrl/remove_empty.py:155-160
+KITTI_SPLIT = {'training': 'training', 'val': 'training', 'validation': 'training', 'test': 'testing', 'testing': 'testing'}
+
+
+def nonempty_frames_packed(points, point_offsets, boxes, box_offsets):
+    """Arguments as crop_frames_packed -> flags [B] int32 on the device: 1 where crop_frames_packed would count at
+    least one point in the box (the same membership arithmetic).  One launch, no workspace, no read-back."""
+    L.require_device(points, boxes)
+    if points.dim() != 2 or points.size(1) < 3 or points.dtype != torch.float32:
+        raise L.OcoccError(f'points must be [N, >= 3] float32, got {tuple(points.shape)} {points.dtype}')
+    po, bo = [int(v) for v in point_offsets], [int(v) for v in box_offsets]
+    frames = len(po) - 1
+    if len(bo) != frames + 1 or frames < 0 or po[0] != 0 or bo[0] != 0 or po[-1] != points.size(0) or bo[-1] != boxes.size(0) \
+            or any(b < a for a, b in zip(po, po[1:])) or any(b < a for a, b in zip(bo, bo[1:])):
+        raise L.OcoccError('nonempty_frames: offsets must start at 0, not decrease and end at the row counts')
+    dev = points.device
+    points = points.contiguous()
+    boxes = boxes[:, :7].contiguous().float()
+    n, b = points.size(0), boxes.size(0)
+    flags = torch.zeros((b,), dtype=torch.int32, device=dev)
+    if b == 0 or n == 0 or frames == 0:
+        return flags
+    max_pts = max(y - x for x, y in zip(po, po[1:]))
+    offs = torch.tensor(po + bo, dtype=torch.int64).to(dev)
+    L.check(L.lib.ococc_tracklet_nonempty(L.ptr(points), n, points.size(1), L.ptr(offs[:frames + 1]), L.ptr(boxes), b,
+                                          L.ptr(offs[frames + 1:]), frames, max_pts, L.ptr(flags), L.stream()),
+            'tracklet_nonempty')
+    return flags
+
+
+def lifted_lidar_boxes(objects, bottom_lift):
+    """records of read_bin -> [n, 7] f32 boxes as bin2lidarboxes + LiDARInstance3DBoxes(origin=(0.5, 0.5, 0.5)) make
+    them (tools/ctrl/utils.py:68-95, 115-144; remove_empty.py:83-88): bottom centre, (width, length, height) kept in
+    the file's order, yaw = -heading - pi/2 wrapped into [-pi, pi], float32 from there on, then the bottom lifted by
+    bottom_lift * height"""
+    rows = np.zeros((len(objects), 7), np.float64)
+    for i, o in enumerate(objects):
+        heading = -o['heading'] - 0.5 * np.pi
+        while heading < -np.pi:
+            heading += 2 * np.pi
+        while heading > np.pi:
+            heading -= 2 * np.pi
+        rows[i] = [o['center_x'], o['center_y'], o['center_z'], o['width'], o['length'], o['height'], heading]
+    boxes = torch.from_numpy(rows).float()
+    boxes[:, 2] += boxes[:, 5] * -0.5
+    boxes[:, 2] += boxes[:, 5] * bottom_lift
+    return boxes
+
+
+def _nonempty_worker(token, process, payload, device):
+    device = _worker_device(token, device)
+    out, batch, batch_bytes = {}, [], 0
+
+    def flush():
+        nonlocal batch, batch_bytes
+        if not batch:
+            return
+        po = np.concatenate([[0], np.cumsum([len(pc) for _, pc, _ in batch])])
+        bo = np.concatenate([[0], np.cumsum([len(b) for _, _, b in batch])])
+        points = torch.from_numpy(np.concatenate([pc for _, pc, _ in batch], 0)).to(device)
+        boxes = torch.from_numpy(np.concatenate([b for _, _, b in batch], 0)).to(device)
+        flags = nonempty_frames_packed(points, po.tolist(), boxes, bo.tolist()).cpu().numpy()   # one read-back per batch
+        for i, (k, _, _) in enumerate(batch):
+            out[k] = flags[bo[i]:bo[i + 1]].astype(bool)
+        batch, batch_bytes = [], 0
+
+    for k, (ts, boxes) in enumerate(payload['frames']):
+        if k % process != token:
+            continue
+        if ts not in payload['ts2idx']:
+            raise KeyError(f'timestamp {ts} has no frame in idx2timestamp.pkl')
+        pc = np.fromfile(osp.join(payload['pc_root'], f"{payload['ts2idx'][ts]}.bin"), dtype=np.float32).reshape(-1, 6)
+        if batch and (batch_bytes + pc.nbytes > CROP_BATCH_BYTES or len(batch) >= 65535):
+            flush()
+        batch.append((k, pc, boxes))
+        batch_bytes += pc.nbytes
+    flush()
+    return out
+
+
+def remove_empty(bin_path, split, type='vehicle', process=1, gt_bin=None, device=None, mm_data_root=None, extra_hw=0.0):
+    """tools/ctrl/remove_empty.py as a function: every box of ``bin_path`` that holds no lidar point of its frame, after
+    its bottom was lifted by 0.2 (vehicle) / 0.1 (pedestrian, cyclist) of its height, is dropped; the kept objects are
+    written UNCHANGED (waymo_io.write_objects) to <stem>_wo_empty_right.bin, frames in the file's order of first
+    appearance and boxes in file order -- whatever ``process`` is (the reference's order depends on how its worker
+    processes are scheduled).  split: 'training' (also 'val') or 'testing' ('test'), the velodyne directory under
+    ``mm_data_root``.  A batch of frames is one launch and one read-back.  With ``gt_bin`` the waymo_native table of the
+    result is printed and written next to it (<stem>_wo_empty_right.txt), in place of the reference's call of the
+    compiled Waymo tool.  Returns the path written."""
+    process = _check_process(process)
+    if type not in BOTTOM_LIFT:
+        raise NotImplementedError(f'type {type!r}: one of {sorted(BOTTOM_LIFT)}')
+    if split not in KITTI_SPLIT:
+        raise ValueError(f'split must be one of {sorted(KITTI_SPLIT)}, got {split!r}')
+    if extra_hw:
+        raise NotImplementedError('extra_hw other than 0 (enlarged_box_hw) is not built; the reference always runs with 0')
+    mm_root = mm_data_root or MM_DATA_ROOT
+    save_path = osp.join(osp.dirname(bin_path), osp.basename(bin_path).split('.')[0] + '_wo_empty_right.bin')
+    print(f'Results will be saved to {save_path}')
+    objects = waymo_io.read_bin(bin_path)
+    ts2idx, _ = load_frame_index(mm_root)
+    boxes = lifted_lidar_boxes(objects, BOTTOM_LIFT[type]).numpy()
+    rows_of = defaultdict(list)                                  # timestamp -> object rows, file order
+    for i, o in enumerate(objects):
+        rows_of[o['frame_timestamp_micros']].append(i)
+    payload = dict(frames=[(ts, boxes[rows]) for ts, rows in rows_of.items()], ts2idx=ts2idx,
+                   pc_root=osp.join(mm_root, KITTI_SPLIT[split], 'velodyne'))
+    flags = {}
+    for part in _run_workers(_nonempty_worker, process, payload, device if process > 1 else _device(device)):
+        flags.update(part)
+    keep = [objects[i] for k, rows in enumerate(rows_of.values()) for i, f in zip(rows, flags[k]) if f]
+    print(f'Num objects after remove: {len(keep)}')
+    waymo_io.write_objects(keep, save_path)
+    if gt_bin is not None:
+        from . import waymo_metrics
+        waymo_metrics.evaluate_files(save_path, gt_bin, txt_path=save_path.replace('.bin', '.txt'))
+    return save_path

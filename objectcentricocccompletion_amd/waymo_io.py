@@ -154,6 +154,32 @@ def convert_tracklet_to_waymo(tracklets, pkl_path, classes=('Car', 'Pedestrian',
     return pkl_path
 
 
+def write_objects(records, path):
+    """The inverse of read_bin: its records (dicts) -> the metrics.Objects file ``path``, every field as it was read --
+    the box stays in the Waymo convention (centre, length / width / height, heading: no conversion), the score is a
+    32-bit float on the wire, fields in field-number order as the protobuf library writes them.  read_bin does not
+    record presence, so the three optional ground-truth fields and the id are written where they differ from the
+    reader's defaults (False / 0 / 0 / ''): a file read, written and read again gives equal records, and a file of
+    convert_tracklet_to_waymo without explicit zeros in those fields gives equal bytes.  Returns ``path``."""
+    chunks = []
+    for o in records:
+        box = b''.join(_f_double(i + 1, o[k]) for i, k in enumerate(
+            ('center_x', 'center_y', 'center_z', 'width', 'length', 'height', 'heading')))
+        label = _f_bytes(1, box) + _f_varint(3, o['type'])
+        if o['id'] != '':
+            label += _f_bytes(4, str(o['id']).encode())
+        if o['detection_difficulty_level']:
+            label += _f_varint(5, int(o['detection_difficulty_level']))
+        if o['num_lidar_points_in_box']:
+            label += _f_varint(7, int(o['num_lidar_points_in_box']))
+        nlz = _f_varint(3, True) if o['overlap_with_nlz'] else b''
+        chunks.append(_f_bytes(1, _f_bytes(1, label) + _f_float(2, o['score']) + nlz +
+                               _f_bytes(4, str(o['context_name']).encode()) + _f_varint(5, int(o['frame_timestamp_micros']))))
+    with open(path, 'wb') as f:
+        f.write(b''.join(chunks))
+    return path
+
+
 # ------------------------------------------------------------------------------------------------ reader
 def read_bin(file_path):
     """tools/ctrl/utils.py:12-16 -> list of dicts (box fields, type, id, score, context_name, frame_timestamp_micros,

@@ -7,6 +7,7 @@ runs without Waymo data:
                                                    (LEVEL_1, LEVEL_2 and ignored objects: tools/waymo_detection_metrics.py)
     <out>/kitti_format/idx2timestamp.pkl, idx2contextname.pkl, training/velodyne/<idx>.bin   ([n, 6] float32 clouds)
     <out>/synthetic_vehicle.yaml                   tools/ctrl/data_configs/synthetic_vehicle.yaml with this tree's paths
+    <out>/synthetic_extend.yaml                    tools/ctrl/data_configs/synthetic_extend.yaml with this tree's paths
     <out>/poses.pkl, <out>/occ_gt/<segment>/<gt id>.npz    what the dataset class needs besides (as make_synthetic_dataset.py)
 
 usage: python tools/make_synthetic_raw.py <out> [--segments 2] [--tracklets 3] [--frames 40]
@@ -106,6 +107,12 @@ def main(argv=None):
                data_root=os.path.join(out, 'tracklet_data'), mm_data_root=os.path.join(out, 'kitti_format'))
     with open(os.path.join(out, 'synthetic_vehicle.yaml'), 'w') as f:
         yaml.safe_dump(cfg, f, sort_keys=False)
+    with open(os.path.join(ROOT, 'tools', 'ctrl', 'data_configs', 'synthetic_extend.yaml')) as f:
+        ext = yaml.safe_load(f)
+    ext.update(bin_path=os.path.join(out, 'waymo_format', 'pred.bin'), mm_data_root=os.path.join(out, 'kitti_format'),
+               poses_path=os.path.join(out, 'poses.pkl'))
+    with open(os.path.join(out, 'synthetic_extend.yaml'), 'w') as f:
+        yaml.safe_dump(ext, f, sort_keys=False)
     print('wrote', a.segments, 'segments x', a.frames, 'frames,', len(preds), 'predicted /', len(gts), 'GT tracklets under', out)
 
 

@@ -52,6 +52,25 @@ def test_argument_errors_are_reported_not_thrown():
     assert rc == -1 and b'dropout_p' in L.lib.ococc_last_error()
 
 
+def test_decoder_training_forward_requires_its_output_tables():
+    """ococc_occ_mlp_train_fwd_bf16 has one contract: z_out, y_out and stats_out are required.  The null checks run before
+    anything is dereferenced or launched, so host arrays stand in for every buffer."""
+    from objectcentricocccompletion_amd import _lib as L
+    buf = (ctypes.c_float * 4)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    table = (ctypes.c_void_p * 3)(p.value, p.value, p.value)
+
+    def call(z_out, y_out, stats_out):
+        return L.lib.ococc_occ_mlp_train_fwd_bf16(p, 64, p, p, table, table, table, 1e-3, p, None, 0, None, z_out, y_out,
+                                                  stats_out, p, None)
+
+    rc = call(None, table, table)
+    assert rc == -1 and b'z_out' in L.lib.ococc_last_error()
+    assert call(table, None, table) == -1 and call(table, table, None) == -1
+    rc = call(table, (ctypes.c_void_p * 3)(p.value, p.value, None), table)   # (no "y2 not kept" form any more)
+    assert rc == -1 and b'null pointer' in L.lib.ococc_last_error()
+
+
 def test_conv_layernorm_descriptor_layout():
     """The LayerNorm epilogue descriptor of the three convolution exports (ococc_conv_ln, _lib.ConvLn), pinned field by
     field through argument errors: every call has n_out = 0, so the checks run and nothing touches a device."""

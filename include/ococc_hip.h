@@ -648,6 +648,28 @@ int ococc_frame_match_f32(const float* pd_boxes, const int32_t* pd_type, const i
                           const int64_t* pair_offsets, int32_t frame_begin, int32_t frame_end, int64_t pair_begin,
                           int64_t pair_end, int32_t max_frame_gt, const float host_iou_thresh[5], int32_t* match_gt,
                           float* match_iou, void* workspace, int64_t workspace_bytes, ococc_stream_t stream);
+/* replaces the same stage of compute_detection_metrics_main with the tool's default matcher as DESIGN.md states it
+ *   (rule 4b: Hungarian, i.e. maximum total overlap, one matching per score cutoff) in place of the score-first greedy
+ *   pass of ococc_frame_match_f32: the overlap launch of that export unchanged, then one assignment launch.
+ * Inputs as ococc_frame_match_f32 (the workspace too: ococc_frame_match_workspace_bytes), plus max_frame_pd: the largest
+ * n_pd among the frames of the call; 18 B * align64(max_frame_gt) + 2 B * align64(max_frame_pd) must fit 64 KiB of LDS.
+ * An edge is an eligible equal-type pair with IoU >= threshold, its weight (int)(iou * 1000.0f) (0: no edge).
+ * Predictions are inserted in their order, one shortest-augmenting-path search each (integer potentials, cost =
+ * -weight, a private zero-cost "unmatched" column per prediction): after n insertions the matching has maximum total
+ * weight for the first n predictions of the (frame, type) group.  Ties: a real column before a private one, the lower
+ * ground-truth index among real columns, the row reached first among private ones.
+ * snap_offsets [P] i64: -1, or where the snapshot that ends at this prediction starts in snapshots [num_snap_words] i32:
+ * snapshots[snap_offsets[p] + r] = the index into gt_boxes of the partner of the r-th prediction of p's (frame, type)
+ * group, or -1, in the matching of the group's predictions up to and including p (r = 0 .. p - group start).  The host
+ * sets an offset at the last prediction of every score-cutoff bucket and sizes the buffer; snapshots that would not
+ * fit num_snap_words are not written.  No atomics, one writer per word: the same input gives the same bytes. */
+int ococc_frame_assign_i32(const float* pd_boxes, const int32_t* pd_type, const int32_t* pd_eligible,
+                           const int32_t* pd_offsets, int64_t num_pd, const float* gt_boxes, const int32_t* gt_type,
+                           const int32_t* gt_eligible, const int32_t* gt_offsets, int64_t num_gt,
+                           const int64_t* pair_offsets, int32_t frame_begin, int32_t frame_end, int64_t pair_begin,
+                           int64_t pair_end, int32_t max_frame_gt, int32_t max_frame_pd, const float host_iou_thresh[5],
+                           const int64_t* snap_offsets, int64_t num_snap_words, int32_t* snapshots, void* workspace,
+                           int64_t workspace_bytes, ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * occupancy IoU counts of one chunk of RoIs, replacing the ATen chain of TrackletRoIHeadOCC.test_occ

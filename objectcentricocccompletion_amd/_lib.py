@@ -119,6 +119,8 @@ SIGNATURES = {
     'ococc_frame_match_workspace_bytes': (c_i64, [c_i64]),
     'ococc_frame_match_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32,
                                       c_i64, c_i64, c_i32, ctypes.c_float * 5, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'ococc_frame_assign_i32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32,
+                                       c_i64, c_i64, c_i32, c_i32, ctypes.c_float * 5, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     'ococc_occ_iou_count': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_vp, c_i64, c_i64, c_vp]),
     'ococc_group_rank_workspace_bytes': (c_i64, [c_i64, c_i64]),
     'ococc_group_rank_i32': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),

@@ -119,13 +119,14 @@ class WaymoTrackletDataset(Dataset):
             return data
 
     def evaluate(self, results, metric='waymo', logger=None, pklfile_prefix=None, submission_prefix=None, show=False,
-                 out_dir=None, pipeline=None, metrics_main=None, assume_points=False):
+                 out_dir=None, pipeline=None, metrics_main=None, assume_points=False, matcher='score_first'):
         """:315-428 -- results: the refined tracklets (``id`` str, ``segment_name``, ``type`` = class index); writes
         ``pklfile_prefix``.bin and evaluates it against <waymo_format>/gt.bin (train_gt.bin for 'result_train' prefixes)
         with the Waymo tool ``metrics_main`` (waymo_io.evaluate: without the tool, the .bin is written and the call
         raises).  metric 'waymo_native' (alone or in a list with 'waymo'): the same two files through
         waymo_metrics.detection_metrics (HIP matching kernels; its protocol and its departures from the tool are stated
-        there), the table printed and written to ``pklfile_prefix``.txt; ``assume_points`` as there."""
+        there), the table printed and written to ``pklfile_prefix``.txt; ``assume_points`` and ``matcher``
+        ('score_first' or 'hungarian') as there."""
         from . import waymo_io
         metrics = [metric] if isinstance(metric, str) else list(metric)
         unknown = [m for m in metrics if m not in ('waymo', 'waymo_native')]
@@ -137,7 +138,7 @@ class WaymoTrackletDataset(Dataset):
         if 'waymo_native' in metrics:
             from . import waymo_metrics
             path = waymo_io.convert_tracklet_to_waymo(results, pklfile_prefix, self.CLASSES)
-            out.update(waymo_metrics.evaluate_files(path, gt, assume_points, f'{pklfile_prefix}.txt'))
+            out.update(waymo_metrics.evaluate_files(path, gt, assume_points, f'{pklfile_prefix}.txt', matcher))
         if 'waymo' in metrics:
             out.update(waymo_io.evaluate(results, pklfile_prefix, gt, self.CLASSES, metrics_main))
         return out
@@ -173,7 +174,7 @@ class WaymoTrackletDatasetWithOcc(WaymoTrackletDataset):
         return out
 
     def evaluate(self, results, metric='waymo', logger=None, pklfile_prefix=None, submission_prefix=None, show=False,
-                 out_dir=None, pipeline=None, metrics_main=None, assume_points=False):
+                 out_dir=None, pipeline=None, metrics_main=None, assume_points=False, matcher='score_first'):
         """:586-672 -- results: one model output per tracklet (``out_tracklets``, and ``inters`` / ``unions`` /
         ``gt_boxes`` with test_occ_iou).  metric 'waymo', 'waymo_native', 'iou' or several (a list): 'waymo' and
         'waymo_native' hand the refined tracklets (``r['out_tracklets'][0]``) to WaymoTrackletDataset.evaluate; 'iou'
@@ -190,7 +191,7 @@ class WaymoTrackletDatasetWithOcc(WaymoTrackletDataset):
                 import tempfile
                 pklfile_prefix = osp.join(tempfile.mkdtemp(), 'results')
             res = super().evaluate([r['out_tracklets'][0] for r in results], detection, logger, pklfile_prefix,
-                                   submission_prefix, show, out_dir, pipeline, metrics_main, assume_points)
+                                   submission_prefix, show, out_dir, pipeline, metrics_main, assume_points, matcher)
             out.update(res or {})
         if 'iou' in metrics:
             from .roi_head import occupancy_iou_metrics

@@ -1,5 +1,6 @@
 #!/usr/bin/env bash
 # Same CLI as the reference's tools/dist_test.sh:  dist_test.sh <config> <checkpoint> <gpus> [test.py args]
+# test.py args pass through, e.g.  --eval waymo_native --matcher hungarian
 # One process per MI355X; each rank evaluates a contiguous shard of the tracklets, rank 0 gathers and evaluates.
 CONFIG=$1
 CHECKPOINT=$2

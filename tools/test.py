@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Test / evaluation entry point with the CLI of the reference's tools/test.py (:23-87):
-    python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--eval iou waymo waymo_native] [--format-only]
+    python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--eval iou waymo waymo_native] [--matcher {score_first,hungarian}] [--format-only]
                          [--eval-options k=v ...] [--cfg-options k=v ...] [--launcher {none,pytorch}]
                          [--tmpdir DIR] [--gpu-collect] [--local_rank N]
 The test dataset is the config's data.test (the reference's data/waymo layout); with --data-root DIR it reads the tree
@@ -40,6 +40,8 @@ def parse_args(argv=None):
     ap.add_argument('--format-only', action='store_true', help='write the Waymo result file without evaluating it')
     ap.add_argument('--eval', type=str, nargs='+', choices=METRICS, help='metrics: iou (occupancy), waymo (detection, needs the Waymo tool), waymo_native (detection, '
                     'HIP matching kernels: objectcentricocccompletion_amd/waymo_metrics.py)')
+    ap.add_argument('--matcher', choices=('score_first', 'hungarian'), default=None,
+                    help='matcher of --eval waymo_native (default score_first; hungarian: maximum total overlap per score cutoff)')
     ap.add_argument('--show', action='store_true', help='ignored: no visualisation here')
     ap.add_argument('--show-dir', help='ignored: no visualisation here')
     ap.add_argument('--gpu-collect', action='store_true', help='collect the ranks\' results by an all-gather')
@@ -60,6 +62,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if 'LOCAL_RANK' not in os.environ:
         os.environ['LOCAL_RANK'] = str(args.local_rank)
+    if args.matcher and 'waymo_native' not in (args.eval or []):
+        ap.error('--matcher goes with --eval waymo_native')
     if args.options and args.eval_options:
         ap.error('--options and --eval-options cannot be both specified')
     if args.options:
@@ -182,6 +186,8 @@ def main(argv=None):
         eval_kwargs = {k: v for k, v in (cfg.get('evaluation') or {}).items()
                        if k not in ('interval', 'tmpdir', 'start', 'gpu_collect', 'save_best', 'rule')}
         eval_kwargs.update(kwargs, metric=args.eval)
+        if args.matcher:
+            eval_kwargs['matcher'] = args.matcher
         metrics = ds.evaluate(outputs, **eval_kwargs)
         print(metrics, flush=True)
     return metrics

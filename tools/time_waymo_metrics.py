@@ -3,6 +3,7 @@
 host packing, kernels (uploads, the launches, the read-back) and host curves, each over --repeats runs after --warmup.
 
     python tools/time_waymo_metrics.py [--frames 40000] [--gt 60] [--pred 80] [--repeats 5] [--warmup 1] [--checker-frames 0]
+                                        [--matcher {score_first,hungarian}]
 
 --checker-frames N additionally times the float64 checker of the tests (tests/waymo_metrics_ref.py) on the first N
 frames, for scale.  The input is drawn from a seed: ground truth spread over +-75 m, three of four predictions
@@ -10,6 +11,7 @@ perturbed copies of a ground-truth box."""
 import argparse
 import json
 import os
+import resource
 import sys
 import time
 
@@ -69,6 +71,7 @@ def main(argv=None):
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--checker-frames', type=int, default=0)
+    ap.add_argument('--matcher', choices=('score_first', 'hungarian'), default='score_first')
     a = ap.parse_args(argv)
     import torch
     from objectcentricocccompletion_amd import waymo_metrics as M
@@ -78,21 +81,27 @@ def main(argv=None):
     for r in range(a.warmup + a.repeats):
         t = {}
         t0 = time.perf_counter()
-        _, ap_dict = M.detection_metrics(pd, gt, timings=t)
+        _, ap_dict = M.detection_metrics(pd, gt, timings=t, matcher=a.matcher)
         t['total'] = time.perf_counter() - t0
         if r >= a.warmup:
             runs.append(t)
-    # the device part alone: events around frame_match on resident tensors
+    # the device part alone: events around frame_match (frame_assign with --matcher hungarian) on resident tensors
     pk = M.pack(pd, gt)
     dev = torch.device('cuda', torch.cuda.current_device())
     up = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x.astype(dt))).to(dev)
     args = (up(pk['pd_boxes'], np.float32), up(pk['pd_type'], np.int32), up(pk['pd_eligible'], np.int32), pk['pd_offsets'],
             up(pk['gt_boxes'], np.float32), up(pk['gt_type'], np.int32), up(pk['gt_eligible'], np.int32), pk['gt_offsets'])
+    if a.matcher == 'hungarian':
+        # the snapshot layout is host arithmetic on the scores: made once, outside the events
+        layout = M.snapshot_layout(pk['pd_offsets'], pk['pd_type'], M.cutoff_buckets(pk['pd_score']))
+        device_part = lambda: M.frame_assign(*args, layout=layout)
+    else:
+        device_part = lambda: M.frame_match(*args)
     dev_ms = []
     for r in range(a.warmup + a.repeats):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        M.frame_match(*args)
+        device_part()
         e1.record()
         torch.cuda.synchronize()
         if r >= a.warmup:
@@ -104,11 +113,17 @@ def main(argv=None):
     t1 = time.perf_counter()
     M.columns(recs)
     t2 = time.perf_counter()
-    out = dict(frames=a.frames, predictions=len(pd['score']), ground_truth=len(gt['score']),
+    out = dict(matcher=a.matcher, frames=a.frames, predictions=len(pd['score']), ground_truth=len(gt['score']),
                pairs=int(a.frames) * a.gt * a.pred, repeats=a.repeats,
                seconds={k: stat([t[k] for t in runs]) for k in ('host_pack', 'kernels', 'host_curves', 'total')},
-               frame_match_device_ms=stat(dev_ms), columns_from_records_us_per_object=(t2 - t1) / n_rec * 1e6,
+               columns_from_records_us_per_object=(t2 - t1) / n_rec * 1e6,
                vehicle_l1_map=ap_dict['Vehicle/L1 mAP'])
+    # between events, tensors resident: frame_match, or frame_assign with its snapshot buffer (allocated and filled inside)
+    out['frame_match_device_ms' if a.matcher == 'score_first' else 'frame_assign_device_ms'] = stat(dev_ms)
+    if a.matcher == 'hungarian':
+        out['snapshot_words'] = int(layout['total'])
+        out['snapshots'] = int(len(layout['ends']))
+    out['peak_rss_mb'] = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
     if a.checker_frames:
         sys.path.insert(0, os.path.join(ROOT, 'tests'))
         import waymo_metrics_ref as R

@@ -685,6 +685,51 @@ int ococc_occ_iou_count(const float* logits, const int64_t* labels, const float*
                         int32_t n, int64_t K, float pos_thresh, int64_t* counts, int64_t row0, int64_t rows,
                         ococc_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * completed-occupancy export (csrc/occ_export.hip): the dense-grid decode around the decoder and the compaction of its
+ * occupied cells, behind OccDecoder.get_occ_packed and TrackletRoIHeadOCC.save_occ_from_tracklet
+ *   (mmdet3d/models/roi_heads/tracklet_roi_head_occ.py:612-745).
+ * The cells of R RoIs are one flat list, RoI after RoI, x slowest and z fastest inside an RoI:
+ *   sizes [R, 3] f32 the enlarged box sizes, dims [R, 3] i32 = ceil(size / voxel_size) (fewer than 2^31 cells per RoI),
+ *   start [R + 1] i64 the exclusive prefix of dims.prod(1) (start[0] = 0, start[R] = n cells).
+ * The centre of cell c of an axis is (c * voxel_size + (-size / 2)) + voxel_size / 2, each operation rounded to f32 on
+ * its own (no fused multiply-add): bit for bit what the ATen chain gives.  R == 0 is an empty result, not an error.
+ *
+ * ococc_dense_grid_cells_f32 replaces generate_dense_voxel_centers (mmdet3d/ops/occ/occ_ops.py:5-50) and the per-box
+ *   feature repeat of get_occ (mmdet3d/models/occ/occ_base.py:300-308) for the cells [lo, hi) of the list:
+ *   centers [hi - lo, 3] f32 and roi_index [hi - lo] i32 (the add_index of ococc_occ_mlp_fwd_bf16).  One launch.
+ *
+ * ococc_occ_select_count replaces the sigmoid / compare / bincount of get_occ (occ_base.py:310-327) on logits [n] f32 of
+ *   the one-logit decoder.  The list is cut into tiles of 1024 consecutive cells of one RoI (never two RoIs in a tile):
+ *   it writes tile_start [R + 1] i64, the exclusive prefix of ceil(cells / 1024) per RoI (derived from start by a
+ *   one-wave launch in front), tile_counts [max_tiles] i32 (occupied cells per tile; 0 behind the last tile) and
+ *   roi_counts [R] i64 (zeroed here).  max_tiles >= ococc_occ_select_max_tiles(n, R) = n / 1024 + R, known without
+ *   reading the device.  Occupied: 1 / (1 + exp(-logit)) > pos_thresh in f32 (ATen's sigmoid; NaN is empty), the same
+ *   device function as ococc_occ_iou_count.  Integer atomics only.
+ *
+ * ococc_occ_select_fill replaces the boolean index and the transform of get_occ (occ_base.py:312-336): given tile_scan
+ *   [max_tiles] i64, the exclusive prefix of tile_counts, it writes the occupied cells in cell order to
+ *   out [n_out, cols] f32 (n_out = sum of roi_counts; rows past n_out are not written).  Columns 0-2: the cell centre in
+ *   the box frame, or with to_lidar in the LiDAR frame: x' = x c + y s, y' = -x s + y c, then + the box centre
+ *   (rois[r, 1:4]), then z + rois[r, 6] / 2, each operation rounded on its own; rois are rows of roi_stride >= 7 floats
+ *   (batch, x, y, z_bottom, w, l, h, yaw, ...), cos_yaw / sin_yaw [R] the caller's cos / sin of the yaw (no
+ *   trigonometric function is evaluated here).  cols == 4 adds roi_value[r] when roi_value [R] is given (the per-frame
+ *   box score save_occ_from_tracklet pads with, :732-737), else sigmoid(logit); out is then 16-byte aligned.
+ *   Ballots and popcounts keep the order (the idiom of ococc_tracklet_crop_fill); no atomics.
+ * ------------------------------------------------------------------------ */
+int ococc_dense_grid_cells_f32(const float* sizes, const int32_t* dims, const int64_t* start, int32_t R,
+                               float voxel_size, int64_t lo, int64_t hi, float* centers, int32_t* roi_index,
+                               ococc_stream_t stream);
+int64_t ococc_occ_select_max_tiles(int64_t n, int32_t R);
+int ococc_occ_select_count(const float* logits, int64_t n, const int64_t* start, int32_t R, float pos_thresh,
+                           int64_t* tile_start, int32_t* tile_counts, int64_t max_tiles, int64_t* roi_counts,
+                           ococc_stream_t stream);
+int ococc_occ_select_fill(const float* logits, int64_t n, const int64_t* start, const int64_t* tile_start, int32_t R,
+                          float pos_thresh, const int64_t* tile_scan, int64_t max_tiles, const float* sizes,
+                          const int32_t* dims, float voxel_size, int32_t to_lidar, const float* rois,
+                          int64_t roi_stride, const float* cos_yaw, const float* sin_yaw, const float* roi_value,
+                          int32_t cols, float* out, int64_t n_out, ococc_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * A12 glue, one launch each (f32; the element-wise chains they replace were 12-35 launches of a few hundred elements):
  * ococc_rotate_z_f32: rotation_3d_in_axis(points [n, m, 3], angles [n], axis=2)

@@ -7,6 +7,7 @@
 // totals with one 64-bit vector atomic each.  Integer sums: the same result in any order.  Memory bound and tiny next to
 // the decoder that produced the logits; what it saves is the ATen chain and the host read-back per chunk.
 #include "common.hpp"
+#include "occ_math.hpp"
 
 namespace {
 
@@ -33,9 +34,7 @@ occ_iou_count_kernel(const float* __restrict__ logits, const int64_t* __restrict
     const int64_t k = base + threadIdx.x;
     bool pred = false, lab = false;
     if (k < K) {
-      const float x = lg[k];
-      const float s = 1.0f / (1.0f + expf(-x));   // ATen: one / (one + std::exp(-a)) in f32
-      pred = s > pos_thresh;                       // false for NaN
+      pred = ococc_occupied(lg[k], pos_thresh);   // ATen's f32 sigmoid; false for NaN (occ_math.hpp)
       if (q && pred) {
         const float px = q[k * 3 + 0], py = q[k * 3 + 1], pz = q[k * 3 + 2];
         pred = (px >= -hx) && (px <= hx) && (py >= -hy) && (py <= hy) && (pz >= -hz) && (pz <= hz);

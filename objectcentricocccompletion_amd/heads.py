@@ -548,6 +548,11 @@ class OccAutoEncoder(nn.Module, SparseHeadMixin):
         return self.occ_decoder.get_occ(local_roi_feats, rois, self.voxel_size, self.scale_wlh, self.offset_wlh,
                                         transform=transform)
 
+    def get_occ_packed(self, local_roi_feats, rois, transform=True, roi_values=None):
+        """get_occ as one array and the rows per RoI (OccDecoder.get_occ_packed): what the occupancy files are cut from."""
+        return self.occ_decoder.get_occ_packed(local_roi_feats, rois, self.voxel_size, self.scale_wlh, self.offset_wlh,
+                                               transform=transform, roi_values=roi_values)
+
     def get_roi_occ(self, local_roi_feats, rois, transform=True, return_score=False):
         """occ_ae_head.py:440-449."""
         return self.occ_decoder.get_roi_occ(local_roi_feats, rois, self.voxel_size, self.scale_wlh,
@@ -707,6 +712,10 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
             return occ_list
         ori_list = self.occ_ae_head.get_occ(ori_roi_feats, rois, transform=transform)
         return [[torch.cat([a, b], dim=0) for a, b in zip(occs, oris)] for occs, oris in zip(occ_list, ori_list)]
+
+    def get_occ_packed(self, local_roi_feats, rois, transform=True, roi_values=None):
+        """get_occ of the fused features as one array and the rows per RoI (OccDecoder.get_occ_packed)."""
+        return self.occ_ae_head.get_occ_packed(local_roi_feats, rois, transform=transform, roi_values=roi_values)
 
     def transformer_forward(self, rois, roi_frame_inds, roi_feats, nonempty_roi_mask, trans_enc=None):
         if not self.training or self.train_cfg.get('fixed_length', True):

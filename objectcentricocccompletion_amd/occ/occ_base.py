@@ -26,6 +26,8 @@ from . import occ_ops
 
 FUSED_WHOLE_MLP = True   # ... and in ONE launch when the widths are the reference's 60 -> 512 -> 1024 -> 1024 -> 1
 FUSED_TRAIN_MLP = os.environ.get('OCOCC_FUSED_TRAIN_MLP', '1') == '1'   # ... and the bf16 TRAINING forward on that launch too (fused_mlp.occ_mlp_train)
+# get_occ_packed on the kernels of csrc/occ_export.hip (0: the ATen chain of get_occ, also taken by two-logit decoders)
+OCC_EXPORT_KERNEL = os.environ.get('OCOCC_OCC_EXPORT_KERNEL', '1') != '0'
 FUSED_MLP = True   # bf16 inference of OccDecoder on the per-layer kernels of occ/fused_mlp.py (False: library GEMMs + LN kernels)
 
 
@@ -318,6 +320,49 @@ class OccDecoder(nn.Module):
             cur = [per_roi[j] for j in ids]
             res.append(torch.cat(cur, 0) if concat_batch else cur)
         return res
+
+    def get_occ_packed(self, roi_feats, rois, voxel_size, scale_wlh, offset_wlh, transform=True, roi_values=None,
+                       chunk=1 << 20):
+        """The occupied cells of get_occ as ONE array: (points [n, 3 or 4] f32 on the device, RoI after RoI in cell
+        order, counts per RoI as a list of int) -- ``torch.cat`` of get_occ's per-RoI tensors bit for bit, with
+        ``roi_values`` [R] a fourth column holding the value of the row's RoI (the score column of the exported files).
+        Per chunk of cells one cells launch and forward(); then one count launch, one scan, one fill launch
+        (csrc/occ_export.hip): no int64 box index, no boolean index, two read-backs (the number of cells, the counts).
+        Two-logit decoders, CPU tensors and OCOCC_OCC_EXPORT_KERNEL=0 take the ATen chain of get_occ."""
+        from .. import _lib as L
+        R = rois.size(0)
+        assert roi_feats.size(0) == R, f'{roi_feats.size(0)}, {R}'
+        assert R == 0 or rois.size(1) in (8, 10)
+        cols = 3 if roi_values is None else 4
+        if R == 0:
+            return rois.new_zeros((0, cols)), []
+        if not (OCC_EXPORT_KERNEL and self.cls_dim == 1 and roi_feats.is_cuda):
+            if OCC_EXPORT_KERNEL:
+                L.log_once(('occ-export', self.cls_dim, roi_feats.is_cuda),
+                           'OccDecoder.get_occ_packed: the export kernels take the one-logit decoder on a ROCm device; '
+                           'running the ATen chain of get_occ')
+            return self._get_occ_packed_aten(roi_feats, rois, voxel_size, scale_wlh, offset_wlh, transform, roi_values)
+        rois = rois.float().contiguous()
+        sizes, dims, start, total = occ_ops.dense_grid_layout(rois[:, 4:7], voxel_size, scale_wlh, offset_wlh)
+        out = []
+        with torch.no_grad():
+            for lo in range(0, total, chunk):
+                centers, index = occ_ops.dense_grid_cells(sizes, dims, start, voxel_size, lo, min(lo + chunk, total), total)
+                out.append(self.forward(roi_feats, centers, index))
+        logits = (torch.cat(out, 0) if len(out) > 1 else out[0]) if out else rois.new_zeros((0, 1))
+        return occ_ops.occ_select(logits, sizes, dims, start, total, voxel_size, self.pos_thresh,
+                                  rois if transform else None, roi_values)
+
+    def _get_occ_packed_aten(self, roi_feats, rois, voxel_size, scale_wlh, offset_wlh, transform, roi_values):
+        sizes = rois[:, 4:7]
+        centers, box, _, logits = self._dense_logits(roi_feats, sizes, voxel_size, scale_wlh, offset_wlh)
+        sel = self._occupied(logits)
+        pts, pbox = centers[sel], box[sel]
+        if transform:
+            pts = self._to_lidar(pts, pbox, rois[:, 1:4], sizes, rois[:, 7])
+        if roi_values is not None:
+            pts = torch.cat([pts, roi_values.to(pts.dtype).view(-1)[pbox].view(-1, 1)], 1)
+        return pts, torch.bincount(pbox, minlength=rois.size(0)).tolist()
 
     def get_cls_from_pred(self, pred):
         if self.cls_dim == 1:

@@ -92,3 +92,92 @@ def occ_iou_count(logits, labels, counts, row0, pos_thresh, roi_xyz=None, half_s
                                       float(pos_thresh), L.ptr(counts), int(row0), counts.size(0), L.stream()),
             'occ_iou_count')
     return counts
+
+
+def dense_grid_layout(bbox_sizes, voxel_size, scale_wlh=[1.0, 1.0, 1.0], offset_wlh=[0.0, 0.0, 0.0]):
+    """The grid of every box as the kernels of csrc/occ_export.hip take it: (enlarged sizes [R, 3] f32, dims [R, 3] i32,
+    start [R + 1] i64 the exclusive prefix of the cells per box, total).  Built on the device with the expressions of
+    dense_voxel_centers_batched; the total is the one read-back."""
+    size = (bbox_sizes * bbox_sizes.new_tensor(scale_wlh) + bbox_sizes.new_tensor(offset_wlh)).contiguous()
+    dims = torch.ceil(size / voxel_size).to(torch.long)
+    start = torch.zeros(size.size(0) + 1, dtype=torch.long, device=size.device)
+    if size.size(0):
+        torch.cumsum(dims[:, 0] * dims[:, 1] * dims[:, 2], 0, out=start[1:])
+    return size, dims.to(torch.int32), start, int(start[-1]) if size.size(0) else 0
+
+
+def _check_layout(L, what, sizes, dims, start):
+    R = sizes.size(0) if sizes.dim() == 2 else -1
+    if sizes.dtype != torch.float32 or sizes.dim() != 2 or sizes.size(1) != 3 or dims.dtype != torch.int32 \
+            or tuple(dims.shape) != (R, 3) or start.dtype != torch.int64 or tuple(start.shape) != (R + 1,):
+        raise L.OcoccError(f'{what}: sizes f32 [R, 3], dims int32 [R, 3] and start int64 [R + 1] expected, got '
+                           f'{tuple(sizes.shape)} {sizes.dtype}, {tuple(dims.shape)} {dims.dtype}, '
+                           f'{tuple(start.shape)} {start.dtype}')
+    return R
+
+
+def dense_grid_cells(sizes, dims, start, voxel_size, lo, hi, total):
+    """Cells [lo, hi) of the flat cell list of dense_grid_layout in one launch (csrc/occ_export.hip): (centres
+    [hi - lo, 3] f32 in the box frame, box index [hi - lo] int32), bit for bit rows lo..hi of
+    dense_voxel_centers_batched.  ``total``: the number of cells dense_grid_layout returned (hi beyond it is refused).
+    Nothing is read back."""
+    from .. import _lib as L
+    L.require_device(sizes, dims, start)
+    R = _check_layout(L, 'dense_grid_cells', sizes, dims, start)
+    lo, hi = int(lo), int(hi)
+    if hi < lo or lo < 0 or hi > int(total):
+        raise L.OcoccError(f'dense_grid_cells: cell range [{lo}, {hi}) of {int(total)} cells')
+    centers = L.empty((hi - lo, 3), torch.float32, sizes.device)
+    index = L.empty((hi - lo,), torch.int32, sizes.device)
+    L.check(L.lib.ococc_dense_grid_cells_f32(L.ptr(sizes.contiguous()), L.ptr(dims.contiguous()), L.ptr(start.contiguous()),
+                                             R, float(voxel_size), lo, hi, L.ptr(centers), L.ptr(index), L.stream()),
+            'dense_grid_cells')
+    return centers, index
+
+
+def occ_select(logits, sizes, dims, start, total, voxel_size, pos_thresh, rois=None, roi_values=None, with_score=False):
+    """The occupied cells (sigmoid(logit) > pos_thresh, as ATen decides it) of the flat cell list, in cell order:
+    (points [n_occ, 3 or 4] f32 on the device, counts per box as a list of int).  logits [N] or [N, 1] f32 of the
+    one-logit decoder, N == ``total``, the number of cells dense_grid_layout returned.  Columns 0-2: the cell centre in the box frame, or with ``rois`` ([R, >= 8]: batch, x, y, z, w, l,
+    h, yaw) in the LiDAR frame by OccDecoder._to_lidar's arithmetic; column 3: ``roi_values[box]`` when given, else (with
+    ``with_score``) sigmoid(logit).  One count launch, one scan, one fill launch (csrc/occ_export.hip); the one
+    read-back is the per-box counts."""
+    from .. import _lib as L
+    L.require_device(logits, sizes, dims, start, rois, roi_values)
+    R = _check_layout(L, 'occ_select', sizes, dims, start)
+    n = logits.numel()
+    if logits.dtype != torch.float32 or (logits.dim() == 2 and logits.size(1) != 1) or logits.dim() > 2:
+        raise L.OcoccError(f'occ_select: logits {tuple(logits.shape)} {logits.dtype} are not f32 [N] or [N, 1]')
+    if n != int(total):
+        raise L.OcoccError(f'occ_select: {n} logits for a layout of {int(total)} cells')
+    if rois is not None and (rois.dtype != torch.float32 or rois.dim() != 2 or rois.size(0) != R or rois.size(1) < 8):
+        raise L.OcoccError(f'occ_select: rois {tuple(rois.shape)} {rois.dtype} are not f32 [{R}, >= 8]')
+    if roi_values is not None and (roi_values.dtype != torch.float32 or roi_values.numel() != R):
+        raise L.OcoccError(f'occ_select: roi_values {tuple(roi_values.shape)} {roi_values.dtype} are not f32 [{R}]')
+    dev = logits.device
+    cols = 4 if (roi_values is not None or with_score) else 3
+    if R == 0:
+        return L.empty((0, cols), torch.float32, dev), []
+    logits, sizes, dims, start = logits.contiguous(), sizes.contiguous(), dims.contiguous(), start.contiguous()
+    tiles = int(L.lib.ococc_occ_select_max_tiles(n, R))
+    tile_start = L.empty((R + 1,), torch.int64, dev)
+    tile_counts = L.empty((tiles,), torch.int32, dev)
+    roi_counts = L.empty((R,), torch.int64, dev)
+    L.check(L.lib.ococc_occ_select_count(L.ptr(logits), n, L.ptr(start), R, float(pos_thresh), L.ptr(tile_start),
+                                         L.ptr(tile_counts), tiles, L.ptr(roi_counts), L.stream()), 'occ_select_count')
+    scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts  # exclusive: where a tile's cells start
+    counts = [int(v) for v in roi_counts.tolist()]                      # the one read-back
+    n_occ = sum(counts)
+    out = L.empty((n_occ, cols), torch.float32, dev)
+    cos = sin = None
+    if rois is not None:
+        rois = rois.contiguous()
+        cos, sin = torch.cos(rois[:, 7]).contiguous(), torch.sin(rois[:, 7]).contiguous()
+    if roi_values is not None:
+        roi_values = roi_values.contiguous().view(-1)
+    L.check(L.lib.ococc_occ_select_fill(L.ptr(logits), n, L.ptr(start), L.ptr(tile_start), R, float(pos_thresh),
+                                        L.ptr(scan), tiles, L.ptr(sizes), L.ptr(dims), float(voxel_size),
+                                        int(rois is not None), L.ptr(rois), rois.size(1) if rois is not None else 0,
+                                        L.ptr(cos), L.ptr(sin), L.ptr(roi_values), cols, L.ptr(out), n_occ, L.stream()),
+            'occ_select_fill')
+    return out, counts

@@ -39,6 +39,17 @@ def bbox3d2roi(bbox_list):
     return rois
 
 
+def check_save_occ_cfg(test_cfg):
+    """test_cfg.save_occ (export the completed occupancy from simple_test) needs occ_save_root and excludes test_cfg.tta:
+    the augmented frames are not the frames to export.  Checked when the head is built, before any forward pass."""
+    if not test_cfg or not test_cfg.get('save_occ', False):
+        return
+    if test_cfg.get('tta', None) is not None:
+        raise ValueError('test_cfg.save_occ with test_cfg.tta: the augmented frames are not the frames to export')
+    if not test_cfg.get('occ_save_root', None):
+        raise ValueError('test_cfg.save_occ needs test_cfg.occ_save_root, the directory the files go to')
+
+
 @HEADS.register_module()
 class TrackletRoIHeadOCC(nn.Module):
 
@@ -46,6 +57,7 @@ class TrackletRoIHeadOCC(nn.Module):
                  pretrained=None, init_cfg=None, general_cfg=dict(), history_only=False):
         super().__init__()
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        check_save_occ_cfg(test_cfg)
         self.general_cfg, self.num_classes = general_cfg, num_classes
         self.with_roi_scores = general_cfg.get('with_roi_scores', False)
         self.with_roi_corners = general_cfg.get('with_roi_corners', False)
@@ -325,7 +337,46 @@ class TrackletRoIHeadOCC(nn.Module):
         if self.test_cfg.get('test_occ_iou', False):
             out.update(self.test_occ(rois, res['fused_roi_feats'], gt_rois, gt_occ_list, gt_occ_score_list, pts_xyz,
                                      pts_batch_idx, pts_frame_inds, roi_frame_inds))
+        if self.test_cfg.get('save_occ', False):
+            # (the reference defines save_occ_from_tracklet and never calls it; test_cfg.save_occ is this package's key)
+            check_save_occ_cfg(self.test_cfg)   # (again: the config may have changed since the head was built)
+            self.save_occ_from_tracklet(tracklet_list, res)
         return [out]
+
+    @torch.no_grad()
+    def save_occ_from_tracklet(self, tracklet_list, bbox_results, gt_tracklet_list=None, gt_occ_list=None,
+                               gt_occ_score_list=None, save_gt_occ=False, gt_score=None):
+        """The completed occupancy of one tracklet as files (tracklet_roi_head_occ.py:612-745, prediction branch):
+        ``<test_cfg.occ_save_root>/<segment>/<timestamp>/<type>_<id>.bin`` per frame, float32 [n, 4]: the occupied cell
+        centres of get_occ(fused features, transform=True) and the frame's box score (``gt_score[i]`` when given) in
+        every row.  Frames under test_cfg.min_evaluate_length are not written, nor (test_cfg.filter_empty_roi) frames
+        whose RoI had no points.  One packed array per tracklet (bbox_head.get_occ_packed), one device-to-host copy,
+        sliced on the host (occ_export.write_tracklet_occ).  Returns the paths written."""
+        from . import occ_export
+        assert len(tracklet_list) == 1, 'only support batch size 1'
+        if save_gt_occ:
+            raise NotImplementedError(
+                'save_occ_from_tracklet(save_gt_occ=True): the reference\'s ground-truth branch crops the labels with '
+                'points_in_boxes_gpu of the roiaware_pool3d extension, which is outside this package\'s scope; only the '
+                'predicted occupancy is exported')
+        tracklet = tracklet_list[0]
+        rois, _, _, _ = self.tracklets2rois([tracklet])
+        feats = bbox_results['fused_roi_feats']
+        score_list = tracklet.concated_scores()
+        if gt_score is not None:
+            assert len(score_list) == len(gt_score), f'{len(score_list)} != {len(gt_score)}'
+            score_list = torch.as_tensor(gt_score, dtype=torch.float32)
+        scores = score_list.detach().to(device=feats.device, dtype=torch.float32)
+        packed, counts = self.bbox_head.get_occ_packed(feats, rois, transform=True, roi_values=scores)
+        skip = set(range(min(self.test_cfg.get('min_evaluate_length', 0), len(counts))))
+        if self.test_cfg.get('filter_empty_roi', False):
+            nonempty = bbox_results['nonempty_roi_mask'].tolist()
+            for i in range(len(counts)):
+                if i not in skip and not nonempty[i]:
+                    print(f'empty roi {i} in {tracklet.segment_name} at {tracklet.ts_list[i]}')
+                    skip.add(i)
+        return occ_export.write_tracklet_occ(self.test_cfg['occ_save_root'], tracklet.segment_name, tracklet.ts_list,
+                                             tracklet.type, tracklet.id, packed.cpu().numpy(), counts, skip)
 
     @staticmethod
     def inverse_aug(trk, boxes, meta):

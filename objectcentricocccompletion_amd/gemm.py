@@ -14,25 +14,19 @@ import os
 import torch
 import torch.nn.functional as F
 
+from . import linear as _linear
+from .linear import mm_f32 as _mm
+
 GEMM_DTYPE = {'bf16': torch.bfloat16, 'bfloat16': torch.bfloat16}.get(os.environ.get('OCOCC_GEMM_DTYPE', '').lower())
 # EMULATE: f32 GEMMs on operands ROUNDED to bf16, forward and backward -- the same numbers as the bf16 products up to the order of the f32 sums
 # (tests: the mixed path computes what it says; what bf16 operands cost against the f32 reference is then one subtraction)
 EMULATE = False
-_TALL = 16384   # rows from which a weight gradient is contracted in slices (fused_mlp.wgrad_rows_bf16)
 
 
 def _r(t, dt):
     """operand of a product: rounded to ``dt``; EMULATE: rounded, then back in f32 (the product then runs as an f32 GEMM)"""
     t = t.to(dt)
     return t.float() if EMULATE else t
-
-
-def _mm(a, b):
-    return torch.mm(a, b) if a.dtype == torch.float32 else torch.mm(a, b, out_dtype=torch.float32)
-
-
-def _bmm(a, b):
-    return torch.bmm(a, b) if a.dtype == torch.float32 else torch.bmm(a, b, out_dtype=torch.float32)
 
 
 class _MixedLinear(torch.autograd.Function):
@@ -59,9 +53,8 @@ class _MixedLinear(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = _mm(dy16, w16).view(shape).to(xdt)
         if ctx.needs_input_grad[1]:
-            if dy16.shape[0] >= _TALL and dy16.dtype != torch.float32:
-                from .occ.fused_mlp import wgrad_rows_bf16
-                dw = wgrad_rows_bf16(dy16, x16).to(wdt)
+            if dy16.shape[0] >= _linear.TALL_ROWS and dy16.dtype != torch.float32:
+                dw = _linear.wgrad_rows_bf16(dy16, x16).to(wdt)
             else:
                 dw = _mm(dy16.t(), x16).to(wdt)
         if bdt is not None and ctx.needs_input_grad[2]:
@@ -77,14 +70,14 @@ class _MixedBmm(torch.autograd.Function):
         a16, b16 = _r(a, GEMM_DTYPE), _r(b, GEMM_DTYPE)
         ctx.save_for_backward(a16, b16)
         ctx.dts = (a.dtype, b.dtype)
-        return _bmm(a16, b16).to(a.dtype)
+        return _mm(a16, b16).to(a.dtype)
 
     @staticmethod
     def backward(ctx, dy):
         a16, b16 = ctx.saved_tensors
         dy16 = _r(dy, GEMM_DTYPE)
-        da = _bmm(dy16, b16.transpose(1, 2)).to(ctx.dts[0]) if ctx.needs_input_grad[0] else None
-        db = _bmm(a16.transpose(1, 2), dy16).to(ctx.dts[1]) if ctx.needs_input_grad[1] else None
+        da = _mm(dy16, b16.transpose(1, 2)).to(ctx.dts[0]) if ctx.needs_input_grad[0] else None
+        db = _mm(a16.transpose(1, 2), dy16).to(ctx.dts[1]) if ctx.needs_input_grad[1] else None
         return da, db
 
 

@@ -14,6 +14,7 @@ import os
 import torch
 
 from .. import _lib as L
+from ..linear import rows_wgrad, wgrad_rows_bf16
 
 _probe = None   # measurement hook (bench.py --workload decode): .wrap(name, flops, launch)
 
@@ -148,27 +149,6 @@ class DecoderWeights(object):
 # Training: the forward is the same single launch (ococc_occ_mlp_train_fwd_bf16 also leaves z, the row statistics and
 # y of every layer), the backward is the chain the separate operators ran -- LayerNorm backward kernels with the
 # dropout masks regenerated from (threshold, seed), library GEMMs for dX and dW -- issued from one autograd node.
-def wgrad_rows_bf16(dz, y, slices=32):
-    """dz^T y -> f32 [n, k] for bf16 dz [M, n], y [M, k] with M in the 1e5..1e6: as ONE GEMM the library runs the
-    [n, k] output as a few dozen macro tiles over a contraction of M (1024 x 1024 at 1 M rows: 4.1 ms, 0.54 PFLOP/s; 1024 x
-    512: 3.4 ms) -- as a batched GEMM over row slices with f32 outputs, summed, 2.05 and 1.08 ms (tools/probe/
-    dec_gemm_bench.py), and the partial sums are not rounded to bf16."""
-    M, n = dz.shape
-    per = M // slices
-    if per < 512 or y.shape[1] < 16:
-        return (dz.t() @ y).float()
-    if n < 16:   # (the head's 1-wide gradient: as it is, the batched form takes a path that costs 11 ms of HOST time per call;
-        wide = torch.zeros((M, 16), dtype=dz.dtype, device=dz.device)   # padded to 16 columns it is the fast one -- 1.4 ms
-        wide[:, :n] = dz                                               # less per 64-tracklet step than one skinny GEMM)
-        return wgrad_rows_bf16(wide, y, slices)[:n]
-    main = per * slices
-    out = torch.bmm(dz[:main].view(slices, per, dz.shape[1]).transpose(1, 2), y[:main].view(slices, per, y.shape[1]),
-                    out_dtype=torch.float32).sum(0)
-    if main < M:
-        out = out + torch.mm(dz[main:].t(), y[main:], out_dtype=torch.float32)
-    return out
-
-
 # The backward stays this operator chain: two one-launch backward kernels ('fused' on parked activations, 'recompute' on
 # nothing but the inputs) were measured slower everywhere and removed -- EXPERIMENTS.md, "why the one-launch decoder backward loses".
 # bench.py reads this to describe what the training forward stores: False = writes z / row statistics / y of every layer.
@@ -211,7 +191,6 @@ class _OccMlpTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogit):
-        from ..linear import sliced_wgrad
         from ..norm import layernorm_act_backward
         t = ctx.saved_tensors
         pe, idx, w_pe, w1, w2, head_w = t[:6]
@@ -240,7 +219,7 @@ class _OccMlpTrain(torch.autograd.Function):
                 dz0 = dz.float()
         # first layer: z0 = pe W_pe^T + roi_part[idx]
         pe32 = pe[:, :w_pe.shape[1]].float()
-        dws[0] = sliced_wgrad(dz0, pe32).to(w_pe.dtype)
+        dws[0] = rows_wgrad(dz0, pe32).to(w_pe.dtype)
         d_roi = torch.empty((K, dz0.shape[1]), dtype=torch.float32, device=dev)
         L.check(L.lib.ococc_segment_reduce_f32(L.ptr(dz0), L.ptr(idx), M, dz0.shape[1], 0, None, L.ptr(d_roi), None, K,
                                                L.stream()), 'occ_mlp_train_bwd: roi_part')

@@ -13,7 +13,7 @@ import torch
 from . import _deferred
 from . import _lib as L
 from . import norm as _norm  # noqa: F401 (registers the 'ln' flusher of _deferred)
-from .linear import TALL_ROWS, sliced_wgrad
+from .linear import POINT_TALL_ROWS, rows_wgrad
 
 ACT = {None: 0, 'none': 0, 'gelu': 1, 'relu': 2}
 
@@ -239,7 +239,7 @@ def weight_grad(weight, dz, xcat):
     rows, n = dz.shape
     k = xcat.shape[1]
     if not WGRAD_KERNEL or rows == 0 or (n * k) % 2:
-        return (sliced_wgrad(dz, xcat) if rows >= 4096 else dz.t() @ xcat).to(weight.dtype)
+        return (rows_wgrad(dz, xcat) if rows >= POINT_TALL_ROWS else dz.t() @ xcat).to(weight.dtype)
     slices = int(L.lib.ococc_point_mlp_wgrad_slices(rows))
     partial = torch.empty((slices, n, k), dtype=torch.float32, device=dz.device)
     L.check(L.lib.ococc_point_mlp_wgrad_f32(dz.data_ptr(), xcat.data_ptr(), rows, n, k, partial.data_ptr(), L.stream()),

@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from .. import _lib as L
+from ..linear import mm_f32, rows_wgrad
 from ..norm import layer_norm_act
 from ..registry import BACKBONES, MIDDLE_ENCODERS, build_conv_layer, build_norm_layer
 from .sst_ops import (LazyWindowDict, flat2window_v2, get_flat2win_inds_v2, get_inner_win_inds, get_window_coors,
@@ -406,6 +407,7 @@ class _BigWindowBlock(torch.autograd.Function):
         lses, rest = t[8:8 + n], t[8 + n:]
         E = xb.shape[1]
         r16 = lambda v: v.to(torch.bfloat16)
+        mm = lambda a, b: mm_f32(a.contiguous(), b.contiguous())   # (the transposed operands are copied: plain row-major GEMMs)
         # LayerNorm backward on the f32 statistics of the stored (bf16) sums
         z = z1.float()
         mean = z.mean(1, keepdim=True)
@@ -417,8 +419,8 @@ class _BigWindowBlock(torch.autograd.Function):
         dz1 = (dg - dg.mean(1, keepdim=True) - xh * (dg * xh).mean(1, keepdim=True)) * rstd
         g_gamma, g_beta = (dy * xh).sum(0), dy.sum(0)
         dz1r = r16(dz1)                                             # operand of the out-projection's two products
-        do = _mm_f32(dz1r, wo16)
-        g_wo = _mm_f32(dz1r.t(), o)
+        do = mm(dz1r, wo16)
+        g_wo = mm(dz1r.t(), o)
         g_bo = dz1r.float().sum(0)
         if ctx.spread is not None:
             rows, qkv_w, o_w = ctx.spread
@@ -426,32 +428,15 @@ class _BigWindowBlock(torch.autograd.Function):
             dqkv = _attn_flat_backward(qkv_w, o_w, do_w, lses, rest, ctx.meta).index_select(0, rows)
         else:
             dqkv = _attn_flat_backward(qkv, o, r16(do), lses, rest, ctx.meta)
-        dx = r16(_mm_f32(dqkv, w16) + dz1)
-        g_w = torch.cat([_mm_f32(dqkv[:, :2 * E].t(), xp), _mm_f32(dqkv[:, 2 * E:].t(), xb)], 0)
+        dx = r16(mm(dqkv, w16) + dz1)
+        g_w = torch.cat([mm(dqkv[:, :2 * E].t(), xp), mm(dqkv[:, 2 * E:].t(), xb)], 0)
         g_b = dqkv.float().sum(0)
         return (dx, None, g_w, g_b, g_wo, g_bo, g_gamma, g_beta, None, None, None, None, None) + (None,) * (4 * n)
 
 
-try:   # bf16 operands, f32 result without a rounding in between (torch >= 2.8); else f32 copies of the operands
-    torch.mm(torch.zeros(1, 1, dtype=torch.bfloat16), torch.zeros(1, 1, dtype=torch.bfloat16), out_dtype=torch.float32)
-    _MM_OUT_DTYPE = True
-except (TypeError, RuntimeError):
-    _MM_OUT_DTYPE = False
-
-
-def _mm_f32(a, b):
-    """a @ b for bf16 operands with f32 accumulation AND an f32 result"""
-    if _MM_OUT_DTYPE and a.is_cuda:
-        return torch.mm(a.contiguous(), b.contiguous(), out_dtype=torch.float32)
-    return a.float() @ b.float()
-
-
 class _TokenLinear(torch.autograd.Function):
-    """y = x W^T + b over ~1e5..1e6 token rows with a tiny [out, in] weight.  The weight gradient
-    dW = dY^T X contracts over the token dimension; the BLAS heuristics give that one output tile
-    per 64x128 of dW (a dozen workgroups on a 256-CU part, ~0.6 ms).  Here the token dimension is cut
-    into 64 slabs, a batched GEMM produces 64 partial dW (thousands of tiles), and the partials are
-    summed in f32."""
+    """y = x W^T + b over ~1e5..1e6 token rows with a tiny [out, in] weight; the weight gradient dW = dY^T X is
+    linear.rows_wgrad over 64 slabs of the token dimension."""
     SLABS = 64
 
     @staticmethod
@@ -465,15 +450,7 @@ class _TokenLinear(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dy = dy.contiguous()
         dx = dy @ w if ctx.needs_input_grad[0] else None
-        n, s = x.shape[0], _TokenLinear.SLABS
-        m = (n // s) * s
-        dw = None
-        if m:
-            part = torch.bmm(dy[:m].view(s, m // s, -1).transpose(1, 2), x[:m].view(s, m // s, -1))
-            dw = part.float().sum(0)
-        if m < n:
-            tail = (dy[m:].t() @ x[m:]).float()
-            dw = tail if dw is None else dw + tail
+        dw = rows_wgrad(dy, x, slices=_TokenLinear.SLABS)
         db = dy.sum(0, dtype=torch.float32).to(dy.dtype) if ctx.has_bias else None  # f32 accumulation, no f32 copy
         return dx, dw.to(w.dtype), db
 
@@ -506,16 +483,7 @@ class _QkvProjection(torch.autograd.Function):
             d_xp = g_qk @ w[:2 * E]
             dpos = d_xp if ctx.needs_input_grad[1] else None
             dx = torch.addmm(d_xp, g_v, w[2 * E:]) if ctx.needs_input_grad[0] else None
-        n, s = x.shape[0], _TokenLinear.SLABS
-        m = (n // s) * s
-        dw = torch.zeros((3 * E, E), dtype=torch.float32, device=x.device)
-        if m:
-            gs = g[:m].view(s, m // s, 3 * E)
-            dw[:2 * E] += torch.bmm(gs[:, :, :2 * E].transpose(1, 2), xp[:m].view(s, m // s, E)).float().sum(0)
-            dw[2 * E:] += torch.bmm(gs[:, :, 2 * E:].transpose(1, 2), x[:m].view(s, m // s, E)).float().sum(0)
-        if m < n:
-            dw[:2 * E] += (g_qk[m:].t() @ xp[m:]).float()
-            dw[2 * E:] += (g_v[m:].t() @ x[m:]).float()
+        dw = torch.cat([rows_wgrad(g_qk, xp, slices=_TokenLinear.SLABS), rows_wgrad(g_v, x, slices=_TokenLinear.SLABS)], 0)
         db = g.sum(0, dtype=torch.float32).to(g.dtype)
         return dx, dpos, dw.to(w.dtype), db
 

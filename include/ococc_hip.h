@@ -118,7 +118,9 @@ int ococc_grid_unique_i32(const int32_t* coors, int64_t n, int32_t ndim, const i
  * feats [n, c] f32, inv [n] int32 in [-1, num_segments) (-1 rows ignored),
  * out [num_segments, c] f32.  counts [num_segments] int32 is required for
  * MEAN (divide) and optional otherwise (segments with count 0 -> 0 for MAX,
- * as torch_scatter does).  arg [num_segments, c] int32 (MAX only, may be
+ * as torch_scatter does; MAX with counts == NULL leaves them at -inf: nothing
+ * tells an empty segment from a written one).  SUM gives empty segments 0
+ * either way.  arg [num_segments, c] int32 (MAX only, may be
  * NULL): smallest row index attaining the max -- the tie rule of
  * max_reduce_traceback_scatter_idx_kernel (scatter_points_cuda.cu:136-160).
  * ------------------------------------------------------------------------ */

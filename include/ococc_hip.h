@@ -732,6 +732,40 @@ int ococc_occ_select_fill(const float* logits, int64_t n, const int64_t* start, 
                           int64_t roi_stride, const float* cos_yaw, const float* sin_yaw, const float* roi_value,
                           int32_t cols, float* out, int64_t n_out, ococc_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * ground-truth occupancy export (csrc/gt_occ_crop.hip): the occupied label cells of one object, moved into the LiDAR
+ * frame of every frame that has a GT box and cropped to that frame's proposal box, behind bbox.crop_gt_occ_packed and
+ * TrackletRoIHeadOCC.save_gt_occ_from_tracklet.  Replaces the save_gt_occ=True branch of save_occ_from_tracklet
+ *   (mmdet3d/models/roi_heads/tracklet_roi_head_occ.py:634-702: the [N, K, 3] repeat, rotation_3d_in_axis, the three
+ *   in-place adds of :661-670, points_in_boxes_gpu and the boolean index per frame of :681-689) and check_pt_in_box3d
+ *   (mmdet3d/ops/roiaware_pool3d/src/points_in_boxes_cuda.cu:24-49).
+ * cells [K, 3] f32: gravity centres in the GT box frame.  gt_boxes / roi_boxes: N rows of gt_stride / roi_stride >= 7
+ * floats (x, y, z_bottom, w, l, h, yaw).  cos_gt / sin_gt [N]: the caller's cos / sin of the GT yaw; cos_roi / sin_roi
+ * [N]: of float((double)roi_yaw + pi / 2), the .cu's rot_angle.  No trigonometric function is evaluated here.
+ * Pair n * K + k is (frame n, cell k).  Per pair, every operation rounded to f32 on its own (no fused multiply-add):
+ *   x' = (x c + y s) + gt_x, y' = (-x s + y c) + gt_y, z' = (z + gt_z) + gt_h / 2;
+ *   kept unless |z' - (roi_z + roi_h / 2)| > roi_h / 2 (a cell on the top or bottom face is kept), and if
+ *   -l / 2 < dx cosa + dy (-sina) < l / 2 and -w / 2 < dx sina + dy cosa < w / 2 with (dx, dy) = (x' - roi_x, y' - roi_y),
+ *   all four strict (a cell on a side face is dropped).
+ * Tiles: 1024 consecutive pairs of one frame, ococc_gt_occ_crop_tiles(N, K) = N * ceil(K / 1024) of them (host
+ * arithmetic; every frame has K cells, so tile t is frame t / ceil(K / 1024) and no table is read).  One wave per tile,
+ * one ballot per 64 pairs.
+ * ococc_gt_occ_crop_count writes tile_counts [tiles] i32 and frame_counts [N] i64 (zeroed here; integer atomics only).
+ * ococc_gt_occ_crop_fill: given tile_scan [tiles] i64, the exclusive prefix of tile_counts, writes the kept cells in
+ *   frame order and ascending cell order inside a frame to out [n_out, 4] f32 (16-byte aligned; n_out = sum of
+ *   frame_counts, rows past it are not written): x', y', z' recomputed, and value[n] (1 when value is NULL).
+ * N == 0 or K == 0 is an empty result, not an error.  No float atomics: the same input gives the same bytes.
+ * ------------------------------------------------------------------------ */
+int64_t ococc_gt_occ_crop_tiles(int64_t N, int64_t K);
+int ococc_gt_occ_crop_count(const float* cells, int64_t K, const float* gt_boxes, int64_t gt_stride,
+                            const float* roi_boxes, int64_t roi_stride, int64_t N, const float* cos_gt,
+                            const float* sin_gt, const float* cos_roi, const float* sin_roi, int32_t* tile_counts,
+                            int64_t tiles, int64_t* frame_counts, ococc_stream_t stream);
+int ococc_gt_occ_crop_fill(const float* cells, int64_t K, const float* gt_boxes, int64_t gt_stride,
+                           const float* roi_boxes, int64_t roi_stride, int64_t N, const float* cos_gt,
+                           const float* sin_gt, const float* cos_roi, const float* sin_roi, const int64_t* tile_scan,
+                           int64_t tiles, const float* value, float* out, int64_t n_out, ococc_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * A12 glue, one launch each (f32; the element-wise chains they replace were 12-35 launches of a few hundred elements):
  * ococc_rotate_z_f32: rotation_3d_in_axis(points [n, m, 3], angles [n], axis=2)

@@ -1,9 +1,15 @@
 """Box helpers on the hot path -- host mirror of rotation_3d_in_axis
 (mmdet3d/core/bbox/structures/utils.py:21-61) and DeltaXYZWLHRBBoxCoder
 (mmdet3d/core/bbox/coders/delta_xyzwhlr_bbox_coder.py:8-90).  Tiny elementwise math."""
+import math
+import os
+
 import torch
 
 from .registry import BBOX_CODERS
+
+# the crop of the ground-truth occupancy export: csrc/gt_occ_crop.hip (0: the ATen chain of crop_gt_occ_aten)
+GT_OCC_KERNEL = os.environ.get('OCOCC_GT_OCC_KERNEL', '1') != '0'
 
 
 def limit_period(val, offset=0.5, period=3.141592653589793):
@@ -64,6 +70,96 @@ def points_box_to_box(xyz, from_boxes, to_boxes):
     xyz -= to_boxes[..., None, :3]
     xyz[..., 2] -= to_boxes[:, None, 5] / 2
     return rotation_3d_in_axis(xyz, -(to_boxes[:, 6]), axis=2)
+
+
+def gt_occ_crop_trig(gt_boxes, roi_boxes):
+    """(cos, sin) of the GT yaw and of the RoI's ``rot_angle`` as check_pt_in_box3d takes it
+    (mmdet3d/ops/roiaware_pool3d/src/points_in_boxes_cuda.cu:24-32): float(rz + pi / 2), the sum in double."""
+    ang = (roi_boxes[:, 6].double() + math.pi / 2).float()
+    return torch.cos(gt_boxes[:, 6]), torch.sin(gt_boxes[:, 6]), torch.cos(ang), torch.sin(ang)
+
+
+def _gt_occ_points_mask(cells, gt_boxes, roi_boxes, trig=None):
+    """points [N, K, 3] and inside mask [N, K] of crop_gt_occ_aten: element-wise products and sums only, so every
+    rounding is defined (an einsum's is not) and is what csrc/gt_occ_crop.hip does"""
+    cg, sg, ca, sa = (t[:, None] for t in (trig if trig is not None else gt_occ_crop_trig(gt_boxes, roi_boxes)))
+    x, y, z = cells[None, :, 0], cells[None, :, 1], cells[None, :, 2]
+    g, r = gt_boxes[:, None, :], roi_boxes[:, None, :]
+    # tracklet_roi_head_occ.py:665-670: rotation_3d_in_axis(axis=2) (the transposed matrix), + centre, z + h / 2
+    px = (x * cg + y * sg) + g[..., 0]
+    py = (-x * sg + y * cg) + g[..., 1]
+    pz = (z + g[..., 2]) + g[..., 5] / 2
+    # check_pt_in_box3d: |z - cz| > h / 2 is outside (the faces are inside); the four side comparisons are strict
+    hh = r[..., 5] / 2
+    dz, dx, dy = pz - (r[..., 2] + hh), px - r[..., 0], py - r[..., 1]
+    lx = dx * ca + dy * (-sa)
+    ly = dx * sa + dy * ca
+    hl, hw = r[..., 4] / 2, r[..., 3] / 2
+    inside = ~(dz.abs() > hh) & (lx > -hl) & (lx < hl) & (ly > -hw) & (ly < hw)
+    return torch.stack([px, py, pz], -1), inside
+
+
+def crop_gt_occ_aten(cells, gt_boxes, roi_boxes, trig=None):
+    """The ground-truth branch of the reference's save_occ_from_tracklet, operator by operator
+    (tracklet_roi_head_occ.py:661-689): cells [K, 3] (occupied label cells, gravity centres in the GT box frame) are
+    moved into the LiDAR frame of each of the N frames by gt_boxes [N, >= 7] (x, y, z_bottom, w, l, h, yaw) and those
+    inside roi_boxes[n] (points_in_boxes_gpu, i.e. check_pt_in_box3d) are kept: a list of N tensors [m_n, 3], cell order
+    kept.  ``trig``: (cos_gt, sin_gt, cos_roi, sin_roi) [N] each instead of gt_occ_crop_trig's.  A boolean index, i.e. a
+    host synchronisation, per frame: the comparator of crop_gt_occ_packed, and what CPU tensors and
+    OCOCC_GT_OCC_KERNEL=0 run."""
+    cells, gt_boxes, roi_boxes = cells.float().reshape(-1, 3), gt_boxes.float(), roi_boxes.float()
+    pts, inside = _gt_occ_points_mask(cells, gt_boxes, roi_boxes, trig)
+    return [pts[n][inside[n]] for n in range(gt_boxes.size(0))]
+
+
+def gt_occ_crop_kernels(cells, gt_boxes, roi_boxes, cos_gt, sin_gt, cos_roi, sin_roi, values=None):
+    """csrc/gt_occ_crop.hip with the cos / sin arrays passed in: (packed [M, 4] f32 on the device, counts per frame as a
+    list of int).  One count launch, one cumsum, one fill launch; the one read-back is the per-frame counts."""
+    from . import _lib as L
+    L.require_device(cells, gt_boxes, roi_boxes, cos_gt, sin_gt, cos_roi, sin_roi, values)
+    if cells.dtype != torch.float32 or cells.dim() != 2 or cells.size(1) != 3:
+        raise L.OcoccError(f'gt_occ_crop: cells {tuple(cells.shape)} {cells.dtype} are not f32 [K, 3]')
+    N, K, dev = gt_boxes.size(0), cells.size(0), cells.device
+    if gt_boxes.dim() != 2 or roi_boxes.dim() != 2 or roi_boxes.size(0) != N or gt_boxes.size(1) < 7 or roi_boxes.size(1) < 7:
+        raise L.OcoccError(f'gt_occ_crop: boxes {tuple(gt_boxes.shape)} / {tuple(roi_boxes.shape)} are not [N, >= 7] both')
+    trig = [cos_gt, sin_gt, cos_roi, sin_roi] + ([values] if values is not None else [])
+    if any(t.dtype != torch.float32 or t.numel() != N for t in trig):
+        raise L.OcoccError(f'gt_occ_crop: cos / sin / values are not f32 [{N}] each')
+    if N == 0 or K == 0:
+        return L.empty((0, 4), torch.float32, dev), [0] * N
+    cells = cells.contiguous()
+    (gb, ldg), (rb, ldr) = _rows7(gt_boxes), _rows7(roi_boxes)
+    trig = [t.contiguous().view(-1) for t in trig]
+    tiles = int(L.lib.ococc_gt_occ_crop_tiles(N, K))
+    tile_counts = L.empty((tiles,), torch.int32, dev)
+    frame_counts = L.empty((N,), torch.int64, dev)
+    L.check(L.lib.ococc_gt_occ_crop_count(L.ptr(cells), K, L.ptr(gb), ldg, L.ptr(rb), ldr, N, *(L.ptr(t) for t in trig[:4]),
+                                          L.ptr(tile_counts), tiles, L.ptr(frame_counts), L.stream()), 'gt_occ_crop_count')
+    scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts   # exclusive: where a tile's cells start
+    counts = [int(v) for v in frame_counts.tolist()]                       # the one read-back
+    M = sum(counts)
+    out = L.empty((M, 4), torch.float32, dev)
+    L.check(L.lib.ococc_gt_occ_crop_fill(L.ptr(cells), K, L.ptr(gb), ldg, L.ptr(rb), ldr, N, *(L.ptr(t) for t in trig[:4]),
+                                         L.ptr(scan), tiles, L.ptr(trig[4]) if values is not None else None, L.ptr(out), M,
+                                         L.stream()), 'gt_occ_crop_fill')
+    return out, counts
+
+
+def crop_gt_occ_packed(cells, gt_boxes, roi_boxes, values=None):
+    """crop_gt_occ_aten as ONE array: (packed [M, 4] f32: the kept cells of frame 0, then of frame 1, ... in the LiDAR
+    frame, ``values[n]`` (1 without values) in column 3; counts per frame as a list of int), bit for bit
+    ``torch.cat(crop_gt_occ_aten(...))``.  On the kernels of csrc/gt_occ_crop.hip: one read-back (the counts); the
+    device-to-host copy of the packed array is the caller's.  CPU tensors and OCOCC_GT_OCC_KERNEL=0 take the ATen chain."""
+    cells, gt_boxes, roi_boxes = cells.float().reshape(-1, 3), gt_boxes.float(), roi_boxes.float()
+    if values is not None:
+        values = values.to(device=cells.device, dtype=torch.float32).view(-1)
+    if GT_OCC_KERNEL and cells.is_cuda:
+        return gt_occ_crop_kernels(cells, gt_boxes, roi_boxes, *gt_occ_crop_trig(gt_boxes, roi_boxes), values=values)
+    parts = crop_gt_occ_aten(cells, gt_boxes, roi_boxes)
+    counts = [int(p.size(0)) for p in parts]
+    col = [p.new_ones((p.size(0), 1)) if values is None else values[n].expand(p.size(0), 1) for n, p in enumerate(parts)]
+    packed = torch.cat([torch.cat([p, c], 1) for p, c in zip(parts, col)], 0) if parts else cells.new_zeros((0, 4))
+    return packed, counts
 
 
 def box_corners(boxes):

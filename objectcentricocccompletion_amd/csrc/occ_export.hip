@@ -32,9 +32,9 @@
 
 namespace {
 
-constexpr int kRounds = 16;
-constexpr int kTile = 64 * kRounds;   // 1024 cells per wave
-constexpr int kWaves = 4;
+constexpr int kRounds = kOccCompactRounds;
+constexpr int kTile = kOccCompactTile;   // 1024 cells per wave
+constexpr int kWaves = kOccCompactWaves;
 constexpr int kBlock = 64 * kWaves;
 constexpr int kLdsStart = 2048;       // entries of start kept in LDS by the cells kernel
 
@@ -163,8 +163,7 @@ occ_select_kernel(const float* __restrict__ logits, int64_t n, const int64_t* __
         Cell c = cell_centre((uint32_t)(cell - r0), a.sizes + r * 3, a.dims + r * 3, a.voxel_size);
         if (a.rois) {
           // OccDecoder._to_lidar: x c + y s, -x s + y c, z; + centre; z + h / 2
-          const float xc = c.x * cy, ys = c.y * sy, xs = -c.x * sy, yc = c.y * cy;
-          c.x = (xc + ys) + bx, c.y = (xs + yc) + by, c.z = (c.z + bz) + hh;
+          ococc_box_to_lidar(c.x, c.y, c.z, cy, sy, bx, by, bz, hh);
         }
         float* o = a.out + pos * a.cols;
         if (a.cols == 4) {

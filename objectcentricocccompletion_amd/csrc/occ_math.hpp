@@ -1,4 +1,4 @@
-// Device arithmetic shared by the occupancy kernels (occ_iou_count.hip, occ_export.hip), written so that a result is
+// Device arithmetic shared by the occupancy kernels (occ_iou_count.hip, occ_export.hip, gt_occ_crop.hip), written so that a result is
 // the f32 value the ATen chain it replaces gives: every operation rounded on its own, no fused multiply-add.
 #pragma once
 #include "common.hpp"
@@ -19,4 +19,20 @@ __device__ __forceinline__ float ococc_cell_centre(int c, float size, float voxe
   const float at = (float)c * voxel_size;
   const float lo = at + (-size / 2.0f);
   return lo + voxel_size / 2.0f;
+}
+
+// The tiles of the order-preserving compactions (occ_export.hip, gt_occ_crop.hip): one wave per tile of 16 rounds of 64
+// consecutive elements, one ballot per round; kOccCompactWaves tiles per block.
+constexpr int kOccCompactRounds = 16;
+constexpr int kOccCompactTile = 64 * kOccCompactRounds;   // 1024 elements per wave
+constexpr int kOccCompactWaves = 4;
+
+// A point of a box's gravity-centred frame in the LiDAR frame (OccDecoder._to_lidar, occ_base.py:220-230, 330-336;
+// tracklet_roi_head_occ.py:665-670): rotation_3d_in_axis(axis=2) with the transposed matrix, x c + y s and -x s + y c,
+// then + the bottom centre (bx, by, bz), then z + half_h; (c, s) the cos / sin of the yaw
+__device__ __forceinline__ void ococc_box_to_lidar(float& x, float& y, float& z, float c, float s, float bx, float by,
+                                                   float bz, float half_h) {
+#pragma clang fp contract(off)
+  const float xc = x * c, ys = y * s, xs = -x * s, yc = y * c;
+  x = (xc + ys) + bx, y = (xs + yc) + by, z = (z + bz) + half_h;
 }

@@ -50,6 +50,17 @@ def check_save_occ_cfg(test_cfg):
         raise ValueError('test_cfg.save_occ needs test_cfg.occ_save_root, the directory the files go to')
 
 
+def check_save_gt_occ_cfg(test_cfg):
+    """test_cfg.save_gt_occ (export the annotated occupancy, cropped to the proposals, from simple_test) needs
+    gt_occ_save_root and excludes test_cfg.tta, as check_save_occ_cfg."""
+    if not test_cfg or not test_cfg.get('save_gt_occ', False):
+        return
+    if test_cfg.get('tta', None) is not None:
+        raise ValueError('test_cfg.save_gt_occ with test_cfg.tta: the augmented frames are not the frames to export')
+    if not test_cfg.get('gt_occ_save_root', None):
+        raise ValueError('test_cfg.save_gt_occ needs test_cfg.gt_occ_save_root, the directory the files go to')
+
+
 @HEADS.register_module()
 class TrackletRoIHeadOCC(nn.Module):
 
@@ -58,6 +69,7 @@ class TrackletRoIHeadOCC(nn.Module):
         super().__init__()
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
         check_save_occ_cfg(test_cfg)
+        check_save_gt_occ_cfg(test_cfg)
         self.general_cfg, self.num_classes = general_cfg, num_classes
         self.with_roi_scores = general_cfg.get('with_roi_scores', False)
         self.with_roi_corners = general_cfg.get('with_roi_corners', False)
@@ -341,6 +353,9 @@ class TrackletRoIHeadOCC(nn.Module):
             # (the reference defines save_occ_from_tracklet and never calls it; test_cfg.save_occ is this package's key)
             check_save_occ_cfg(self.test_cfg)   # (again: the config may have changed since the head was built)
             self.save_occ_from_tracklet(tracklet_list, res)
+        if self.test_cfg.get('save_gt_occ', False) and gt_rois is not None:
+            check_save_gt_occ_cfg(self.test_cfg)
+            self.save_gt_occ_from_tracklet(tracklet_list, res, gt_rois, gt_occ_list)
         return [out]
 
     @torch.no_grad()
@@ -351,7 +366,8 @@ class TrackletRoIHeadOCC(nn.Module):
         centres of get_occ(fused features, transform=True) and the frame's box score (``gt_score[i]`` when given) in
         every row.  Frames under test_cfg.min_evaluate_length are not written, nor (test_cfg.filter_empty_roi) frames
         whose RoI had no points.  One packed array per tracklet (bbox_head.get_occ_packed), one device-to-host copy,
-        sliced on the host (occ_export.write_tracklet_occ).  Returns the paths written."""
+        sliced on the host (occ_export.write_tracklet_occ).  Returns the paths written.  The ground-truth branch
+        (save_gt_occ=True) is save_gt_occ_from_tracklet, a method of its own."""
         from . import occ_export
         assert len(tracklet_list) == 1, 'only support batch size 1'
         if save_gt_occ:
@@ -376,6 +392,49 @@ class TrackletRoIHeadOCC(nn.Module):
                     print(f'empty roi {i} in {tracklet.segment_name} at {tracklet.ts_list[i]}')
                     skip.add(i)
         return occ_export.write_tracklet_occ(self.test_cfg['occ_save_root'], tracklet.segment_name, tracklet.ts_list,
+                                             tracklet.type, tracklet.id, packed.cpu().numpy(), counts, skip)
+
+    @torch.no_grad()
+    def save_gt_occ_from_tracklet(self, tracklet_list, bbox_results, gt_rois, gt_occ_list, root=None):
+        """The annotated occupancy of the matched GT track as files, cropped to the proposal boxes (the save_gt_occ=True
+        branch of the reference's save_occ_from_tracklet, tracklet_roi_head_occ.py:634-702): for every frame of the
+        proposal tracklet that has a GT box (``gt_rois[:, 0] == 1``; gt_rois as get_gt_rois returns it, aligned to the
+        proposal's ts_list) the occupied label cells ``gt_occ[..., :3][gt_occ[..., 3] == 1]`` are moved into that
+        frame's LiDAR frame by the GT box and those inside the proposal box are written to
+        ``<test_cfg.gt_occ_save_root>/<segment>/<timestamp>/<type>_<id>.bin``, float32 [n, 4] with score 1, under the
+        proposal's segment, type and id.  Nothing is written (``[]``) without labels, without a matched frame or without
+        an occupied cell.  test_cfg.min_evaluate_length and filter_empty_roi apply to the frame's index in the PROPOSAL
+        tracklet (the reference indexes its filtered list against the unfiltered mask: not reproduced).  One packed
+        array per tracklet (bbox.crop_gt_occ_packed), one device-to-host copy.  Returns the paths written."""
+        from . import occ_export
+        from .bbox import crop_gt_occ_packed
+        from .tracklet import host_index
+        assert len(tracklet_list) == 1, 'only support batch size 1'
+        tracklet = tracklet_list[0]
+        if gt_rois is None or gt_occ_list is None or gt_occ_list[0] is None:
+            return []
+        assert gt_rois.size(0) == len(tracklet), f'{gt_rois.size(0)} gt_rois for {len(tracklet)} frames'
+        frames = [i for i, m in enumerate((gt_rois[:, 0] == 1).tolist()) if m]
+        if not frames:
+            return []
+        occ = gt_occ_list[0]
+        cells = occ[..., :3][occ[..., 3] == 1].float()
+        if cells.size(0) == 0:
+            return []
+        rois, _, _, _ = self.tracklets2rois([tracklet])
+        dev = rois.device
+        idx = host_index(frames, dev)
+        packed, counts = crop_gt_occ_packed(cells.to(dev), gt_rois.to(dev)[idx][:, 1:8], rois[idx][:, 1:8])
+        low = self.test_cfg.get('min_evaluate_length', 0)
+        skip = {k for k, i in enumerate(frames) if i < low}
+        if self.test_cfg.get('filter_empty_roi', False):
+            nonempty = bbox_results['nonempty_roi_mask'].tolist()
+            for k, i in enumerate(frames):
+                if k not in skip and not nonempty[i]:
+                    print(f'empty roi {i} in {tracklet.segment_name} at {tracklet.ts_list[i]}')
+                    skip.add(k)
+        root = root if root is not None else self.test_cfg['gt_occ_save_root']
+        return occ_export.write_tracklet_occ(root, tracklet.segment_name, [tracklet.ts_list[i] for i in frames],
                                              tracklet.type, tracklet.id, packed.cpu().numpy(), counts, skip)
 
     @staticmethod

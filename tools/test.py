@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Test / evaluation entry point with the CLI of the reference's tools/test.py (:23-87):
-    python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--save-occ DIR] [--eval iou waymo waymo_native] [--matcher {score_first,hungarian}] [--format-only]
+    python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--save-occ DIR] [--save-gt-occ DIR] [--eval iou waymo waymo_native] [--matcher {score_first,hungarian}] [--format-only]
                          [--eval-options k=v ...] [--cfg-options k=v ...] [--launcher {none,pytorch}]
                          [--tmpdir DIR] [--gpu-collect] [--local_rank N]
 The test dataset is the config's data.test (the reference's data/waymo layout); with --data-root DIR it reads the tree
@@ -63,6 +63,10 @@ def parse_args(argv=None):
                     help='export the completed occupancy: DIR/<segment>/<timestamp>/<type>_<id>.bin per object and frame, '
                     'float32 [n, 4] (sets test_cfg.occ_save_root and test_cfg.save_occ; read back with '
                     'objectcentricocccompletion_amd.occ_export.load_frame_occ)')
+    ap.add_argument('--save-gt-occ', metavar='DIR', default=None,
+                    help='export the annotated occupancy of the matched ground-truth tracks, cropped to the proposal boxes: '
+                    'the same layout and format under DIR, score 1, frames with a GT box only (sets '
+                    'test_cfg.gt_occ_save_root and test_cfg.save_gt_occ)')
     args = ap.parse_args(argv)
     if 'LOCAL_RANK' not in os.environ:
         os.environ['LOCAL_RANK'] = str(args.local_rank)
@@ -140,9 +144,9 @@ def run_shard(model, dataset, lo, hi, device, seed=0):
 
 def main(argv=None):
     args = parse_args(argv)
-    assert args.out or args.eval or args.format_only or args.show or args.show_dir or args.save_occ, (
+    assert args.out or args.eval or args.format_only or args.show or args.show_dir or args.save_occ or args.save_gt_occ, (
         'Please specify at least one operation (save/eval/format/show the results) with the argument "--out", "--eval", '
-        '"--format-only", "--save-occ", "--show" or "--show-dir"')
+        '"--format-only", "--save-occ", "--save-gt-occ", "--show" or "--show-dir"')
     if args.eval and args.format_only:
         raise ValueError('--eval and --format_only cannot be both specified')
     if args.out is not None and not args.out.endswith(('.pkl', '.pickle')):
@@ -160,6 +164,9 @@ def main(argv=None):
         # (ranks hold disjoint tracklets, hence disjoint files: nothing to coordinate beyond makedirs(exist_ok=True))
         os.makedirs(args.save_occ, exist_ok=True)
         config.merge_from_dict(cfg, {'model.test_cfg.occ_save_root': args.save_occ, 'model.test_cfg.save_occ': True})
+    if args.save_gt_occ:
+        os.makedirs(args.save_gt_occ, exist_ok=True)
+        config.merge_from_dict(cfg, {'model.test_cfg.gt_occ_save_root': args.save_gt_occ, 'model.test_cfg.save_gt_occ': True})
     rank, world, local_rank = init_dist(args.dist_backend) if args.launcher == 'pytorch' else (0, 1, 0)
     dev = torch.device('cuda', local_rank % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)

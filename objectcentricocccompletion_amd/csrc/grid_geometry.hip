@@ -22,12 +22,15 @@
 //                               writes the bitmap, its local prefix, the per-point codes and a [grids x slices x 28]
 //                               count table
 //   S  geometry_bases_kernel    exclusive prefix of that table (28 columns): global row bases and pair bases
-//   B  grid_emit_kernel         one workgroup per (grid, row slice) with the grid's bitmap back in LDS: voxel
-//                               coordinates, the global prefix words, the means of the point features (first arrival
-//                               plain-stores, later arrivals add with float atomics behind a workgroup barrier, the
-//                               owner of a shared row divides), the offset-major neighbour table, the 16-row block
-//                               masks, the reference-format pair lists in CPU-functor order, and the -1 / zero
-//                               padding rows of the fixed-capacity form.
+//   B  grid_emit_kernel         three roles by block index, none waiting for another.  ROW role, one workgroup per
+//                               (grid, row slice) with the grid's bitmap back in LDS: voxel coordinates, the global
+//                               prefix words, the offset-major neighbour table, the 16-row block masks, the
+//                               reference-format pair lists in CPU-functor order, the row order's records.  POINT
+//                               role, one workgroup per (grid, part = the slices of one workgroup of A) with the part's
+//                               bitmap words in LDS: inv, the point counts and the means of the point features (first
+//                               arrival plain-stores, later arrivals add with float atomics behind a workgroup barrier,
+//                               the owner of a shared row divides -- all points of a row meet in one workgroup).
+//                               PADDING role: the -1 / zero rows of the fixed-capacity form.
 // Nothing leaves the chip between the phases of a kernel except the outputs; the only global atomics are the float
 // adds of the 1.6 % of points that share a cell and the 32-bit ORs of the block masks.
 #include "common.hpp"
@@ -55,6 +58,11 @@ constexpr int kPadBlocks = 64;       // workgroups of kernel B that write the pa
 constexpr int kCols = 28;            // 27 kernel offsets + the voxel count
 constexpr int kMaxSlices = 16;
 constexpr int kCodesPerThread = 8;   // point codes a thread of kernel B fetches in one round
+// waves per SIMD kernel B is compiled for: the row and the point workgroups of the benchmark batch (64 grids x (12 + 4))
+// and the padding ones are 1088 workgroups on 256 CUs, resident together only at 5 workgroups of 4 waves per CU
+#ifndef OCOCC_GEO_EMIT_WAVES
+#define OCOCC_GEO_EMIT_WAVES 5
+#endif
 
 // workgroup barrier for data exchanged through LDS only: does not wait for the wave's global stores to land
 // (__syncthreads() does, with s_waitcnt vmcnt(0), which is what the places that hand GLOBAL data on need)
@@ -69,12 +77,6 @@ struct GeoParams {
   int32_t asplit;  // workgroups of kernel A per grid; each counts for spa = ceil(slices / asplit) consecutive slices
   int32_t spa;
 };
-
-__device__ __forceinline__ int32_t lds_rank(const uint32_t* bm, const uint32_t* pf, int32_t cell) {
-  const uint32_t w = bm[cell >> 5];
-  const uint32_t bit = 1u << (cell & 31);
-  return (w & bit) ? (int32_t)(pf[cell >> 5] + __popc(w & (bit - 1u))) : -1;
-}
 
 // exclusive popcount scan of `words` bitmap words held in LDS.  tmp: kWaves words
 __device__ void lds_popc_scan(const uint32_t* bm, uint32_t* pf, int words, uint32_t* tmp) {
@@ -352,27 +354,45 @@ __device__ __forceinline__ void put_feat_row(const float* __restrict__ src, floa
   }
 }
 
-// ---- B: one workgroup per (grid, row slice); the workgroups behind them write the padding rows -------------------
-__global__ void __launch_bounds__(kEmitThreads)
+// LDS of kernel B's two roles, at the start of the dynamic allocation with the role's bitmap and prefix words behind it:
+// one size per launch, the larger of the two (static arrays of both roles would add up instead)
+struct RowLds {
+  int32_t part[3][kEmitWaves][32];
+  uint32_t oh[kLocalBuckets + 3];
+  int32_t base[kCols];
+  int32_t wcnt[27][kEmitWaves];  // per round: valid entries per offset and wave, then their exclusive prefix
+  int32_t run[27 + 1];
+  int32_t cell[kEmitThreads];
+};
+struct PointLds {
+  int2 list[kCodesPerThread * kEmitThreads];    // (point - segment start, row) work items of one round
+  int32_t code[kCodesPerThread * kEmitThreads];  // the round's point codes (thread t owns slots j * 256 + t)
+  int32_t part[kEmitWaves];
+  int n, n2, pad0, pad1;
+};
+static_assert(sizeof(RowLds) % 16 == 0 && sizeof(PointLds) % 16 == 0, "the bitmap words behind the struct stay aligned");
+
+// ---- B: three roles by block index: one workgroup per (grid, row slice) for the rows, one per (grid, part of the
+// slices) for the points, and behind them the workgroups that write the padding rows ------------------------------
+__global__ void __launch_bounds__(kEmitThreads) __attribute__((amdgpu_waves_per_eu(OCOCC_GEO_EMIT_WAVES)))
 grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g, const uint32_t* __restrict__ bitmap,
                  const uint32_t* __restrict__ local_prefix, uint32_t* __restrict__ prefix_out,
                  int32_t* __restrict__ code_of, const int64_t* __restrict__ seg, const int32_t* __restrict__ bases,
                  const int32_t* __restrict__ totals, int32_t* __restrict__ inv, int32_t* __restrict__ out_coors,
                  int32_t* __restrict__ counts, float* __restrict__ out_f32, uint16_t* __restrict__ out_bf16, int64_t cap,
                  int32_t* __restrict__ nbr_t, uint32_t* __restrict__ blockmask, int32_t* __restrict__ pairs,
-                 int emit_blocks, uint32_t* __restrict__ order_hist, i32x4_t* __restrict__ order_rowrec,
+                 int emit_blocks, int point_blocks, uint32_t* __restrict__ order_hist, i32x4_t* __restrict__ order_rowrec,
                  const int32_t* __restrict__ count_table, const int32_t* __restrict__ part_sums, int32_t* __restrict__ indice_num,
                  int32_t* __restrict__ num_voxels,
                  const int32_t* __restrict__ bad_flags, int nflags, int32_t* __restrict__ status) {
   extern __shared__ uint32_t smem[];
+  RowLds& R = *(RowLds*)smem;
   // (part_sums != null: no geometry_bases_kernel ran -- few enough kernel-A workgroups that every workgroup here sums
   // their count rows in front of its own, plus the single slices of its own part, and workgroup 0 writes what that
   // kernel's lane 0s did)
-  __shared__ int32_t s_part[3][kEmitWaves][32];
   // (order_hist != null: the rows' neighbour-pattern records of ococc_subm_row_order are written here, where the row's
   // 27 table entries sit in registers anyway -- the separate counting pass re-read the whole table, 14 us)
-  __shared__ uint32_t s_oh[kLocalBuckets];
-  if ((int)blockIdx.x >= emit_blocks) {
+  if ((int)blockIdx.x >= emit_blocks + point_blocks) {
     // padding rows of the fixed-capacity form: -1 coordinates, zero count and features, no neighbours; the padding
     // workgroups take them in turns of 256
     int64_t total;
@@ -381,15 +401,16 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
       for (int e = threadIdx.x; e < g.batch * g.asplit; e += kEmitThreads) v += part_sums[(int64_t)e * kCols + 27];
 #pragma unroll
       for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-      if ((threadIdx.x & 63) == 0) s_part[0][threadIdx.x >> 6][0] = v;
+      if ((threadIdx.x & 63) == 0) R.part[0][threadIdx.x >> 6][0] = v;
       __syncthreads();
       total = 0;
-      for (int w = 0; w < kEmitWaves; ++w) total += s_part[0][w][0];
+      for (int w = 0; w < kEmitWaves; ++w) total += R.part[0][w][0];
     } else {
       total = totals[27];
     }
-    const int64_t turn = (int64_t)(gridDim.x - emit_blocks) * kEmitThreads;
-    const int64_t r0 = total + (int64_t)(blockIdx.x - emit_blocks) * kEmitThreads;
+    const int first_pad = emit_blocks + point_blocks;
+    const int64_t turn = (int64_t)(gridDim.x - first_pad) * kEmitThreads;
+    const int64_t r0 = total + (int64_t)(blockIdx.x - first_pad) * kEmitThreads;
     if (r0 >= cap) return;
     for (int64_t r = r0 + threadIdx.x; r - threadIdx.x < cap; r += turn) {
       const bool have = r < cap;
@@ -418,22 +439,210 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
     }
     return;
   }
-  uint32_t* bm = smem;            // [words]
-  uint32_t* pf = smem + g.words;  // [words] local prefix (rank inside the grid)
-  __shared__ int32_t s_base[kCols];
-  __shared__ int32_t s_wcnt[27][kEmitWaves];  // per round: valid entries per offset and wave, then their exclusive prefix
-  __shared__ int32_t s_run[27];
-  __shared__ int2 s_list[kCodesPerThread * kEmitThreads];  // (point - segment start, row) work items of one round
-  __shared__ int s_n, s_n2;
-  __shared__ int32_t s_cell[kEmitThreads];
-  __shared__ int32_t s_code[kCodesPerThread * kEmitThreads];  // the round's point codes (thread t owns slots j * 256 + t)
+  if ((int)blockIdx.x >= emit_blocks) {
+    // ---- point role: the points of one grid whose voxel row lies in one PART of the grid's slices (the spa
+    // consecutive ones one workgroup of kernel A counted): inv, point counts, feature rows, means.  A row's points all meet in this one workgroup
+    // -- "plain store, barrier, atomic adds, barrier, divide" holds inside a workgroup only -- so the parts are row
+    // ranges; the grid's codes are scanned once per part and phase, not once per slice.  Needs of the grid: its
+    // segment, the part's bitmap and prefix words, and the grid's first row.
+    PointLds& P = *(PointLds*)smem;
+    uint32_t* bm = smem + sizeof(PointLds) / 4;  // [spa * wps]: words pw_lo .. pw_hi of the grid
+    uint32_t* pf = bm + g.spa * g.wps;
+    const int pblk = (int)blockIdx.x - emit_blocks;
+    const int b = pblk / g.asplit, part = pblk % g.asplit;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    STAMP(5);
+    // the point codes of the first round are requested before anything else
+    const int64_t p_lo = seg[2 * b], p_hi = seg[2 * b + 1];
+    {
+      int32_t codes[kCodesPerThread];
+#pragma unroll
+      for (int j = 0; j < kCodesPerThread; ++j) {
+        const int64_t i = p_lo + (int64_t)j * kEmitThreads + threadIdx.x;
+        codes[j] = i < p_hi ? code_of[i] : -1;
+      }
+#pragma unroll
+      for (int j = 0; j < kCodesPerThread; ++j) P.code[j * kEmitThreads + threadIdx.x] = codes[j];  // (own slots: read back by this thread)
+    }
+    const int pw_lo = part * g.spa * g.wps < g.words ? part * g.spa * g.wps : g.words;
+    const int pw_hi = pw_lo + g.spa * g.wps < g.words ? pw_lo + g.spa * g.wps : g.words;
+    const uint32_t* gbm = bitmap + (int64_t)b * g.words;
+    const uint32_t* gpf = local_prefix + (int64_t)b * g.words;
+    for (int w = pw_lo + threadIdx.x; w < pw_hi; w += kEmitThreads) {
+      bm[w - pw_lo] = gbm[w];
+      pf[w - pw_lo] = gpf[w];
+    }
+    // global row of this grid's first voxel: the voxel column of kernel A's workgroups in front of the grid
+    int32_t grid_base = 0;
+    if (part_sums) {
+      int32_t v = 0;
+      for (int e = threadIdx.x; e < b * g.asplit; e += kEmitThreads) v += part_sums[(int64_t)e * kCols + 27];
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+      if (lane == 0) P.part[wave] = v;
+    } else {
+      grid_base = bases[((int64_t)b * g.slices) * kCols + 27];
+    }
+    if (threadIdx.x == 0) P.n2 = 0;
+    const int32_t grid_rows = (int32_t)(gpf[g.words - 1] + __popc(gbm[g.words - 1]));
+    const int32_t loc_lo = pw_lo < g.words ? (int32_t)gpf[pw_lo] : grid_rows;
+    const int32_t loc_hi = pw_hi < g.words ? (int32_t)gpf[pw_hi] : grid_rows;
+    __syncthreads();
+    if (part_sums) {
+#pragma unroll
+      for (int w = 0; w < kEmitWaves; ++w) grid_base += P.part[w];
+    }
+    const int32_t row_lo = grid_base + loc_lo, row_hi = grid_base + loc_hi;
+    // global row of a cell of this grid, -1 if the cell's word belongs to another part
+    auto part_rank = [&](int32_t cell) -> int32_t {
+      const int wi = (cell >> 5) - pw_lo;
+      if ((unsigned)wi >= (unsigned)(pw_hi - pw_lo)) return -1;
+      const uint32_t w = bm[wi];
+      const uint32_t bit = 1u << (cell & 31);
+      return (w & bit) ? grid_base + (int32_t)(pf[wi] + __popc(w & (bit - 1u))) : -1;
+    };
+    STAMP(6);
+    // Every phase first SCANS the round's points (codes -> rank -> "mine?") into a work list in LDS and then serves the
+    // list cooperatively, one thread per (entry, 16-byte piece or channel): the loads of a round are all in flight
+    // before the first store or atomic waits for one, and the few threads that own a shared row do not hold up a wave.
+    const int32_t cells = g.words * 32;
+    const int64_t per_round = (int64_t)kCodesPerThread * kEmitThreads;
+    const bool one_round = p_hi - p_lo <= per_round;
+    const int pieces = (c + 3) / 4;
+    auto load_codes = [&](int64_t base) {
+      int32_t codes[kCodesPerThread];
+#pragma unroll
+      for (int j = 0; j < kCodesPerThread; ++j) {
+        const int64_t i = base + (int64_t)j * kEmitThreads + threadIdx.x;
+        codes[j] = i < p_hi ? code_of[i] : -1;
+      }
+#pragma unroll
+      for (int j = 0; j < kCodesPerThread; ++j) P.code[j * kEmitThreads + threadIdx.x] = codes[j];
+    };
+    // phase 1: inv for every owned point; first arrivals copy their features into the row (f32 and bf16)
+    for (int64_t base = p_lo; base < p_hi; base += per_round) {
+      if (base != p_lo) load_codes(base);
+      if (threadIdx.x == 0) P.n = 0;
+      LDS_BARRIER();
+#pragma unroll 1
+      for (int j = 0; j < kCodesPerThread; ++j) {
+        const int64_t i = base + (int64_t)j * kEmitThreads + threadIdx.x;
+        const int32_t code = P.code[j * kEmitThreads + threadIdx.x];
+        if (i >= p_hi) continue;
+        if (code < 0) {
+          if (part == 0 && code == -2) inv[i] = -1;  // (codes <= -3: a finaliser mark of an earlier call: never seen here)
+          continue;
+        }
+        const int32_t r = part_rank((code >> 1) - b * cells);
+        if (r < 0) continue;   // another part's row
+        inv[i] = r;
+        if (!(code & 1) && r < cap) {
+          const int slot = atomicAdd(&P.n, 1);
+          P.list[slot] = make_int2((int)(i - p_lo), r);
+        }
+      }
+      LDS_BARRIER();
+      const int nl = P.n;
+      for (int t = threadIdx.x; t < nl * pieces; t += kEmitThreads) {
+        const int2 e = P.list[t / pieces];
+        const int piece = t % pieces;
+        const float* src = feats + (p_lo + e.x) * c;
+        float* dst = out_f32 + (int64_t)e.y * c;
+        uint16_t* dst16 = out_bf16 ? out_bf16 + (int64_t)e.y * c : nullptr;
+        if (piece == 0) counts[e.y] = 1;
+        if ((c & 3) == 0) {
+          const float4 v = *(const float4*)(src + piece * 4);
+          *(float4*)(dst + piece * 4) = v;
+          if (dst16) {
+            uint2 q;
+            q.x = (uint32_t)ococc_f32_to_bf16(v.x) | ((uint32_t)ococc_f32_to_bf16(v.y) << 16);
+            q.y = (uint32_t)ococc_f32_to_bf16(v.z) | ((uint32_t)ococc_f32_to_bf16(v.w) << 16);
+            *(uint2*)(dst16 + piece * 4) = q;
+          }
+        } else {
+          for (int ch = piece * 4; ch < piece * 4 + 4 && ch < c; ++ch) {
+            dst[ch] = src[ch];
+            if (dst16) dst16[ch] = ococc_f32_to_bf16(src[ch]);
+          }
+        }
+      }
+      LDS_BARRIER();
+    }
+    __syncthreads();  // the row copies are complete (s_waitcnt vmcnt(0) in front of the barrier) before anything adds to them
+    STAMP(8);
+    // phase 2: later arrivals add their features to the row and count themselves; the one that takes a row's count from
+    // 1 to 2 marks itself (code -3 - row) as the row's finaliser
+    for (int64_t base = p_lo; base < p_hi; base += per_round) {
+      if (!one_round) load_codes(base);
+      if (threadIdx.x == 0) P.n = 0;
+      LDS_BARRIER();
+#pragma unroll 1
+      for (int j = 0; j < kCodesPerThread; ++j) {
+        const int64_t i = base + (int64_t)j * kEmitThreads + threadIdx.x;
+        const int32_t code = P.code[j * kEmitThreads + threadIdx.x];
+        if (i >= p_hi || code < 0 || !(code & 1)) continue;
+        const int32_t r = part_rank((code >> 1) - b * cells);
+        if (r < 0 || r >= cap) continue;
+        const int slot = atomicAdd(&P.n, 1);
+        P.list[slot] = make_int2((int)(i - p_lo), r);
+      }
+      LDS_BARRIER();
+      const int nl = P.n;
+      for (int t = threadIdx.x; t < nl * c; t += kEmitThreads) {
+        const int2 e = P.list[t / c];
+        const int ch = t % c;
+        atomicAdd(out_f32 + (int64_t)e.y * c + ch, feats[(p_lo + e.x) * c + ch]);
+        if (ch == 0 && atomicAdd(counts + e.y, 1) == 1) {
+          code_of[p_lo + e.x] = -3 - e.y;
+          atomicAdd(&P.n2, 1);
+        }
+      }
+      LDS_BARRIER();
+    }
+    __syncthreads();  // the adds and marks are complete
+    STAMP(9);
+    // phase 3: rows with more than one point: sum -> mean (read past L1: the adds went to L2)
+    if (P.n2 > 0) {
+      for (int64_t base = p_lo; base < p_hi; base += per_round) {
+        load_codes(base);
+        if (threadIdx.x == 0) P.n = 0;
+        LDS_BARRIER();
+#pragma unroll 1
+        for (int j = 0; j < kCodesPerThread; ++j) {
+          const int64_t i = base + (int64_t)j * kEmitThreads + threadIdx.x;
+          const int32_t code = P.code[j * kEmitThreads + threadIdx.x];
+          if (i >= p_hi || code > -3) continue;
+          const int32_t r = -3 - code;
+          if (r < row_lo || r >= row_hi) continue;  // another part's finaliser
+          const int slot = atomicAdd(&P.n, 1);
+          P.list[slot] = make_int2((int)(i - p_lo), r);
+        }
+        LDS_BARRIER();
+        const int nl = P.n;
+        for (int t = threadIdx.x; t < nl * c; t += kEmitThreads) {
+          const int64_t r = P.list[t / c].y;
+          const int ch = t % c;
+          const float cnt = (float)__hip_atomic_load(counts + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const float v = __hip_atomic_load(out_f32 + r * c + ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / cnt;
+          out_f32[r * c + ch] = v;
+          if (out_bf16) out_bf16[r * c + ch] = ococc_f32_to_bf16(v);
+        }
+        LDS_BARRIER();
+      }
+    }
+    STAMP(10);
+    return;
+  }
+  // ---- row role: the rows of one slice of one grid --------------------------------------------------------------
+  uint32_t* bm = smem + sizeof(RowLds) / 4;  // [words]
+  uint32_t* pf = bm + g.words;               // [words] local prefix (rank inside the grid)
   const int b = blockIdx.x / g.slices, sl = blockIdx.x % g.slices;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
   STAMP(5);
-  // (part sums: column c of kernel A's count rows, lane -> column, 8 interleaved parts; asked for FIRST -- they depend
-  // on nothing, the point codes below wait for their segment's bounds -- and only summed behind the bitmap: the
-  // vector-memory counter retires in order, so consumed here they would hold everything behind them back by a trip)
+  // (part sums: column c of kernel A's count rows, lane -> column, 8 interleaved parts; asked for first and only
+  // summed behind the bitmap: the vector-memory counter retires in order, so consumed here they would hold the bitmap
+  // loads behind them back by a trip)
   constexpr int kPartLoads = kFusedBasesMaxEntries / (2 * kEmitWaves);
   constexpr int kOwnLoads = kMaxSlices / 4;   // slices of the own part in front of this one: at most spa - 1 < 4
   int32_t pv[kPartLoads], pw[kOwnLoads];
@@ -449,18 +658,6 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
       const int s2 = (sl / g.spa) * g.spa + u;
       pw[u] = (pcol < kCols && ppart == 0 && s2 < sl) ? count_table[((int64_t)b * g.slices + s2) * kCols + pcol] : 0;
     }
-  }
-  // the point codes of the first round are requested before anything else: their latency hides behind the row loop
-  const int64_t p_lo = seg[2 * b], p_hi = seg[2 * b + 1];
-  {
-    int32_t codes[kCodesPerThread];
-#pragma unroll
-    for (int j = 0; j < kCodesPerThread; ++j) {
-      const int64_t i = p_lo + (int64_t)j * kEmitThreads + threadIdx.x;
-      codes[j] = i < p_hi ? code_of[i] : -1;
-    }
-#pragma unroll
-    for (int j = 0; j < kCodesPerThread; ++j) s_code[j * kEmitThreads + threadIdx.x] = codes[j];  // (own slots: read back by this thread)
   }
   for (int w = threadIdx.x; w < g.words; w += kEmitThreads) {
     bm[w] = bitmap[(int64_t)b * g.words + w];
@@ -484,32 +681,32 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
     a_grid += __shfl_xor(a_grid, 32, 64);
     a_all += __shfl_xor(a_all, 32, 64);
     if (lane < 32) {
-      s_part[0][wave][lane] = a_me;
-      s_part[1][wave][lane] = a_grid;
-      s_part[2][wave][lane] = a_all;
+      R.part[0][wave][lane] = a_me;
+      R.part[1][wave][lane] = a_grid;
+      R.part[2][wave][lane] = a_all;
     }
   } else if (threadIdx.x < kCols) {
-    s_base[threadIdx.x] = bases[((int64_t)b * g.slices + sl) * kCols + threadIdx.x];
+    R.base[threadIdx.x] = bases[((int64_t)b * g.slices + sl) * kCols + threadIdx.x];
   }
-  if (threadIdx.x < 27) s_run[threadIdx.x] = 0;
+  if (threadIdx.x < 27) R.run[threadIdx.x] = 0;
   if (order_hist)
-    for (int i = threadIdx.x; i < kLocalBuckets; i += kEmitThreads) s_oh[i] = 0u;
+    for (int i = threadIdx.x; i < kLocalBuckets; i += kEmitThreads) R.oh[i] = 0u;
   // global row of this grid's first voxel: the slice-0 base of the voxel column
   int32_t grid_base = part_sums ? 0 : bases[((int64_t)b * g.slices) * kCols + 27];
   __syncthreads();
   if (part_sums) {
 #pragma unroll
     for (int w = 0; w < kEmitWaves; ++w) {
-      grid_base += s_part[1][w][27];
+      grid_base += R.part[1][w][27];
     }
-    if (threadIdx.x < kCols) {   // (s_base is first read behind the row loop's barriers)
+    if (threadIdx.x < kCols) {   // (R.base is first read behind the row loop's barriers)
       int32_t me = 0, all = 0;
 #pragma unroll
       for (int w = 0; w < kEmitWaves; ++w) {
-        me += s_part[0][w][threadIdx.x];
-        all += s_part[2][w][threadIdx.x];
+        me += R.part[0][w][threadIdx.x];
+        all += R.part[2][w][threadIdx.x];
       }
-      s_base[threadIdx.x] = me;
+      R.base[threadIdx.x] = me;
       if (blockIdx.x == 0) {
         // indice_num[k] = pairs of offset k = entries of table column 26 - k (= column k, by symmetry); geometry.h order
         if (threadIdx.x < 27) indice_num[26 - threadIdx.x] = all;
@@ -546,7 +743,7 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
       while (bits) {
         const int bb = __ffs(bits) - 1;
         bits &= bits - 1;
-        if ((unsigned)idx < (unsigned)kEmitThreads) s_cell[idx] = w * 32 + bb;
+        if ((unsigned)idx < (unsigned)kEmitThreads) R.cell[idx] = w * 32 + bb;
         ++idx;
       }
     }
@@ -554,12 +751,10 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
     int32_t cell = 0;
     int x = 0, y = 0, z = 0;
     if (have) {
-      cell = s_cell[threadIdx.x];
+      cell = R.cell[threadIdx.x];
       x = cell % g.gx; y = (cell / g.gx) % g.gy; z = cell / plane;
-      if (row < cap) {
-        *(int4*)(out_coors + (int64_t)row * 4) = make_int4(b, z, y, x);
-        counts[row] = 1;
-      }
+      // (the row's point count belongs to the point role: its later arrivals add to it from another workgroup)
+      if (row < cap) *(int4*)(out_coors + (int64_t)row * 4) = make_int4(b, z, y, x);
     }
     // the three x-neighbours of one (dz, dy) are consecutive cells: ONE 64-bit window of the bitmap and ONE prefix word
     // serve all three.  (Unrolled on purpose: nine independent LDS round trips in flight; a rolled body, or a second
@@ -597,7 +792,7 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
     for (int k = 0; k < 27; ++k) {
       if (have && row < cap) nbr_t[(int64_t)k * cap + row] = nb[k];
       const unsigned long long m = __ballot(nb[k] >= 0);
-      if (lane == 0) s_wcnt[k][wave] = (int32_t)__popcll(m);
+      if (lane == 0) R.wcnt[k][wave] = (int32_t)__popcll(m);
       if (nb[k] >= 0) mbits |= 1u << k;
     }
     if (order_hist && have && row < cap) {
@@ -609,7 +804,7 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
           else if (e2 < 0) e2 = nb[k];
         }
       const int key = order_key_local(mbits, 13);
-      const uint32_t rank = atomicAdd(&s_oh[key], 1u);   // place inside this workgroup's share of the bucket
+      const uint32_t rank = atomicAdd(&R.oh[key], 1u);   // place inside this workgroup's share of the bucket
       order_rowrec[row] = i32x4_t{(int)((uint32_t)order_global(key, (int)blockIdx.x) | (rank << kOrderKeyBits)),
                                   (int)mbits, e1, e2};
     }
@@ -632,14 +827,14 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
     STAMP(13);
     LDS_BARRIER();
     if (threadIdx.x < 27) {  // counts -> position of each wave's first entry (base of the slice + rounds so far + waves before)
-      int32_t acc = s_base[threadIdx.x] + s_run[threadIdx.x];
+      int32_t acc = R.base[threadIdx.x] + R.run[threadIdx.x];
       const int32_t start = acc;
       for (int t = 0; t < kEmitWaves; ++t) {
-        const int32_t cnt = s_wcnt[threadIdx.x][t];
-        s_wcnt[threadIdx.x][t] = acc;
+        const int32_t cnt = R.wcnt[threadIdx.x][t];
+        R.wcnt[threadIdx.x][t] = acc;
         acc += cnt;
       }
-      s_run[threadIdx.x] += acc - start;
+      R.run[threadIdx.x] += acc - start;
     }
     LDS_BARRIER();
     STAMP(14);
@@ -648,7 +843,7 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
     for (int k = 0; k < 27; ++k) {
       if (nb[k] >= 0) {
         const unsigned long long m = __ballot(true);
-        const int32_t p = s_wcnt[k][wave] + (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        const int32_t p = R.wcnt[k][wave] + (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         if (p < cap) {
           pairs[((int64_t)(26 - k) * 2 + 0) * cap + p] = row;
           pairs[((int64_t)(26 - k) * 2 + 1) * cap + p] = nb[k];
@@ -658,8 +853,7 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
     LDS_BARRIER();
   }
 
-  // the workgroup's share of every bucket starts where the bucket's counter stood: the atomics are asked for here and
-  // their answers used at the very end of the kernel, behind the point phases
+  // the workgroup's share of every bucket starts where the bucket's counter stood
   constexpr int kOrderPer = (kLocalBuckets + kEmitThreads - 1) / kEmitThreads;
   uint32_t o_cnt[kOrderPer], o_got[kOrderPer];
   if (order_hist) {
@@ -667,149 +861,18 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
 #pragma unroll
     for (int i = 0; i < kOrderPer; ++i) {
       const int bk = threadIdx.x + kEmitThreads * i;
-      o_cnt[i] = bk < kLocalBuckets ? s_oh[bk] : 0u;
+      o_cnt[i] = bk < kLocalBuckets ? R.oh[bk] : 0u;
       o_got[i] = 0u;
       if (o_cnt[i]) o_got[i] = atomicAdd(&order_hist[order_global(bk, (int)blockIdx.x)], o_cnt[i]);
     }
   }
   STAMP(7);
-  // ---- points of this grid whose voxel row belongs to the slice, kCodesPerThread * 256 per round ----
-  // Every phase first SCANS the round's points (codes -> rank -> "mine?") into a work list in LDS and then serves the
-  // list cooperatively, one thread per (entry, 16-byte piece or channel): the loads of a round are all in flight
-  // before the first store or atomic waits for one, and the few threads that own a shared row do not hold up a wave.
-  const int32_t cells = g.words * 32;
-  const int64_t per_round = (int64_t)kCodesPerThread * kEmitThreads;
-  const bool one_round = p_hi - p_lo <= per_round;
-  const int pieces = (c + 3) / 4;
-  auto load_codes = [&](int64_t base) {
-    int32_t codes[kCodesPerThread];
-#pragma unroll
-    for (int j = 0; j < kCodesPerThread; ++j) {
-      const int64_t i = base + (int64_t)j * kEmitThreads + threadIdx.x;
-      codes[j] = i < p_hi ? code_of[i] : -1;
-    }
-#pragma unroll
-    for (int j = 0; j < kCodesPerThread; ++j) s_code[j * kEmitThreads + threadIdx.x] = codes[j];
-  };
-  // phase 1: inv for every owned point; first arrivals copy their features into the row (f32 and bf16)
-  for (int64_t base = p_lo; base < p_hi; base += per_round) {
-    if (base != p_lo) load_codes(base);
-    if (threadIdx.x == 0) s_n = 0;
-    LDS_BARRIER();
-#pragma unroll 1
-    for (int j = 0; j < kCodesPerThread; ++j) {
-      const int64_t i = base + (int64_t)j * kEmitThreads + threadIdx.x;
-      const int32_t code = s_code[j * kEmitThreads + threadIdx.x];
-      if (i >= p_hi) continue;
-      if (code < 0) {
-        if (sl == 0 && code == -2) inv[i] = -1;  // (codes <= -3: a finaliser mark of an earlier call: never seen here)
-        continue;
-      }
-      const int32_t r = grid_base + lds_rank(bm, pf, (code >> 1) - b * cells);
-      if (r < row_lo || r >= row_hi) continue;
-      inv[i] = r;
-      if (!(code & 1) && r < cap) {
-        const int slot = atomicAdd(&s_n, 1);
-        s_list[slot] = make_int2((int)(i - p_lo), r);
-      }
-    }
-    LDS_BARRIER();
-    const int nl = s_n;
-    for (int t = threadIdx.x; t < nl * pieces; t += kEmitThreads) {
-      const int2 e = s_list[t / pieces];
-      const int piece = t % pieces;
-      const float* src = feats + (p_lo + e.x) * c;
-      float* dst = out_f32 + (int64_t)e.y * c;
-      uint16_t* dst16 = out_bf16 ? out_bf16 + (int64_t)e.y * c : nullptr;
-      if ((c & 3) == 0) {
-        const float4 v = *(const float4*)(src + piece * 4);
-        *(float4*)(dst + piece * 4) = v;
-        if (dst16) {
-          uint2 q;
-          q.x = (uint32_t)ococc_f32_to_bf16(v.x) | ((uint32_t)ococc_f32_to_bf16(v.y) << 16);
-          q.y = (uint32_t)ococc_f32_to_bf16(v.z) | ((uint32_t)ococc_f32_to_bf16(v.w) << 16);
-          *(uint2*)(dst16 + piece * 4) = q;
-        }
-      } else {
-        for (int ch = piece * 4; ch < piece * 4 + 4 && ch < c; ++ch) {
-          dst[ch] = src[ch];
-          if (dst16) dst16[ch] = ococc_f32_to_bf16(src[ch]);
-        }
-      }
-    }
-    LDS_BARRIER();
-  }
-  __syncthreads();  // the row copies are complete (s_waitcnt vmcnt(0) in front of the barrier) before anything adds to them
-  STAMP(8);
-  // phase 2: later arrivals add their features to the row and count themselves; the one that takes a row's count from
-  // 1 to 2 marks itself (code -3 - row) as the row's finaliser
-  int32_t* s_nfin = &s_n2;
-  if (threadIdx.x == 0) s_n2 = 0;
-  for (int64_t base = p_lo; base < p_hi; base += per_round) {
-    if (!one_round) load_codes(base);
-    if (threadIdx.x == 0) s_n = 0;
-    LDS_BARRIER();
-#pragma unroll 1
-    for (int j = 0; j < kCodesPerThread; ++j) {
-      const int64_t i = base + (int64_t)j * kEmitThreads + threadIdx.x;
-      const int32_t code = s_code[j * kEmitThreads + threadIdx.x];
-      if (i >= p_hi || code < 0 || !(code & 1)) continue;
-      const int32_t r = grid_base + lds_rank(bm, pf, (code >> 1) - b * cells);
-      if (r < row_lo || r >= row_hi || r >= cap) continue;
-      const int slot = atomicAdd(&s_n, 1);
-      s_list[slot] = make_int2((int)(i - p_lo), r);
-    }
-    LDS_BARRIER();
-    const int nl = s_n;
-    for (int t = threadIdx.x; t < nl * c; t += kEmitThreads) {
-      const int2 e = s_list[t / c];
-      const int ch = t % c;
-      atomicAdd(out_f32 + (int64_t)e.y * c + ch, feats[(p_lo + e.x) * c + ch]);
-      if (ch == 0 && atomicAdd(counts + e.y, 1) == 1) {
-        code_of[p_lo + e.x] = -3 - e.y;
-        atomicAdd(s_nfin, 1);
-      }
-    }
-    LDS_BARRIER();
-  }
-  __syncthreads();  // the adds and marks are complete
-  STAMP(9);
-  // phase 3: rows with more than one point: sum -> mean (read past L1: the adds went to L2)
-  if (s_n2 > 0) {
-    for (int64_t base = p_lo; base < p_hi; base += per_round) {
-      load_codes(base);
-      if (threadIdx.x == 0) s_n = 0;
-      LDS_BARRIER();
-#pragma unroll 1
-      for (int j = 0; j < kCodesPerThread; ++j) {
-        const int64_t i = base + (int64_t)j * kEmitThreads + threadIdx.x;
-        const int32_t code = s_code[j * kEmitThreads + threadIdx.x];
-        if (i >= p_hi || code > -3) continue;
-        const int32_t r = -3 - code;
-        if (r < row_lo || r >= row_hi) continue;  // another slice's finaliser
-        const int slot = atomicAdd(&s_n, 1);
-        s_list[slot] = make_int2((int)(i - p_lo), r);
-      }
-      LDS_BARRIER();
-      const int nl = s_n;
-      for (int t = threadIdx.x; t < nl * c; t += kEmitThreads) {
-        const int64_t r = s_list[t / c].y;
-        const int ch = t % c;
-        const float cnt = (float)__hip_atomic_load(counts + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const float v = __hip_atomic_load(out_f32 + r * c + ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / cnt;
-        out_f32[r * c + ch] = v;
-        if (out_bf16) out_bf16[r * c + ch] = ococc_f32_to_bf16(v);
-      }
-      LDS_BARRIER();
-    }
-  }
-  STAMP(10);
   if (order_hist) {
     // this workgroup's share of every bucket starts where the counter stood when its atomic arrived
 #pragma unroll
     for (int i = 0; i < kOrderPer; ++i) {
       const int bk = threadIdx.x + kEmitThreads * i;
-      if (o_cnt[i]) s_oh[bk] = o_got[i];
+      if (o_cnt[i]) R.oh[bk] = o_got[i];
     }
     __syncthreads();
     const int32_t hi = row_hi < cap ? row_hi : (int32_t)cap;
@@ -819,9 +882,10 @@ grid_emit_kernel(const float* __restrict__ feats, int c, int64_t n, GeoParams g,
     for (int32_t r = row_lo + threadIdx.x; r < hi; r += kEmitThreads) {
       const uint32_t x = (uint32_t)order_rowrec[r].x;
       const int lk = order_local((int)(x & ((1u << kOrderKeyBits) - 1u)));   // global bucket -> this workgroup's
-      order_rowrec[r].x = (int)(x + (s_oh[lk] << kOrderKeyBits));
+      order_rowrec[r].x = (int)(x + (R.oh[lk] << kOrderKeyBits));
     }
   }
+  STAMP(15);
 }
 
 struct GeoLayout {
@@ -932,11 +996,14 @@ extern "C" int ococc_object_grid_geometry_order_f32(const float* points, int32_t
   int64_t* seg = (int64_t*)(ws + L.off_seg);
   int32_t* bad_flags = (int32_t*)(ws + L.off_bad);
   const size_t lds = (size_t)g.words * 8;
+  // kernel B: the row role holds the grid's words, the point role its part's (spa slices) and the point staging
+  const size_t lds_row = sizeof(RowLds) + (size_t)g.words * 8, lds_point = sizeof(PointLds) + (size_t)g.spa * g.wps * 8;
+  const size_t lds_emit = lds_row > lds_point ? lds_row : lds_point;
   const int64_t mask_words = ococc_cdiv(capacity, 16);
-  if (lds > 48 * 1024) {
+  if (lds > 48 * 1024)
     OCOCC_HIP(hipFuncSetAttribute((const void*)grid_mark_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    OCOCC_HIP(hipFuncSetAttribute((const void*)grid_emit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
+  if (lds_emit > 48 * 1024)
+    OCOCC_HIP(hipFuncSetAttribute((const void*)grid_emit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_emit));
   // the prefix of the count table: inside kernel B for small batches (kernel A also leaves the sums of each of its
   // workgroups' slices; every workgroup of B reads those in front of its own: quadratic in the batch, one trip to L2),
   // a launch of its own for large ones
@@ -952,16 +1019,16 @@ extern "C" int ococc_object_grid_geometry_order_f32(const float* points, int32_t
                        indice_num, num_voxels, capacity, bad_flags, (int)(batch_size * g.asplit), status);
     OCOCC_CHECK_LAUNCH();
   }
-  const int emit_blocks = (int)entries;
+  const int emit_blocks = (int)entries, point_blocks = batch_size * g.asplit;
   // the padding workgroups index rows from the device-side total and take them in turns (worst case every row is
   // padding: an empty batch)
   const int64_t pad_need = ococc_cdiv(capacity, kEmitThreads);
   const int pad_blocks = (int)(pad_need < kPadBlocks ? pad_need : kPadBlocks);
-  hipLaunchKernelGGL(grid_emit_kernel, dim3(emit_blocks + pad_blocks), dim3(kEmitThreads), lds, stream, feats, (int)c, n, g,
-                     bitmap, lpre, prefix, code_of, seg, bases, totals, inv, voxel_coors, counts, voxel_feats,
-                     voxel_feats_bf16, capacity, nbr_t, blockmask, indice_pairs, emit_blocks, (uint32_t*)order_counters,
-                     (i32x4_t*)order_rowrec, (const int32_t*)table, (const int32_t*)part_sums, indice_num, num_voxels,
-                     (const int32_t*)bad_flags, (int)(batch_size * g.asplit), status);
+  hipLaunchKernelGGL(grid_emit_kernel, dim3(emit_blocks + point_blocks + pad_blocks), dim3(kEmitThreads), lds_emit, stream, feats,
+                     (int)c, n, g, bitmap, lpre, prefix, code_of, seg, bases, totals, inv, voxel_coors, counts, voxel_feats,
+                     voxel_feats_bf16, capacity, nbr_t, blockmask, indice_pairs, emit_blocks, point_blocks,
+                     (uint32_t*)order_counters, (i32x4_t*)order_rowrec, (const int32_t*)table, (const int32_t*)part_sums,
+                     indice_num, num_voxels, (const int32_t*)bad_flags, (int)(batch_size * g.asplit), status);
   OCOCC_CHECK_LAUNCH();
   if (order_rec)   // the slots: a launch of its own
     return ococc_subm_row_order_place(order_rowrec, 27, 13, capacity, heavy_blocks, mid_blocks, order_counters, order_rec,

@@ -1118,6 +1118,25 @@ int ococc_temporal_attention_bwd_f32(const float* q, int64_t ldq, const float* k
                                      float* dk, int64_t lddk, float* dv, int64_t lddv, ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * A9, online  one frame of that attention core against cached keys and values (csrc/causal_attn_step.hip).
+ * Replaces, for a tracklet that arrives frame by frame, the re-run of the chain above on the growing prefix: under the
+ * causal mask of OccBBoxHead.get_future_mask (ococc_bbox_head.py:1034-1043; test_cfg.attn_window_size) row t of
+ * nn.MultiheadAttention as SimpleEncoderLayer calls it (mmdet3d/models/occ/layers.py:35-87) reads keys lo .. t only.
+ * q, k_new, v_new: f32 [n, heads * head_dim], one row per stepping tracklet, head h in columns h * head_dim .., row
+ * strides ldq / ldk / ldv floats.  slot [n]: the cache slot of each row (device, distinct, in [0, slots)); pos [slots]:
+ * the frames already cached per slot (device).  k_cache, v_cache: f32 [slots, cap, heads * head_dim], contiguous.
+ * For row i with s = slot[i], t = pos[s]: k_new[i] / v_new[i] are written to cache row (s, t), and
+ *   out[i] = softmax(scale q[i] . K[s, lo .. t]) V[s, lo .. t]  per head,  lo = max(0, t - window + 1) (window <= 0: 0).
+ * pos is NOT advanced (every encoder layer has its own cache and shares pos; the caller bumps it after the last layer).
+ * No cache row outside [lo, t] is read, none but t is written; a row whose slot or pos[slot] is out of range is skipped
+ * (nothing written, out[i] untouched).  cap <= 256, head_dim % 4 == 0 and <= 384, 16-byte aligned rows (OCOCC_EINVAL
+ * otherwise, nothing launched).  No dropout (inference); no atomics; deterministic. */
+int ococc_temporal_attention_step_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk, const float* v_new,
+                                      int64_t ldv, const int32_t* slot, const int32_t* pos, float* k_cache, float* v_cache,
+                                      int32_t n, int32_t slots, int32_t cap, int32_t heads, int32_t head_dim, float scale,
+                                      int32_t window, float* out, int64_t ldo, ococc_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * A11 / A10, fused  the occupancy decoder's per-query MLP, one launch per layer (or one for the whole MLP):
  *   y = dropout(act(LayerNorm(x W^T + bias + add_rows[add_index]))),  optionally  head = y . head_weight + head_bias
  * replaces OccDecoder.forward's conv_occ (mmdet3d/models/occ/occ_base.py:99-153): build_mlp's

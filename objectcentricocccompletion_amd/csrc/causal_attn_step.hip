@@ -1,0 +1,184 @@
+// A9, online  one frame of the temporal transformer's attention against cached keys and values.
+//
+// Reference: the same block as csrc/causal_attn.hip (SimpleEncoderLayer.forward -> nn.MultiheadAttention,
+// mmdet3d/models/occ/layers.py:35-87, under the causal mask of OccBBoxHead.get_future_mask, ococc_bbox_head.py:1034-1043,
+// optionally windowed by test_cfg.attn_window_size).  Under that mask row t of the full product reads keys lo..t only, so
+// a tracklet that arrives frame by frame needs one query row per frame against the keys and values of the frames before it.
+// Here: one workgroup per (row, head).  It appends the row's new key and value to its head's column slice of cache row
+// (slot, pos[slot]) and computes  softmax(scale q . K[lo..t]) V[lo..t]  with the new key and value taken from LDS, the
+// cached ones straight from global memory into registers with float4 loads (a memory-bound read of at most 2 * 256 * D
+// floats: no LDS staging of K / V, no split of the keys across workgroups).  Scores: 16 lanes per key, kSK = 16 keys per pass
+// of the workgroup; the softmax over <= 256 scores by wave butterflies; the product with V with the keys dealt round-robin to
+// the 16 lane groups and the 16 partial rows summed in a fixed order.  f32 throughout, no atomics, no dropout (inference only).
+// The kernel does not advance pos: every encoder layer has a cache of its own and shares pos, the caller bumps it once.
+#include "common.hpp"
+
+namespace {
+
+constexpr int kST = 256;      // threads per workgroup
+constexpr int kSK = 16;       // keys per pass (16 lanes each)
+constexpr int kSMaxS = 256;   // cache rows per slot at most (kAMaxS of causal_attn.hip)
+constexpr int kSNJ = 6;       // float4 column groups per thread: D <= 16 * 4 * kSNJ = 384 (kANJ of causal_attn.hip)
+constexpr int kSMaxD = 64 * kSNJ;
+
+struct StepArgs {
+  const float* q;
+  const float* k_new;
+  const float* v_new;
+  int64_t ldq, ldk, ldv;
+  const int32_t* slot;   // [n]
+  const int32_t* pos;    // [slots]
+  float* k_cache;        // [slots, cap, H * D]
+  float* v_cache;
+  int32_t n, slots, cap, H, D;
+  float scale;
+  int32_t window;
+  float* out;
+  int64_t ldo;
+};
+
+__device__ __forceinline__ float dot4(const f32x4 a, const f32x4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
+__device__ __forceinline__ float sum16(float v) {
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  v += __shfl_xor(v, 4, 64);
+  v += __shfl_xor(v, 8, 64);
+  return v;
+}
+
+__global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
+  __shared__ __attribute__((aligned(16))) float sq[kSMaxD];          // the query row, scaled
+  __shared__ __attribute__((aligned(16))) float sk[kSMaxD];          // the new key
+  __shared__ __attribute__((aligned(16))) float sv[kSMaxD];          // the new value
+  __shared__ float ss[kSMaxS];                                       // scores -> probabilities of keys lo .. t
+  __shared__ float red[2 * (kST / 64)];
+  __shared__ __attribute__((aligned(16))) float part[kSK * kSMaxD];  // the 16 partial context rows
+  const int i = blockIdx.x, h = blockIdx.y;
+  const int s = a.slot[i];
+  if (s < 0 || s >= a.slots) return;   // (the host checks both; a host bug must not write outside the cache)
+  const int t = a.pos[s];
+  if (t < 0 || t >= a.cap) return;
+  const int lo = a.window > 0 && t - a.window + 1 > 0 ? t - a.window + 1 : 0;
+  const int nk = t - lo + 1;           // keys lo .. t, the last one the new one
+  const int D4 = a.D >> 2, col0 = h * a.D;
+  const int64_t ldc = (int64_t)a.H * a.D;
+  float* kc = a.k_cache + (int64_t)s * a.cap * ldc + col0;
+  float* vc = a.v_cache + (int64_t)s * a.cap * ldc + col0;
+  const int tid = threadIdx.x, r = tid >> 4, c0 = tid & 15;
+
+  if (tid < D4) {   // append: this head's slice of cache row t, and the LDS copies the sums below read
+    const f32x4 qv = *(const f32x4*)(a.q + (int64_t)i * a.ldq + col0 + tid * 4);
+    const f32x4 kv = *(const f32x4*)(a.k_new + (int64_t)i * a.ldk + col0 + tid * 4);
+    const f32x4 vv = *(const f32x4*)(a.v_new + (int64_t)i * a.ldv + col0 + tid * 4);
+    *(f32x4*)(sq + tid * 4) = qv * a.scale;
+    *(f32x4*)(sk + tid * 4) = kv;
+    *(f32x4*)(sv + tid * 4) = vv;
+    *(f32x4*)(kc + (int64_t)t * ldc + tid * 4) = kv;
+    *(f32x4*)(vc + (int64_t)t * ldc + tid * 4) = vv;
+  }
+  __syncthreads();
+
+  // scores: lane group r takes key j0 + r of every pass, its 16 lanes the float4 columns c0, c0 + 16, ...
+  for (int j0 = 0; j0 < nk; j0 += kSK) {
+    const int j = j0 + r;
+    float acc = 0.f;
+    if (j < nk) {
+      if (j == nk - 1) {
+        for (int c4 = c0; c4 < D4; c4 += 16) acc += dot4(*(const f32x4*)(sq + c4 * 4), *(const f32x4*)(sk + c4 * 4));
+      } else {
+        const float* krow = kc + (int64_t)(lo + j) * ldc;
+        for (int c4 = c0; c4 < D4; c4 += 16) acc += dot4(*(const f32x4*)(sq + c4 * 4), *(const f32x4*)(krow + c4 * 4));
+      }
+    }
+    acc = sum16(acc);
+    if (j < nk && c0 == 0) ss[j] = acc;
+  }
+  __syncthreads();
+
+  {   // softmax over the nk <= 256 scores, one per thread
+    const int lane = tid & 63, wave = tid >> 6;
+    const float x = tid < nk ? ss[tid] : -INFINITY;
+    float m = x;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const float e = tid < nk ? __expf(x - m) : 0.f;
+    float sum = e;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0) red[4 + wave] = sum;
+    __syncthreads();
+    const float inv = 1.f / ((red[4] + red[5]) + (red[6] + red[7]));
+    if (tid < nk) ss[tid] = e * inv;
+  }
+  __syncthreads();
+
+  // context: lane group r sums the keys j = r, r + 16, ... in turn; then the 16 partial rows in a fixed order
+  f32x4 o[kSNJ];
+#pragma unroll
+  for (int jj = 0; jj < kSNJ; ++jj) o[jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int j = r; j < nk; j += kSK) {
+    const float w = ss[j];
+    if (j == nk - 1) {
+#pragma unroll
+      for (int jj = 0; jj < kSNJ; ++jj) {
+        const int c4 = c0 + 16 * jj;
+        if (c4 < D4) o[jj] += *(const f32x4*)(sv + c4 * 4) * w;
+      }
+    } else {
+      const float* vrow = vc + (int64_t)(lo + j) * ldc;
+#pragma unroll
+      for (int jj = 0; jj < kSNJ; ++jj) {
+        const int c4 = c0 + 16 * jj;
+        if (c4 < D4) o[jj] += *(const f32x4*)(vrow + c4 * 4) * w;
+      }
+    }
+  }
+#pragma unroll
+  for (int jj = 0; jj < kSNJ; ++jj) {
+    const int c4 = c0 + 16 * jj;
+    if (c4 < D4) *(f32x4*)(part + r * kSMaxD + c4 * 4) = o[jj];
+  }
+  __syncthreads();
+  if (tid < D4) {
+    f32x4 acc = *(const f32x4*)(part + tid * 4);
+#pragma unroll
+    for (int g = 1; g < kSK; ++g) acc += *(const f32x4*)(part + g * kSMaxD + tid * 4);
+    *(f32x4*)(a.out + (int64_t)i * a.ldo + col0 + tid * 4) = acc;
+  }
+}
+
+}  // namespace
+
+extern "C" int ococc_temporal_attention_step_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk,
+                                                 const float* v_new, int64_t ldv, const int32_t* slot, const int32_t* pos,
+                                                 float* k_cache, float* v_cache, int32_t n, int32_t slots, int32_t cap,
+                                                 int32_t H, int32_t D, float scale, int32_t window, float* out, int64_t ldo,
+                                                 ococc_stream_t stream_) {
+  OCOCC_REQUIRE(n >= 0 && slots >= 1 && cap >= 1 && H >= 1 && D >= 1, "empty cache or negative row count");
+  OCOCC_REQUIRE(n <= slots, "more rows than cache slots (the slots of one step are distinct)");
+  OCOCC_REQUIRE(cap <= kSMaxS && D <= kSMaxD && D % 4 == 0,
+                "caches of up to 256 frames per slot, head width a multiple of 4 up to 384");
+  OCOCC_REQUIRE(H <= 65535, "too many heads");
+  if (n == 0) return OCOCC_OK;
+  OCOCC_REQUIRE(q && k_new && v_new && slot && pos && k_cache && v_cache && out, "null pointer");
+  const int64_t E = (int64_t)H * D;
+  OCOCC_REQUIRE(ldq >= E && ldk >= E && ldv >= E && ldo >= E, "row stride under heads * head_dim");
+  OCOCC_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 &&
+                    (((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache |
+                      (uintptr_t)out) & 15) == 0,
+                "rows must be 16-byte aligned");
+  StepArgs a{};
+  a.q = q; a.k_new = k_new; a.v_new = v_new;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.slot = slot; a.pos = pos;
+  a.k_cache = k_cache; a.v_cache = v_cache;
+  a.n = n; a.slots = slots; a.cap = cap; a.H = H; a.D = D;
+  a.scale = scale; a.window = window;
+  a.out = out; a.ldo = ldo;
+  hipLaunchKernelGGL(attn_step_kernel, dim3(n, H), dim3(kST), 0, (hipStream_t)stream_, a);
+  OCOCC_CHECK_LAUNCH();
+  return OCOCC_OK;
+}

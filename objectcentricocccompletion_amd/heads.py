@@ -672,9 +672,9 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
         final_cluster_feats = self.align_roi_feature_and_rois(final_cluster_feats, out_coors, len(rois))
         return final_cluster_feats, nonempty_roi_mask, out_coors
 
-    def forward(self, pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds):
-        """ococc_bbox_head.py:319-400 -> dict(fused_roi_feats, nonempty_roi_mask, ori_roi_feats,
-        cls_score, bbox_pred)."""
+    def _encode_rois(self, pts_xyz, pts_features, pts_info, roi_inds, rois):
+        """The per-RoI stages in front of the temporal transformer: the SIR features of the pooled points (zeros and an
+        all-False mask when no RoI holds a point) and the single-frame shape latent of the occupancy auto-encoder."""
         if pts_xyz.size(0) == 0:
             final_cluster_feats = pts_features.new_zeros((len(rois), self.roi_feature_channels))
             nonempty_roi_mask = pts_features.new_zeros(len(rois), dtype=torch.bool)
@@ -683,14 +683,10 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
                                                                         roi_inds, rois)
         local_roi_feats, _, local_xyz = self.occ_ae_head.encode(pts_xyz, pts_features[:, :2], pts_info,
                                                                 roi_inds, rois)
-        roi_feats_fused = self.transformer_forward(rois, roi_frame_inds, final_cluster_feats, nonempty_roi_mask)
-        tail = None
-        if local_roi_feats.requires_grad and roi_feats_fused.requires_grad and final_cluster_feats.requires_grad:
-            tail = graphed_call(self, _HeadTail, (local_roi_feats, roi_feats_fused, final_cluster_feats), slot='tail')
-        if tail is not None:
-            shape_latent, cls_score, bbox_pred = tail
-            return dict(fused_roi_feats=shape_latent, nonempty_roi_mask=nonempty_roi_mask, ori_roi_feats=local_roi_feats,
-                        cls_score=cls_score, bbox_pred=bbox_pred)
+        return final_cluster_feats, nonempty_roi_mask, local_roi_feats
+
+    def _fuse_and_predict(self, local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask):
+        """The per-RoI stages behind the temporal transformer: shape latent by ``fused_mode``, then score and box deltas."""
         if self.fused_mode == 'residual':
             shape_latent = local_roi_feats + self.conv_latent(roi_feats_fused)
         elif self.fused_mode == 'concat':
@@ -702,6 +698,45 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
         fused = self.conv_fused(torch.cat([shape_latent, second], dim=1))
         ret.update(cls_score=self.conv_cls(fused), bbox_pred=self.conv_reg(fused))
         return ret
+
+    def forward(self, pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds):
+        """ococc_bbox_head.py:319-400 -> dict(fused_roi_feats, nonempty_roi_mask, ori_roi_feats,
+        cls_score, bbox_pred)."""
+        final_cluster_feats, nonempty_roi_mask, local_roi_feats = self._encode_rois(pts_xyz, pts_features, pts_info,
+                                                                                    roi_inds, rois)
+        roi_feats_fused = self.transformer_forward(rois, roi_frame_inds, final_cluster_feats, nonempty_roi_mask)
+        tail = None
+        if local_roi_feats.requires_grad and roi_feats_fused.requires_grad and final_cluster_feats.requires_grad:
+            tail = graphed_call(self, _HeadTail, (local_roi_feats, roi_feats_fused, final_cluster_feats), slot='tail')
+        if tail is not None:
+            shape_latent, cls_score, bbox_pred = tail
+            return dict(fused_roi_feats=shape_latent, nonempty_roi_mask=nonempty_roi_mask, ori_roi_feats=local_roi_feats,
+                        cls_score=cls_score, bbox_pred=bbox_pred)
+        return self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
+
+    @torch.no_grad()
+    def forward_step(self, pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds, slot, cache):
+        """``forward`` for ONE new frame of each of n tracklets that arrive frame by frame: rois [n, 8] (column 0 the row's
+        own index), roi_frame_inds [n] the frame number of each (= the frames its slot has been stepped through), ``slot``
+        the list of the rows' cache slots, ``cache`` the TemporalCache of ``trans_enc`` (occ/layers.py).  Every stage but
+        the temporal transformer works per RoI and runs as in ``forward``; the transformer attends from the new frame to
+        the cached ones (TransformerEncoder.step), which under the causal mask of ``get_future_mask`` -- windowed by
+        test_cfg.attn_window_size as there -- is row t of the full pass over frames 0..t.  Returns the dict of ``forward``
+        for the n new RoIs.  test_cfg.allow_attn_future makes the model non-causal: ValueError; test_cfg.online_tuning
+        (test-time tuning of the latent) is not built for single steps: NotImplementedError."""
+        if self.training:
+            raise RuntimeError('OccBBoxHead.forward_step is inference only: call .eval() first')
+        if self.test_cfg.get('allow_attn_future', False):
+            raise ValueError('test_cfg.allow_attn_future lets a frame attend to later frames: such a model cannot run '
+                             'frame by frame')
+        if self.test_cfg.get('online_tuning', False):
+            raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference')
+        final_cluster_feats, nonempty_roi_mask, local_roi_feats = self._encode_rois(pts_xyz, pts_features, pts_info,
+                                                                                    roi_inds, rois)
+        pos_embed = self._pos_embed(roi_frame_inds, rois[:, 1:])
+        roi_feats_fused = self.trans_enc.step(final_cluster_feats, pos_embed, slot, cache,
+                                              self.test_cfg.get('attn_window_size', -1))
+        return self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
 
     # ------------------------------------------------------------------ temporal transformer
     def get_occ(self, local_roi_feats, rois, transform=True, ori_roi_feats=None):
@@ -753,6 +788,15 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
                 mask[i, :i - window_size + 1] = 1
         return mask
 
+    def _pos_embed(self, frame_inds, boxes, seq_first=False):
+        """frame positional encoding of frame_inds plus, with_roi_pos_encoding, the MLP of ``boxes`` [..., 7] (a callable
+        is called only then).  seq_first: frame_inds is [L, B] and the boxes are [B, L, 7]; else both are row lists."""
+        pos_embed = self.pos_enc(frame_inds)
+        if self.with_roi_pos_encoding:
+            roi_term = self.roi_pos_enc_mlp(boxes() if callable(boxes) else boxes)
+            pos_embed = pos_embed + (roi_term.transpose(0, 1) if seq_first else roi_term)
+        return pos_embed
+
     def transformer_forward_fixed_length(self, rois, roi_frame_inds, roi_feats, nonempty_roi_mask, trans_enc=None):
         """ococc_bbox_head.py:849-908."""
         rois_batch_idx = rois[:, 0]
@@ -764,10 +808,9 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
         re_feats, sb, sf = self.reorder_feats(roi_feats, roi_frame_inds, rois_batch_idx, batch_size=B)
         re_frames = self.reorder_feats(roi_frame_inds.clone(), roi_frame_inds, rois_batch_idx, sb, sf)[0].squeeze(-1)
         re_feats = re_feats.view(B, L, re_feats.shape[-1]).permute(1, 0, 2)  # [L, B, D]
-        pos_embed = self.pos_enc(re_frames.transpose(0, 1))
-        if self.with_roi_pos_encoding:
-            re_rois = self.reorder_feats(rois[:, 1:], roi_frame_inds, rois_batch_idx, sb, sf)[0]
-            pos_embed = pos_embed + self.roi_pos_enc_mlp(re_rois).transpose(0, 1)
+        pos_embed = self._pos_embed(re_frames.transpose(0, 1),
+                                    lambda: self.reorder_feats(rois[:, 1:], roi_frame_inds, rois_batch_idx, sb, sf)[0],
+                                    seq_first=True)
         if not self.training and self.test_cfg.get('allow_attn_future', False):
             future_mask = None
         else:
@@ -793,9 +836,8 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
         feats = torch.stack([pad(f) for f in feats_l], 0)  # [B, max_len, D]
         key_padding = torch.stack([torch.arange(max_len, device=feats.device) >= len(f) for f in feats_l], 0)
         frame_inds = torch.arange(max_len, device=feats.device)[None, :].repeat(len(feats_l), 1)
-        pos_embed = self.pos_enc(frame_inds.transpose(0, 1))
-        if self.with_roi_pos_encoding:
-            pos_embed = pos_embed + self.roi_pos_enc_mlp(torch.stack([pad(r) for r in rois_l], 0)).transpose(0, 1)
+        pos_embed = self._pos_embed(frame_inds.transpose(0, 1), lambda: torch.stack([pad(r) for r in rois_l], 0),
+                                    seq_first=True)
         enc = self.trans_enc if trans_enc is None else trans_enc
         out = enc(feats.permute(1, 0, 2), pos_enc=pos_embed, key_padding_mask=key_padding,
                   attn_mask=self.get_future_mask(max_len, feats.device)).transpose(0, 1)

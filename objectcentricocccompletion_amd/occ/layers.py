@@ -73,6 +73,82 @@ class _TemporalAttention(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None, None
 
 
+class TemporalCache(object):
+    """Keys and values of the frames a tracklet has been stepped through, for online inference (MultiheadAttention.step):
+    per encoder layer ``k[i]`` / ``v[i]`` f32 [slots, cap, E] on the device, one slot per tracklet that is being followed.
+    ``pos`` int32 [slots] on the device is the number of frames cached per slot, shared by all layers (the attention kernel
+    reads it, TransformerEncoder.step bumps it once per step); ``pos_host`` is its mirror on the host, a list of ints, so
+    that the bounds checks and ``reset`` need no read-back.
+
+    Memory: 2 * num_layers * cap * E * 4 bytes per slot -- for the ococcnet model (3 layers, E = 1536) at the default
+    ``cap`` = 256 (the longest sequence the attention kernels take; the reference's PositionalEncoding stops at 200) that
+    is 9.4 MB per slot, 604 MB for 64 slots.  A tracklet longer than ``cap`` frames does not fit: the step raises."""
+
+    def __init__(self, num_layers, slots, embed_dim, device, cap=256):
+        from .. import _lib as L
+        device = torch.device(device)   # (a CPU cache can be built and kept account of; every step on it raises)
+        if not (1 <= int(cap) <= 256):
+            raise L.OcoccError(f'TemporalCache: cap {cap} outside 1..256, the longest sequence the attention kernels take')
+        if int(slots) < 1 or int(num_layers) < 1:
+            raise L.OcoccError('TemporalCache: at least one slot and one layer')
+        self.num_layers, self.slots, self.cap, self.embed_dim = int(num_layers), int(slots), int(cap), int(embed_dim)
+        self.k = [torch.zeros((self.slots, self.cap, self.embed_dim), dtype=torch.float32, device=device)
+                  for _ in range(self.num_layers)]
+        self.v = [torch.zeros_like(k) for k in self.k]
+        self.pos = torch.zeros((self.slots,), dtype=torch.int32, device=device)
+        self.pos_host = [0] * self.slots
+
+    @property
+    def device(self):
+        return self.pos.device
+
+    def nbytes(self):
+        return 2 * self.num_layers * self.slots * self.cap * self.embed_dim * 4
+
+    def check_step(self, slots):
+        """the host-side checks of one step over the slot list ``slots``: in range, distinct, room for one more frame"""
+        from .. import _lib as L
+        slots = [int(s) for s in slots]
+        if len(set(slots)) != len(slots):
+            raise L.OcoccError(f'TemporalCache: duplicate slots in one step: {sorted(slots)}')
+        for s in slots:
+            if not 0 <= s < self.slots:
+                raise L.OcoccError(f'TemporalCache: slot {s} outside 0..{self.slots - 1}')
+            if self.pos_host[s] >= self.cap:
+                raise L.OcoccError(f'TemporalCache: slot {s} already holds cap = {self.cap} frames; a tracklet longer than '
+                                   'the cache is not supported (reset the slot or build the cache with a larger cap <= 256)')
+        return slots
+
+    def advance(self, slots, slot_dev):
+        """one more frame in every slot of ``slots`` (``slot_dev``: the same list as an int32 / int64 device tensor)"""
+        self.pos.index_add_(0, slot_dev.long(), torch.ones_like(slot_dev, dtype=torch.int32))
+        for s in slots:
+            self.pos_host[s] += 1
+
+    def reset(self, slots=None):
+        """forget the frames of ``slots`` (all when None): the slot can follow a new tracklet.  The cached rows are left
+        as they are -- nothing reads a row at or past ``pos``."""
+        from ..tracklet import host_index
+        if slots is None:
+            self.pos.zero_()
+            self.pos_host = [0] * self.slots
+            return
+        slots = [int(s) for s in slots]
+        for s in slots:
+            if not 0 <= s < self.slots:
+                from .. import _lib as L
+                raise L.OcoccError(f'TemporalCache: slot {s} outside 0..{self.slots - 1}')
+        if slots:
+            self.pos.index_fill_(0, host_index(slots, self.pos.device), 0)
+        for s in slots:
+            self.pos_host[s] = 0
+
+
+def _eval_only(module, what):
+    if module.training:
+        raise RuntimeError(f'{what} is inference only (no dropout, no backward pass): call .eval() first')
+
+
 class PositionalEncoding(nn.Module):
     def __init__(self, d_model: int, max_len: int = 200):
         super().__init__()
@@ -153,6 +229,33 @@ class MultiheadAttention(nn.Module):
         ctx = gemm.bmm(prob, self._heads(v, S)).transpose(0, 1).reshape(L * B, E)
         return gemm.linear(ctx, self.out_proj.weight, self.out_proj.bias).view(L, B, E), None
 
+    @torch.no_grad()
+    def step(self, x_qk, x_v, slot, cache_k, cache_v, pos, window=-1):
+        """One new frame per tracklet against the cached ones: x_qk, x_v [n, E] (this frame's src + pos and src),
+        ``slot`` int32 [n] the cache slot of each row, cache_k / cache_v [slots, cap, E] this layer's cache, ``pos`` int32
+        [slots] the frames cached per slot.  q and k leave one product with the first 2E rows of in_proj as in ``forward``;
+        ococc_temporal_attention_step_f32 appends k and v at row pos[slot] and attends to the frames lo..pos[slot]
+        (``window`` > 0: the last ``window`` frames, as get_future_mask windows the past); out_proj follows.  ``pos`` is
+        left as it is.  No fall-back: arguments the kernel does not take raise."""
+        from .. import _lib as L
+        _eval_only(self, 'MultiheadAttention.step')
+        L.require_device(x_qk, x_v, slot, cache_k, cache_v, pos)
+        n, E = x_qk.shape
+        assert E == self.embed_dim and x_v.shape == (n, E) and slot.shape == (n,) and slot.dtype == torch.int32
+        assert pos.dtype == torch.int32 and cache_k.shape == cache_v.shape and cache_k.shape[2] == E
+        assert cache_k.dtype == cache_v.dtype == torch.float32 and cache_k.is_contiguous() and cache_v.is_contiguous()
+        assert pos.shape == (cache_k.shape[0],)
+        w, b = self.in_proj_weight, self.in_proj_bias
+        qk = gemm.linear(x_qk.float(), w[:2 * E], b[:2 * E])
+        v = gemm.linear(x_v.float(), w[2 * E:], b[2 * E:])
+        q, k = qk[:, :E], qk[:, E:]
+        ctx = torch.empty((n, E), dtype=torch.float32, device=qk.device)
+        L.check(L.lib.ococc_temporal_attention_step_f32(
+            q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), slot.data_ptr(), pos.data_ptr(),
+            cache_k.data_ptr(), cache_v.data_ptr(), n, cache_k.shape[0], cache_k.shape[1], self.num_heads, self.head_dim,
+            float(self.head_dim) ** -0.5, int(window), ctx.data_ptr(), ctx.stride(0), L.stream()), 'temporal_attention_step')
+        return gemm.linear(ctx, self.out_proj.weight, self.out_proj.bias)
+
 
 class SimpleEncoderLayer(nn.Module):
     """Post-LN encoder layer with q = k = src + pos, v = src (layers.py:35-87): attention block, then feed-forward block,
@@ -187,6 +290,15 @@ class SimpleEncoderLayer(nn.Module):
         x = self._residual_norm(self.norm1, src, attended, self.dropout1)
         return self._residual_norm(self.norm2, x, self._feed_forward(x), self.dropout2)
 
+    @torch.no_grad()
+    def step(self, src, pos_enc, slot, cache_k, cache_v, pos, window=-1):
+        """``forward`` for one new frame per tracklet, src / pos_enc [n, E], against this layer's cache
+        (MultiheadAttention.step): the same post-LN structure, the dropouts are the identity (inference only)."""
+        _eval_only(self, 'SimpleEncoderLayer.step')
+        attended = self.self_attn.step(self.with_pos_embed(src, pos_enc), src, slot, cache_k, cache_v, pos, window)
+        x = self._residual_norm(self.norm1, src, attended, self.dropout1)
+        return self._residual_norm(self.norm2, x, self._feed_forward(x), self.dropout2)
+
 
 def _get_clones(module, N):
     return nn.ModuleList([copy.deepcopy(module) for _ in range(N)])
@@ -204,4 +316,27 @@ class TransformerEncoder(nn.Module):
         x = src
         for layer in self.layers:
             x = layer(x, key_padding_mask=key_padding_mask, pos_enc=pos_enc, attn_mask=attn_mask)
+        return x
+
+    @torch.no_grad()
+    def step(self, src, pos_enc, slot, cache, window=-1):
+        """One new frame for each of n tracklets: src, pos_enc [n, E]; ``slot``: the cache slot of each row, a list of
+        ints (a tensor is read back: the bounds checks run on the host); ``cache`` a TemporalCache with one (k, v) pair
+        per layer.  Row i equals row pos[slot[i]] of ``forward`` over the frames 0..pos[slot[i]] of that tracklet under the
+        future mask (windowed by ``window`` > 0).  Bumps ``cache.pos`` and its host mirror once, after the last layer.
+        The host-side checks (duplicate slots, a step past ``cache.cap``, CPU tensors) raise before anything is launched."""
+        from .. import _lib as L
+        from ..tracklet import host_index
+        _eval_only(self, 'TransformerEncoder.step')
+        if cache.num_layers != self.num_layers:
+            raise L.OcoccError(f'TemporalCache of {cache.num_layers} layers for an encoder of {self.num_layers}')
+        slots = cache.check_step(slot.tolist() if torch.is_tensor(slot) else slot)
+        if len(slots) != src.shape[0]:
+            raise L.OcoccError(f'{len(slots)} slots for {src.shape[0]} rows')
+        L.require_device(src, pos_enc, cache.pos)
+        slot_dev = host_index(slots, src.device, dtype=torch.int32)
+        x = src
+        for i, layer in enumerate(self.layers):
+            x = layer.step(x, pos_enc, slot_dev, cache.k[i], cache.v[i], cache.pos, window)
+        cache.advance(slots, slot_dev)
         return x

@@ -296,10 +296,13 @@ class TrackletRandomFlip(object):
 @PIPELINES.register_module()
 class TrackletPoseTransform(object):
     """Bring every frame's points and boxes from that frame's ego pose into the ego frame of the tracklet's middle
-    frame (tracklet_pipelines.py:228-303).  tracklet.pose_list holds the per-frame ego -> world 4x4 poses."""
+    frame (tracklet_pipelines.py:228-303).  tracklet.pose_list holds the per-frame ego -> world 4x4 poses.
+    ``shared_frame='first'`` (this package's): the FIRST frame's ego frame instead -- the one frame a caller that receives
+    the tracklet frame by frame knows from the start (online inference, tools/test.py --online)."""
 
-    def __init__(self, concat=True, centering=False):
-        self.concat, self.centering = concat, centering
+    def __init__(self, concat=True, centering=False, shared_frame='middle'):
+        assert shared_frame in ('middle', 'first'), shared_frame
+        self.concat, self.centering, self.shared_frame = concat, centering, shared_frame
 
     @staticmethod
     def points_frame_transform(src_points, src_pose, tgt_pose, tgt_pose_inv=None):
@@ -313,7 +316,8 @@ class TrackletPoseTransform(object):
         poses = trk.pose_list
         assert getattr(trk, 'shared_pose', None) is None
         assert len(points) == len(trk) == len(poses)
-        center_pose = poses[len(poses) // 2]
+        mid = len(poses) // 2 if self.shared_frame == 'middle' else 0
+        center_pose = poses[mid]
         trk.frame_transform(center_pose)
         for t in _candidates(results):
             t.frame_transform(center_pose)
@@ -321,7 +325,8 @@ class TrackletPoseTransform(object):
         points = [torch.cat([self.points_frame_transform(p[:, :3], pose, None, inv), p[:, 3:]], 1)
                   for pose, p in zip(poses, points)]
         if self.centering:  # translation only: the middle frame's box centre becomes the origin
-            translation = -1 * trk.boxes[len(trk) // 2:len(trk) // 2 + 1, :3].clone()
+            c = len(trk) // 2 if self.shared_frame == 'middle' else 0
+            translation = -1 * trk.boxes[c:c + 1, :3].clone()
             for p in points:
                 p[:, :3] += translation.to(p)
             trk.translate(translation)

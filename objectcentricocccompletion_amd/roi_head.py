@@ -13,6 +13,7 @@ from torch import nn
 from ._lib import const_tensor
 from .bbox import points_box_to_box, rotation_3d_in_axis
 from .occ import occ_ops
+from .occ.layers import TemporalCache
 from .registry import BBOX_ASSIGNERS, DETECTORS, HEADS, ROI_EXTRACTORS
 from .tracklet import SamplingResult, Tracklet
 
@@ -59,6 +60,26 @@ def check_save_gt_occ_cfg(test_cfg):
         raise ValueError('test_cfg.save_gt_occ with test_cfg.tta: the augmented frames are not the frames to export')
     if not test_cfg.get('gt_occ_save_root', None):
         raise ValueError('test_cfg.save_gt_occ needs test_cfg.gt_occ_save_root, the directory the files go to')
+
+
+class OnlineState(object):
+    """What frame-by-frame inference keeps between steps (TrackletRoIHeadOCC.online_begin): ``cache``, the TemporalCache of
+    the temporal transformer, and ``frames``, the steps taken per slot (a list of ints on the host: the cache's own
+    ``pos_host``, since a slot's frame index is the number of frames it has cached)."""
+
+    def __init__(self, cache):
+        self.cache = cache
+
+    @property
+    def frames(self):
+        return self.cache.pos_host
+
+    @property
+    def slots(self):
+        return self.cache.slots
+
+    def reset(self, slots=None):
+        self.cache.reset(slots)
 
 
 @HEADS.register_module()
@@ -290,6 +311,11 @@ class TrackletRoIHeadOCC(nn.Module):
 
     def _bbox_forward(self, pts_xyz, pts_feats, pts_batch_idx, pts_frame_inds, rois, roi_scores, roi_frame_inds):
         """Pool the points of every RoI, append the RoI score, run the head (:828-878)."""
+        pooled = self._pool_points(pts_xyz, pts_feats, pts_batch_idx, pts_frame_inds, rois, roi_scores, roi_frame_inds)
+        return self.bbox_head(*pooled, rois, roi_frame_inds)
+
+    def _pool_points(self, pts_xyz, pts_feats, pts_batch_idx, pts_frame_inds, rois, roi_scores, roi_frame_inds):
+        """The points of every RoI with the RoI score / corner offsets appended: (xyz, features, pooling info, RoI index)."""
         assert pts_xyz.size(0) == pts_feats.size(0) == pts_batch_idx.size(0) == pts_frame_inds.size(0)
         inds, roi_inds, info = self.roi_extractor(pts_xyz[:, :3], pts_batch_idx, pts_frame_inds, rois[:, :8],
                                                   roi_frame_inds)
@@ -298,7 +324,7 @@ class TrackletRoIHeadOCC(nn.Module):
             new_feats = torch.cat([new_feats, roi_scores[roi_inds].unsqueeze(1)], 1)
         if self.with_roi_corners:
             new_feats = torch.cat([new_feats, self.roi_corner_offsets(rois, roi_inds, new_xyz).to(new_feats.dtype)], 1)
-        return self.bbox_head(new_xyz, new_feats, info, roi_inds, rois, roi_frame_inds)
+        return new_xyz, new_feats, info, roi_inds
 
     @staticmethod
     def roi_corner_offsets(rois, roi_inds, xyz):
@@ -327,16 +353,31 @@ class TrackletRoIHeadOCC(nn.Module):
         copy of the proposal updated through Tracklet.update_from_prediction (RoIs without points keep their
         proposal box and score); with test_occ_iou the per-RoI occupancy intersection / union counts follow."""
         assert len(tracklet_list) == 1, 'only support batch size 1'
-        gt_rois = gt_occ_list = gt_occ_score_list = None
-        if gt_candidates_list is not None:
-            gts, gt_occ_list, gt_occ_score_list = self._select_one2one_candidates(
-                tracklet_list, gt_candidates_list, gt_occs_list, gt_occ_scores_list)
-            gt_rois = self.get_gt_rois(tracklet_list, gts)
+        if self.test_cfg.get('online', False):   # (this package's key: frame by frame over a K/V cache, the same result)
+            return self.simple_test_online(pts_xyz, pts_feats, pts_batch_idx, pts_frame_inds, img_metas, tracklet_list,
+                                           gt_candidates_list, gt_occs_list, gt_occ_scores_list)
+        gt_rois, gt_occ_list, gt_occ_score_list = self._test_gt_rois(tracklet_list, gt_candidates_list, gt_occs_list,
+                                                                     gt_occ_scores_list)
         rois, roi_frame_inds, cls_preds, labels_3d = self.tracklets2rois(tracklet_list)
         res = self._bbox_forward(pts_xyz, pts_feats, pts_batch_idx, pts_frame_inds, rois, cls_preds, roi_frame_inds)
         decoded = self.bbox_head.get_bboxes_from_tracklet(rois, res['cls_score'], res['bbox_pred'],
                                                           res['nonempty_roi_mask'], labels_3d, cls_preds, img_metas,
                                                           gt_rois=gt_rois, cfg=self.test_cfg)
+        return self._test_results(tracklet_list, decoded, res, rois, roi_frame_inds, img_metas, gt_rois, gt_occ_list,
+                                  gt_occ_score_list, pts_xyz, pts_batch_idx, pts_frame_inds)
+
+    def _test_gt_rois(self, tracklet_list, gt_candidates_list, gt_occs_list, gt_occ_scores_list):
+        """(GT boxes aligned to the proposal [R, 8] with the matched flag first, occupancy labels, their scores) of the
+        candidate selected for the tracklet; three Nones without candidates"""
+        if gt_candidates_list is None:
+            return None, None, None
+        gts, gt_occ_list, gt_occ_score_list = self._select_one2one_candidates(
+            tracklet_list, gt_candidates_list, gt_occs_list, gt_occ_scores_list)
+        return self.get_gt_rois(tracklet_list, gts), gt_occ_list, gt_occ_score_list
+
+    def _test_results(self, tracklet_list, decoded, res, rois, roi_frame_inds, img_metas, gt_rois, gt_occ_list,
+                      gt_occ_score_list, pts_xyz, pts_batch_idx, pts_frame_inds):
+        """simple_test behind the head: the refined tracklet, the occupancy counts, the exports"""
         out_tracklets = []
         for i, trk in enumerate(tracklet_list):
             new = trk.clone()
@@ -357,6 +398,91 @@ class TrackletRoIHeadOCC(nn.Module):
             check_save_gt_occ_cfg(self.test_cfg)
             self.save_gt_occ_from_tracklet(tracklet_list, res, gt_rois, gt_occ_list)
         return [out]
+
+    # ------------------------------------------------------------------ online inference
+    def online_begin(self, slots, device, cap=256):
+        """State for frame-by-frame inference over ``slots`` tracklets at a time (simple_test_step): the TemporalCache of
+        the head's temporal transformer -- 2 * layers * cap * E * 4 bytes per slot, 9.4 MB for the ococcnet model at the
+        default cap = 256 -- whose per-slot frame counter is also the frame index the next step of the slot gets.
+        ``state.reset(slots)`` hands slots to new tracklets."""
+        enc = self.bbox_head.trans_enc
+        return OnlineState(TemporalCache(enc.num_layers, slots, self.bbox_head.roi_feature_channels, device, cap=cap))
+
+    @torch.no_grad()
+    def simple_test_step(self, pts_xyz, pts_feats, pts_batch_idx, boxes, scores, labels, slot, state, gt_rois=None):
+        """One new frame of n tracklets: the frame's points (pts_batch_idx: the ROW 0..n-1 a point belongs to), the
+        proposal boxes [n, 7], scores [n] and labels [n] of this frame, ``slot`` the list of the rows' slots in ``state``
+        (online_begin).  Pools the frame's points into the frame's boxes, appends the RoI score / corner offsets as
+        _bbox_forward does, runs OccBBoxHead.forward_step (the temporal transformer reads the slots' cached frames) and
+        decodes with get_bboxes_from_tracklet.  The frame index of a row is the number of steps its slot has taken, which is
+        what tracklets2rois gives offline.  Returns dict(boxes [n, 7], scores [n], labels [n], valid [n] -- RoIs without
+        points are flagged, the caller keeps their proposal --, fused_roi_feats [n, D], ori_roi_feats [n, D]).
+
+        ALL frames of a tracklet must be given in ONE fixed coordinate frame: the encoders see absolute coordinates, so the
+        cached keys and values belong to the frame they were computed in.  (The offline pipeline moves a tracklet into the
+        ego pose of its middle frame, which an online caller cannot know; the first frame's pose serves.)
+
+        Reported on the host before anything is launched: a step past the cache's cap and duplicate or out-of-range
+        slots (OcoccError), CPU tensors (OcoccError), training mode (RuntimeError)."""
+        from . import _lib as L
+        from .tracklet import host_index
+        if self.training:
+            raise RuntimeError('simple_test_step is inference only: call .eval() first')
+        slots = state.cache.check_step(slot)
+        L.require_device(pts_xyz, pts_feats, pts_batch_idx, boxes, scores, labels, state.cache.pos)
+        n, dev = boxes.size(0), boxes.device
+        if len(slots) != n or scores.size(0) != n or labels.size(0) != n:
+            raise L.OcoccError(f'{len(slots)} slots, {scores.size(0)} scores, {labels.size(0)} labels for {n} boxes')
+        if pts_xyz.size(0) == 0:   # (a frame without points: one zero row, as the detector gives an empty sample)
+            pts_xyz, pts_feats, pts_batch_idx = TrackletDetectorOCC.fake_points_for_empty_input(
+                [pts_xyz, pts_feats, pts_batch_idx])
+        rois = bbox3d2roi([boxes[i:i + 1, :7] for i in range(n)])     # column 0: the row's own index
+        frames = host_index([state.cache.pos_host[s] for s in slots], dev)
+        same = torch.zeros_like(frames)                                  # (the points are this frame's: one frame key)
+        pooled = self._pool_points(pts_xyz, pts_feats, pts_batch_idx.long(), torch.zeros_like(pts_batch_idx, dtype=torch.long),
+                                   rois, scores, same)
+        res = self.bbox_head.forward_step(*pooled, rois, frames, slots, state.cache)
+        one = torch.cat([torch.zeros_like(rois[:, :1]), rois[:, 1:]], 1)   # (one group: get_bboxes splits by column 0)
+        out_boxes, out_scores, out_labels, valid = self.bbox_head.get_bboxes_from_tracklet(
+            one, res['cls_score'], res['bbox_pred'], res['nonempty_roi_mask'], labels, scores, None, gt_rois=gt_rois,
+            cfg=self.test_cfg)[0]
+        return dict(boxes=out_boxes, scores=out_scores, labels=out_labels, valid=valid,
+                    fused_roi_feats=res['fused_roi_feats'], ori_roi_feats=res['ori_roi_feats'])
+
+    @torch.no_grad()
+    def simple_test_online(self, pts_xyz, pts_feats, pts_batch_idx, pts_frame_inds, img_metas, tracklet_list,
+                           gt_candidates_list=None, gt_occs_list=None, gt_occ_scores_list=None, **kwargs):
+        """simple_test computed the way the method is deployed: the tracklet is fed to simple_test_step frame by frame in
+        one slot of a fresh state, then test_occ / the exports run on the concatenated per-step features.  Same arguments,
+        same result (the temporal transformer is causal: frame t never saw the later frames offline either); what
+        simple_test does when test_cfg.online is set.  The points are taken in the coordinate frame they come in."""
+        from . import _lib as L
+        from .tracklet import host_index
+        assert len(tracklet_list) == 1, 'only support batch size 1'
+        if self.test_cfg.get('tta', None) is not None:
+            raise NotImplementedError('test_cfg.online with test_cfg.tta')
+        num = len(tracklet_list[0])
+        if num > 256:
+            raise L.OcoccError(f'a tracklet of {num} frames: the K/V cache of online inference holds at most 256')
+        L.require_device(pts_xyz, pts_feats, pts_batch_idx, pts_frame_inds)
+        gt_rois, gt_occ_list, gt_occ_score_list = self._test_gt_rois(tracklet_list, gt_candidates_list, gt_occs_list,
+                                                                     gt_occ_scores_list)
+        rois, roi_frame_inds, cls_preds, labels_3d = self.tracklets2rois(tracklet_list)
+        state = self.online_begin(1, rois.device, cap=max(num, 1))
+        # the points frame by frame: one stable sort, the counts in one read-back
+        order = torch.sort(pts_frame_inds, stable=True).indices
+        counts = torch.bincount(pts_frame_inds, minlength=num).tolist()
+        assert len(counts) == num, 'a point lies in a frame past the tracklet'
+        steps = []
+        for t, sel in enumerate(order.split(counts)):
+            steps.append(self.simple_test_step(
+                pts_xyz[sel], pts_feats[sel], torch.zeros_like(pts_batch_idx[sel]), rois[t:t + 1, 1:8], cls_preds[t:t + 1],
+                labels_3d[t:t + 1], [0], state, gt_rois=None if gt_rois is None else gt_rois[t:t + 1]))
+        cat = lambda k: torch.cat([s[k] for s in steps], 0)
+        res = dict(fused_roi_feats=cat('fused_roi_feats'), ori_roi_feats=cat('ori_roi_feats'), nonempty_roi_mask=cat('valid'))
+        decoded = [(cat('boxes'), cat('scores'), cat('labels'), cat('valid'))]
+        return self._test_results(tracklet_list, decoded, res, rois, roi_frame_inds, img_metas, gt_rois, gt_occ_list,
+                                  gt_occ_score_list, pts_xyz, pts_batch_idx, pts_frame_inds)
 
     @torch.no_grad()
     def save_occ_from_tracklet(self, tracklet_list, bbox_results, gt_tracklet_list=None, gt_occ_list=None,
@@ -613,6 +739,9 @@ class TrackletDetectorOCC(nn.Module):
         its boxes are mapped back through the augmentation (TrackletRoIHeadOCC.inverse_aug) and the per-frame
         boxes are merged with Tracklet.merge_augs under test_cfg['tta'].  Returns one merged Tracklet per sample."""
         assert len(points) == len(img_metas) == len(pts_frame_inds) == len(tracklet)
+        if self.roi_head.test_cfg.get('online', False):
+            raise NotImplementedError('test_cfg.online with test-time augmentation: every augmentation would need its own '
+                                      'K/V cache; refine the augmented tracklets offline')
         tta = self.roi_head.test_cfg['tta']
         per_aug = []
         for p, meta, inds, trks in zip(points, img_metas, pts_frame_inds, tracklet):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Test / evaluation entry point with the CLI of the reference's tools/test.py (:23-87):
-    python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--save-occ DIR] [--save-gt-occ DIR] [--eval iou waymo waymo_native] [--matcher {score_first,hungarian}] [--format-only]
+    python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--save-occ DIR] [--save-gt-occ DIR] [--online] [--eval iou waymo waymo_native] [--matcher {score_first,hungarian}] [--format-only]
                          [--eval-options k=v ...] [--cfg-options k=v ...] [--launcher {none,pytorch}]
                          [--tmpdir DIR] [--gpu-collect] [--local_rank N]
 The test dataset is the config's data.test (the reference's data/waymo layout); with --data-root DIR it reads the tree
@@ -67,6 +67,10 @@ def parse_args(argv=None):
                     help='export the annotated occupancy of the matched ground-truth tracks, cropped to the proposal boxes: '
                     'the same layout and format under DIR, score 1, frames with a GT box only (sets '
                     'test_cfg.gt_occ_save_root and test_cfg.save_gt_occ)')
+    ap.add_argument('--online', action='store_true',
+                    help='refine every tracklet frame by frame over a temporal K/V cache, the way the method is deployed '
+                    '(sets test_cfg.online; the tracklet is moved into the ego frame of its FIRST frame, the one an online '
+                    'caller knows); metrics and files as without it')
     args = ap.parse_args(argv)
     if 'LOCAL_RANK' not in os.environ:
         os.environ['LOCAL_RANK'] = str(args.local_rank)
@@ -105,6 +109,10 @@ def build_test_dataset_cfg(cfg, args):
         ds_cfg.update(data_root=args.data_root, ann_file=j(args.candidates), tracklet_proposals_file=j(args.proposals),
                       occ_anno_root=j(args.occ_root), pose_file=j('poses.pkl'))
     ds_cfg.pop('samples_per_gpu', None)
+    if getattr(args, 'online', False):
+        # the frames of a tracklet must share ONE coordinate frame known at its first step: the first frame's ego pose
+        ds_cfg['pipeline'] = [dict(step, shared_frame='first') if step.get('type') == 'TrackletPoseTransform' else step
+                              for step in ds_cfg['pipeline']]
     return ds_cfg
 
 
@@ -167,6 +175,8 @@ def main(argv=None):
     if args.save_gt_occ:
         os.makedirs(args.save_gt_occ, exist_ok=True)
         config.merge_from_dict(cfg, {'model.test_cfg.gt_occ_save_root': args.save_gt_occ, 'model.test_cfg.save_gt_occ': True})
+    if args.online:
+        config.merge_from_dict(cfg, {'model.test_cfg.online': True})
     rank, world, local_rank = init_dist(args.dist_backend) if args.launcher == 'pytorch' else (0, 1, 0)
     dev = torch.device('cuda', local_rank % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)

@@ -59,12 +59,28 @@ CASES = [  # rows, k, n, add, bias, head
     (129, 512, 1024, False, False, False), (2500, 512, 1024, False, True, False),
     (63, 1024, 1024, False, False, True), (3001, 1024, 1024, False, False, True),
     (700, 1024, 512, False, False, True), (515, 256, 512, True, False, True), (300, 128, 1024, False, False, False),
+    # more tiles than workgroups (second_trip_rows): the next tile's rows are prefetched into the LDS tile while this
+    # tile's epilogue runs -- through registers (K = 64), by DMA (K = 512, 1024)
+    ('second-trip', 64, 512, True, False, False), ('second-trip', 512, 1024, False, True, False),
+    ('second-trip', 1024, 1024, False, False, True),
 ]
+
+
+def second_trip_rows(dev):
+    """(rows, CU count): 64 (CU + 1) + 27 rows = CU + 2 tiles for the persistent grid of min(tiles, CU) workgroups: two
+    of them take a second tile, one of them the ragged one of 27 rows."""
+    cu = torch.cuda.get_device_properties(dev).multi_processor_count
+    return 64 * (cu + 1) + 27, cu
 
 
 @pytest.mark.parametrize('rows,k,n,add,bias,head', CASES)
 def test_mlp_layer_vs_oracle(dev, rows, k, n, add, bias, head):
     from objectcentricocccompletion_amd.occ import fused_mlp as fm
+    ref_dev = torch.device('cpu')
+    if rows == 'second-trip':
+        rows, cu = second_trip_rows(dev)
+        assert (rows + 63) // 64 > cu and rows % 64 == 27
+        ref_dev = dev   # (the float64 oracle of ~1.6e4 rows: on the device)
     g = torch.Generator().manual_seed(rows + k + n)
     x = bf16(torch.randn(rows, k, generator=g))
     W = torch.randn(n, k, generator=g) / k ** 0.5
@@ -79,8 +95,10 @@ def test_mlp_layer_vs_oracle(dev, rows, k, n, add, bias, head):
     to = lambda t: None if t is None else t.to(dev)
     y, ho = fm.mlp_layer(x.to(dev), wf, n, to(gam), to(bet), 1e-3, 'gelu', bias=to(b), add_rows=to(addrows), add_index=to(idx),
                          head_weight=to(hw), head_bias=to(hb), want_y=True)
-    ey, eh = D.mlp_layer(x, W, gam, bet, 1e-3, bias=b, add=addrows, idx=idx, head_w=hw, head_b=hb, rounding='bf16')
-    y = y.cpu().double()
+    at = lambda t: None if t is None else t.to(ref_dev)
+    ey, eh = D.mlp_layer(at(x), at(W), at(gam), at(bet), 1e-3, bias=at(b), add=at(addrows), idx=at(idx), head_w=at(hw),
+                         head_b=at(hb), rounding='bf16')
+    y = y.to(ref_dev).double()
     # north_star: 1e-3 norm-wise.  Element-wise a value may land on the neighbouring bf16 (f32 vs f64 sums and the
     # 1.5e-7 erf polynomial in front of the rounding): one bf16 step, relative to the LayerNorm output's scale (GELU
     # shrinks negative values but not their absolute error)
@@ -88,11 +106,11 @@ def test_mlp_layer_vs_oracle(dev, rows, k, n, add, bias, head):
     assert bool(((y - ey).abs() <= BF16_ULP * (ey.abs() + 0.05) + 1e-6).all()), float((y - ey).abs().max())
     assert float(((y - ey) == 0).double().mean()) > 0.97
     if head:
-        ho = ho.cpu().double()
+        ho = ho.to(ref_dev).double()
         assert float((ho - eh).norm() / eh.norm()) < 1e-3
         only, ho2 = fm.mlp_layer(x.to(dev), wf, n, to(gam), to(bet), 1e-3, 'gelu', bias=to(b), add_rows=to(addrows),
                                  add_index=to(idx), head_weight=to(hw), head_bias=to(hb), want_y=False)
-        assert only is None and torch.equal(ho2.cpu().double(), ho)   # same arithmetic with the activation left on chip
+        assert only is None and torch.equal(ho2.to(ref_dev).double(), ho)   # same arithmetic with the activation left on chip
 
 
 def test_mlp_layer_without_norm_and_empty(dev):

@@ -1136,6 +1136,24 @@ int ococc_temporal_attention_step_f32(const float* q, int64_t ldq, const float* 
                                       int32_t n, int32_t slots, int32_t cap, int32_t heads, int32_t head_dim, float scale,
                                       int32_t window, float* out, int64_t ldo, ococc_stream_t stream);
 
+/* A9, online, past 256 frames  the same kernel template with the scores kept in LDS (csrc/causal_attn_step.hip): the
+ * step of nn.MultiheadAttention as SimpleEncoderLayer calls it (mmdet3d/models/occ/layers.py:35-87) under the causal mask
+ * of OccBBoxHead.get_future_mask (ococc_bbox_head.py:1034-1043; test_cfg.attn_window_size) for tracklets longer than the
+ * 256 frames the export above takes.  Arguments as above, and ``ring`` after ``window``:
+ *   ring == 0: frame f of a slot lives in cache row f; cap <= 4096; a row with pos[slot] >= cap is skipped.
+ *   ring != 0: frame f lives in cache row f % cap, and 1 <= window <= cap is required: the row of frame t = pos[slot]
+ *              overwrites frame t - cap, which the window no longer reads, so pos[slot] may grow to 2^31 - 1.
+ * out[i] = softmax(scale q[i] . K[frames lo .. t]) V[frames lo .. t] per head, lo = max(0, t - window + 1) (window <= 0: 0).
+ * With more than 256 keys a thread owns the scores tid, tid + 256, ...; for <= 256 keys the arithmetic is, operation for
+ * operation, that of ococc_temporal_attention_step_f32.  pos is not advanced.  cap > 4096, ring with window < 1 or
+ * window > cap, n > slots, head_dim % 4 != 0 or > 384, null pointers, unaligned rows: OCOCC_EINVAL, nothing launched.
+ * No dropout (inference); no atomics; deterministic. */
+int ococc_temporal_attention_step_long_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk, const float* v_new,
+                                           int64_t ldv, const int32_t* slot, const int32_t* pos, float* k_cache,
+                                           float* v_cache, int32_t n, int32_t slots, int32_t cap, int32_t heads,
+                                           int32_t head_dim, float scale, int32_t window, int32_t ring, float* out,
+                                           int64_t ldo, ococc_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * A11 / A10, fused  the occupancy decoder's per-query MLP, one launch per layer (or one for the whole MLP):
  *   y = dropout(act(LayerNorm(x W^T + bias + add_rows[add_index]))),  optionally  head = y . head_weight + head_bias

@@ -11,6 +11,15 @@
 // of the workgroup; the softmax over <= 256 scores by wave butterflies; the product with V with the keys dealt round-robin to
 // the 16 lane groups and the 16 partial rows summed in a fixed order.  f32 throughout, no atomics, no dropout (inference only).
 // The kernel does not advance pos: every encoder layer has a cache of its own and shares pos, the caller bumps it once.
+//
+// Two instances of ONE kernel template, so the arithmetic lives in one place:
+//   ococc_temporal_attention_step_f32       kMaxS = 256: one score per thread, frame f in cache row f, a slot is full at cap.
+//   ococc_temporal_attention_step_long_f32  kMaxS = 4096 (kLongMaxS): the scores stay in LDS (16 KB) and a thread owns the
+//     scores tid, tid + 256, ...; it takes their maximum and their sum locally before the wave butterflies, so for <= 256
+//     keys it does operation for operation what the first instance does.  ``ring``: frame f lives in cache row f % cap, the
+//     new frame t overwrites frame t - cap, which a window <= cap no longer reads -- a windowed model follows a tracklet of
+//     any length (pos up to 2^31 - 1) in ``window`` rows per slot.  Without ``ring`` a model that attends to all history
+//     gets up to 4096 cached frames.  A workgroup still reads and writes only its own head's column slice.
 #include "common.hpp"
 
 namespace {
@@ -18,6 +27,7 @@ namespace {
 constexpr int kST = 256;      // threads per workgroup
 constexpr int kSK = 16;       // keys per pass (16 lanes each)
 constexpr int kSMaxS = 256;   // cache rows per slot at most (kAMaxS of causal_attn.hip)
+constexpr int kLongMaxS = 4096;   // ... of the long instance: 16 KB of scores in LDS, 46 KB in all
 constexpr int kSNJ = 6;       // float4 column groups per thread: D <= 16 * 4 * kSNJ = 384 (kANJ of causal_attn.hip)
 constexpr int kSMaxD = 64 * kSNJ;
 
@@ -33,6 +43,7 @@ struct StepArgs {
   int32_t n, slots, cap, H, D;
   float scale;
   int32_t window;
+  int32_t ring;          // long instance only: frame f in cache row f % cap
   float* out;
   int64_t ldo;
 };
@@ -46,20 +57,26 @@ __device__ __forceinline__ float sum16(float v) {
   return v;
 }
 
+template <int kMaxS>
 __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
+  constexpr bool kLong = kMaxS > kST;   // several scores per thread, ring addressing
   __shared__ __attribute__((aligned(16))) float sq[kSMaxD];          // the query row, scaled
   __shared__ __attribute__((aligned(16))) float sk[kSMaxD];          // the new key
   __shared__ __attribute__((aligned(16))) float sv[kSMaxD];          // the new value
-  __shared__ float ss[kSMaxS];                                       // scores -> probabilities of keys lo .. t
+  __shared__ float ss[kMaxS];                                        // scores -> probabilities of keys lo .. t
   __shared__ float red[2 * (kST / 64)];
   __shared__ __attribute__((aligned(16))) float part[kSK * kSMaxD];  // the 16 partial context rows
   const int i = blockIdx.x, h = blockIdx.y;
   const int s = a.slot[i];
   if (s < 0 || s >= a.slots) return;   // (the host checks both; a host bug must not write outside the cache)
   const int t = a.pos[s];
-  if (t < 0 || t >= a.cap) return;
+  const bool ring = kLong && a.ring != 0;
+  if (t < 0 || (!ring && t >= a.cap)) return;
   const int lo = a.window > 0 && t - a.window + 1 > 0 ? t - a.window + 1 : 0;
   const int nk = t - lo + 1;           // keys lo .. t, the last one the new one
+  if (nk > a.cap || nk > kMaxS) return;   // (ring: window <= cap, checked by the host)
+  const int trow = ring ? t % a.cap : t;      // the cache row of frame t
+  const int row0 = ring ? lo % a.cap : lo;    // ... of frame lo; frame lo + j: row0 + j, wrapped once (j < nk <= cap)
   const int D4 = a.D >> 2, col0 = h * a.D;
   const int64_t ldc = (int64_t)a.H * a.D;
   float* kc = a.k_cache + (int64_t)s * a.cap * ldc + col0;
@@ -73,8 +90,8 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
     *(f32x4*)(sq + tid * 4) = qv * a.scale;
     *(f32x4*)(sk + tid * 4) = kv;
     *(f32x4*)(sv + tid * 4) = vv;
-    *(f32x4*)(kc + (int64_t)t * ldc + tid * 4) = kv;
-    *(f32x4*)(vc + (int64_t)t * ldc + tid * 4) = vv;
+    *(f32x4*)(kc + (int64_t)trow * ldc + tid * 4) = kv;
+    *(f32x4*)(vc + (int64_t)trow * ldc + tid * 4) = vv;
   }
   __syncthreads();
 
@@ -86,7 +103,9 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
       if (j == nk - 1) {
         for (int c4 = c0; c4 < D4; c4 += 16) acc += dot4(*(const f32x4*)(sq + c4 * 4), *(const f32x4*)(sk + c4 * 4));
       } else {
-        const float* krow = kc + (int64_t)(lo + j) * ldc;
+        int row = row0 + j;
+        if (ring && row >= a.cap) row -= a.cap;
+        const float* krow = kc + (int64_t)row * ldc;
         for (int c4 = c0; c4 < D4; c4 += 16) acc += dot4(*(const f32x4*)(sq + c4 * 4), *(const f32x4*)(krow + c4 * 4));
       }
     }
@@ -95,10 +114,12 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
   }
   __syncthreads();
 
-  {   // softmax over the nk <= 256 scores, one per thread
+  {   // softmax over the nk scores: thread tid owns the scores tid, tid + 256, ... (one when nk <= 256)
     const int lane = tid & 63, wave = tid >> 6;
     const float x = tid < nk ? ss[tid] : -INFINITY;
     float m = x;
+    if constexpr (kLong)
+      for (int j = tid + kST; j < nk; j += kST) m = fmaxf(m, ss[j]);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
     if (lane == 0) red[wave] = m;
@@ -106,12 +127,20 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     const float e = tid < nk ? __expf(x - m) : 0.f;
     float sum = e;
+    if constexpr (kLong)
+      for (int j = tid + kST; j < nk; j += kST) {
+        const float ej = __expf(ss[j] - m);
+        ss[j] = ej;
+        sum += ej;
+      }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
     if (lane == 0) red[4 + wave] = sum;
     __syncthreads();
     const float inv = 1.f / ((red[4] + red[5]) + (red[6] + red[7]));
     if (tid < nk) ss[tid] = e * inv;
+    if constexpr (kLong)
+      for (int j = tid + kST; j < nk; j += kST) ss[j] *= inv;
   }
   __syncthreads();
 
@@ -128,7 +157,9 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
         if (c4 < D4) o[jj] += *(const f32x4*)(sv + c4 * 4) * w;
       }
     } else {
-      const float* vrow = vc + (int64_t)(lo + j) * ldc;
+      int row = row0 + j;
+      if (ring && row >= a.cap) row -= a.cap;
+      const float* vrow = vc + (int64_t)row * ldc;
 #pragma unroll
       for (int jj = 0; jj < kSNJ; ++jj) {
         const int c4 = c0 + 16 * jj;
@@ -150,7 +181,37 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
   }
 }
 
+// the launch behind both exports (their checks come first: nothing is dereferenced or launched before they pass)
+template <int kMaxS>
+int launch_step(const float* q, int64_t ldq, const float* k_new, int64_t ldk, const float* v_new, int64_t ldv,
+                const int32_t* slot, const int32_t* pos, float* k_cache, float* v_cache, int32_t n, int32_t slots, int32_t cap,
+                int32_t H, int32_t D, float scale, int32_t window, int32_t ring, float* out, int64_t ldo,
+                ococc_stream_t stream_) {
+  StepArgs a{};
+  a.q = q; a.k_new = k_new; a.v_new = v_new;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.slot = slot; a.pos = pos;
+  a.k_cache = k_cache; a.v_cache = v_cache;
+  a.n = n; a.slots = slots; a.cap = cap; a.H = H; a.D = D;
+  a.scale = scale; a.window = window; a.ring = ring;
+  a.out = out; a.ldo = ldo;
+  hipLaunchKernelGGL(attn_step_kernel<kMaxS>, dim3(n, H), dim3(kST), 0, (hipStream_t)stream_, a);
+  OCOCC_CHECK_LAUNCH();
+  return OCOCC_OK;
+}
+
 }  // namespace
+
+#define OCOCC_STEP_COMMON_CHECKS()                                                                                     \
+  OCOCC_REQUIRE(H <= 65535, "too many heads");                                                                         \
+  if (n == 0) return OCOCC_OK;                                                                                         \
+  OCOCC_REQUIRE(q && k_new && v_new && slot && pos && k_cache && v_cache && out, "null pointer");                      \
+  OCOCC_REQUIRE(ldq >= (int64_t)H * D && ldk >= (int64_t)H * D && ldv >= (int64_t)H * D && ldo >= (int64_t)H * D,      \
+                "row stride under heads * head_dim");                                                                  \
+  OCOCC_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 &&                                        \
+                    (((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache |   \
+                      (uintptr_t)out) & 15) == 0,                                                                      \
+                "rows must be 16-byte aligned")
 
 extern "C" int ococc_temporal_attention_step_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk,
                                                  const float* v_new, int64_t ldv, const int32_t* slot, const int32_t* pos,
@@ -161,24 +222,24 @@ extern "C" int ococc_temporal_attention_step_f32(const float* q, int64_t ldq, co
   OCOCC_REQUIRE(n <= slots, "more rows than cache slots (the slots of one step are distinct)");
   OCOCC_REQUIRE(cap <= kSMaxS && D <= kSMaxD && D % 4 == 0,
                 "caches of up to 256 frames per slot, head width a multiple of 4 up to 384");
-  OCOCC_REQUIRE(H <= 65535, "too many heads");
-  if (n == 0) return OCOCC_OK;
-  OCOCC_REQUIRE(q && k_new && v_new && slot && pos && k_cache && v_cache && out, "null pointer");
-  const int64_t E = (int64_t)H * D;
-  OCOCC_REQUIRE(ldq >= E && ldk >= E && ldv >= E && ldo >= E, "row stride under heads * head_dim");
-  OCOCC_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldo % 4 == 0 &&
-                    (((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache |
-                      (uintptr_t)out) & 15) == 0,
-                "rows must be 16-byte aligned");
-  StepArgs a{};
-  a.q = q; a.k_new = k_new; a.v_new = v_new;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
-  a.slot = slot; a.pos = pos;
-  a.k_cache = k_cache; a.v_cache = v_cache;
-  a.n = n; a.slots = slots; a.cap = cap; a.H = H; a.D = D;
-  a.scale = scale; a.window = window;
-  a.out = out; a.ldo = ldo;
-  hipLaunchKernelGGL(attn_step_kernel, dim3(n, H), dim3(kST), 0, (hipStream_t)stream_, a);
-  OCOCC_CHECK_LAUNCH();
-  return OCOCC_OK;
+  OCOCC_STEP_COMMON_CHECKS();
+  return launch_step<kSMaxS>(q, ldq, k_new, ldk, v_new, ldv, slot, pos, k_cache, v_cache, n, slots, cap, H, D, scale, window,
+                             0, out, ldo, stream_);
+}
+
+extern "C" int ococc_temporal_attention_step_long_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk,
+                                                      const float* v_new, int64_t ldv, const int32_t* slot,
+                                                      const int32_t* pos, float* k_cache, float* v_cache, int32_t n,
+                                                      int32_t slots, int32_t cap, int32_t H, int32_t D, float scale,
+                                                      int32_t window, int32_t ring, float* out, int64_t ldo,
+                                                      ococc_stream_t stream_) {
+  OCOCC_REQUIRE(n >= 0 && slots >= 1 && cap >= 1 && H >= 1 && D >= 1, "empty cache or negative row count");
+  OCOCC_REQUIRE(cap <= kLongMaxS, "caches of up to 4096 frames per slot");
+  OCOCC_REQUIRE(ring == 0 || (window >= 1 && window <= cap),
+                "a ring cache needs a window of 1 .. cap frames (the row of frame t overwrites frame t - cap)");
+  OCOCC_REQUIRE(n <= slots, "more rows than cache slots (the slots of one step are distinct)");
+  OCOCC_REQUIRE(D <= kSMaxD && D % 4 == 0, "head width a multiple of 4 up to 384");
+  OCOCC_STEP_COMMON_CHECKS();
+  return launch_step<kLongMaxS>(q, ldq, k_new, ldk, v_new, ldv, slot, pos, k_cache, v_cache, n, slots, cap, H, D, scale,
+                                window, ring != 0, out, ldo, stream_);
 }

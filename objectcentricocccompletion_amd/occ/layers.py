@@ -82,12 +82,25 @@ class TemporalCache(object):
 
     Memory: 2 * num_layers * cap * E * 4 bytes per slot -- for the ococcnet model (3 layers, E = 1536) at the default
     ``cap`` = 256 (the longest sequence the attention kernels take; the reference's PositionalEncoding stops at 200) that
-    is 9.4 MB per slot, 604 MB for 64 slots.  A tracklet longer than ``cap`` frames does not fit: the step raises."""
+    is 9.4 MB per slot, 604 MB for 64 slots.  A tracklet longer than ``cap`` frames does not fit: the step raises.
 
-    def __init__(self, num_layers, slots, embed_dim, device, cap=256):
+    Past 256 frames (both make the steps call ococc_temporal_attention_step_long_f32):
+    ``long``: ``cap`` up to 4096 rows per slot, for a model that attends to all history (151 MB per slot at 4096).
+    ``ring``: frame f lives in row f % cap, so a model with test_cfg.attn_window_size = W <= cap, which only ever reads
+    the last W frames, follows a tracklet of any length -- a slot is never full (``pos`` is an int32: 2**31 - 1 frames),
+    and cap = W = 16 is 0.6 MB per slot.  The step needs 1 <= window <= cap (TransformerEncoder.step checks)."""
+
+    MAX_LONG_CAP, MAX_FRAMES = 4096, 2 ** 31 - 1   # kLongMaxS of csrc/causal_attn_step.hip; the int32 frame counter
+
+    def __init__(self, num_layers, slots, embed_dim, device, cap=256, ring=False, long=False):
         from .. import _lib as L
         device = torch.device(device)   # (a CPU cache can be built and kept account of; every step on it raises)
-        if not (1 <= int(cap) <= 256):
+        self.ring, self.long = bool(ring), bool(long) or bool(ring)
+        if self.long:
+            if not (1 <= int(cap) <= self.MAX_LONG_CAP):
+                raise L.OcoccError(f'TemporalCache: cap {cap} outside 1..{self.MAX_LONG_CAP}, the most frames the long '
+                                   'attention step keeps scores for')
+        elif not (1 <= int(cap) <= 256):
             raise L.OcoccError(f'TemporalCache: cap {cap} outside 1..256, the longest sequence the attention kernels take')
         if int(slots) < 1 or int(num_layers) < 1:
             raise L.OcoccError('TemporalCache: at least one slot and one layer')
@@ -106,7 +119,8 @@ class TemporalCache(object):
         return 2 * self.num_layers * self.slots * self.cap * self.embed_dim * 4
 
     def check_step(self, slots):
-        """the host-side checks of one step over the slot list ``slots``: in range, distinct, room for one more frame"""
+        """the host-side checks of one step over the slot list ``slots``: in range, distinct, room for one more frame (a
+        ring cache always has room: only its frame counter can run out)"""
         from .. import _lib as L
         slots = [int(s) for s in slots]
         if len(set(slots)) != len(slots):
@@ -114,9 +128,14 @@ class TemporalCache(object):
         for s in slots:
             if not 0 <= s < self.slots:
                 raise L.OcoccError(f'TemporalCache: slot {s} outside 0..{self.slots - 1}')
-            if self.pos_host[s] >= self.cap:
+            if self.ring:
+                if self.pos_host[s] >= self.MAX_FRAMES:
+                    raise L.OcoccError(f'TemporalCache: slot {s} has been stepped through 2**31 - 1 frames, the last its '
+                                       'int32 counter holds (reset the slot)')
+            elif self.pos_host[s] >= self.cap:
                 raise L.OcoccError(f'TemporalCache: slot {s} already holds cap = {self.cap} frames; a tracklet longer than '
-                                   'the cache is not supported (reset the slot or build the cache with a larger cap <= 256)')
+                                   'the cache is not supported (reset the slot or build the cache with a larger cap <= '
+                                   f'{self.MAX_LONG_CAP if self.long else 256})')
         return slots
 
     def advance(self, slots, slot_dev):
@@ -230,13 +249,15 @@ class MultiheadAttention(nn.Module):
         return gemm.linear(ctx, self.out_proj.weight, self.out_proj.bias).view(L, B, E), None
 
     @torch.no_grad()
-    def step(self, x_qk, x_v, slot, cache_k, cache_v, pos, window=-1):
+    def step(self, x_qk, x_v, slot, cache_k, cache_v, pos, window=-1, ring=False, long=False):
         """One new frame per tracklet against the cached ones: x_qk, x_v [n, E] (this frame's src + pos and src),
         ``slot`` int32 [n] the cache slot of each row, cache_k / cache_v [slots, cap, E] this layer's cache, ``pos`` int32
         [slots] the frames cached per slot.  q and k leave one product with the first 2E rows of in_proj as in ``forward``;
         ococc_temporal_attention_step_f32 appends k and v at row pos[slot] and attends to the frames lo..pos[slot]
         (``window`` > 0: the last ``window`` frames, as get_future_mask windows the past); out_proj follows.  ``pos`` is
-        left as it is.  No fall-back: arguments the kernel does not take raise."""
+        left as it is.  ``long`` / ``ring`` (TemporalCache): ococc_temporal_attention_step_long_f32 instead -- caches of up
+        to 4096 rows, and with ``ring`` frame f in row f % cap (1 <= window <= cap).  No fall-back: arguments the kernel
+        does not take raise."""
         from .. import _lib as L
         _eval_only(self, 'MultiheadAttention.step')
         L.require_device(x_qk, x_v, slot, cache_k, cache_v, pos)
@@ -250,10 +271,18 @@ class MultiheadAttention(nn.Module):
         v = gemm.linear(x_v.float(), w[2 * E:], b[2 * E:])
         q, k = qk[:, :E], qk[:, E:]
         ctx = torch.empty((n, E), dtype=torch.float32, device=qk.device)
-        L.check(L.lib.ococc_temporal_attention_step_f32(
-            q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), slot.data_ptr(), pos.data_ptr(),
-            cache_k.data_ptr(), cache_v.data_ptr(), n, cache_k.shape[0], cache_k.shape[1], self.num_heads, self.head_dim,
-            float(self.head_dim) ** -0.5, int(window), ctx.data_ptr(), ctx.stride(0), L.stream()), 'temporal_attention_step')
+        if long or ring:
+            L.check(L.lib.ococc_temporal_attention_step_long_f32(
+                q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), slot.data_ptr(),
+                pos.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(), n, cache_k.shape[0], cache_k.shape[1], self.num_heads,
+                self.head_dim, float(self.head_dim) ** -0.5, int(window), int(bool(ring)), ctx.data_ptr(), ctx.stride(0),
+                L.stream()), 'temporal_attention_step_long')
+        else:
+            L.check(L.lib.ococc_temporal_attention_step_f32(
+                q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), slot.data_ptr(),
+                pos.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(), n, cache_k.shape[0], cache_k.shape[1], self.num_heads,
+                self.head_dim, float(self.head_dim) ** -0.5, int(window), ctx.data_ptr(), ctx.stride(0), L.stream()),
+                'temporal_attention_step')
         return gemm.linear(ctx, self.out_proj.weight, self.out_proj.bias)
 
 
@@ -291,11 +320,13 @@ class SimpleEncoderLayer(nn.Module):
         return self._residual_norm(self.norm2, x, self._feed_forward(x), self.dropout2)
 
     @torch.no_grad()
-    def step(self, src, pos_enc, slot, cache_k, cache_v, pos, window=-1):
+    def step(self, src, pos_enc, slot, cache_k, cache_v, pos, window=-1, ring=False, long=False):
         """``forward`` for one new frame per tracklet, src / pos_enc [n, E], against this layer's cache
-        (MultiheadAttention.step): the same post-LN structure, the dropouts are the identity (inference only)."""
+        (MultiheadAttention.step, which ``ring`` / ``long`` go to): the same post-LN structure, the dropouts are the
+        identity (inference only)."""
         _eval_only(self, 'SimpleEncoderLayer.step')
-        attended = self.self_attn.step(self.with_pos_embed(src, pos_enc), src, slot, cache_k, cache_v, pos, window)
+        attended = self.self_attn.step(self.with_pos_embed(src, pos_enc), src, slot, cache_k, cache_v, pos, window, ring,
+                                       long)
         x = self._residual_norm(self.norm1, src, attended, self.dropout1)
         return self._residual_norm(self.norm2, x, self._feed_forward(x), self.dropout2)
 
@@ -324,12 +355,18 @@ class TransformerEncoder(nn.Module):
         ints (a tensor is read back: the bounds checks run on the host); ``cache`` a TemporalCache with one (k, v) pair
         per layer.  Row i equals row pos[slot[i]] of ``forward`` over the frames 0..pos[slot[i]] of that tracklet under the
         future mask (windowed by ``window`` > 0).  Bumps ``cache.pos`` and its host mirror once, after the last layer.
-        The host-side checks (duplicate slots, a step past ``cache.cap``, CPU tensors) raise before anything is launched."""
+        A ring cache (``cache.ring``) needs 1 <= window <= cache.cap.
+        The host-side checks (duplicate slots, a step past ``cache.cap``, a window a ring cache cannot serve, CPU tensors)
+        raise before anything is launched."""
         from .. import _lib as L
         from ..tracklet import host_index
         _eval_only(self, 'TransformerEncoder.step')
         if cache.num_layers != self.num_layers:
             raise L.OcoccError(f'TemporalCache of {cache.num_layers} layers for an encoder of {self.num_layers}')
+        ring, long = cache.ring, cache.long
+        if ring and not 1 <= int(window) <= cache.cap:
+            raise L.OcoccError(f'a ring TemporalCache of cap = {cache.cap} rows serves windows of 1..{cache.cap} frames, not '
+                               f'window = {window}: the row of frame t overwrites frame t - cap')
         slots = cache.check_step(slot.tolist() if torch.is_tensor(slot) else slot)
         if len(slots) != src.shape[0]:
             raise L.OcoccError(f'{len(slots)} slots for {src.shape[0]} rows')
@@ -337,6 +374,6 @@ class TransformerEncoder(nn.Module):
         slot_dev = host_index(slots, src.device, dtype=torch.int32)
         x = src
         for i, layer in enumerate(self.layers):
-            x = layer.step(x, pos_enc, slot_dev, cache.k[i], cache.v[i], cache.pos, window)
+            x = layer.step(x, pos_enc, slot_dev, cache.k[i], cache.v[i], cache.pos, window, ring, long)
         cache.advance(slots, slot_dev)
         return x

@@ -400,13 +400,16 @@ class TrackletRoIHeadOCC(nn.Module):
         return [out]
 
     # ------------------------------------------------------------------ online inference
-    def online_begin(self, slots, device, cap=256):
+    def online_begin(self, slots, device, cap=256, ring=False, long=False):
         """State for frame-by-frame inference over ``slots`` tracklets at a time (simple_test_step): the TemporalCache of
         the head's temporal transformer -- 2 * layers * cap * E * 4 bytes per slot, 9.4 MB for the ococcnet model at the
         default cap = 256 -- whose per-slot frame counter is also the frame index the next step of the slot gets.
-        ``state.reset(slots)`` hands slots to new tracklets."""
+        ``state.reset(slots)`` hands slots to new tracklets.  Tracklets of more than 256 frames: ``ring=True`` with
+        cap >= test_cfg.attn_window_size > 0 (a windowed model: any length, 0.6 MB per slot at cap = 16), or ``long=True``
+        with cap up to 4096 (a model that attends to all history)."""
         enc = self.bbox_head.trans_enc
-        return OnlineState(TemporalCache(enc.num_layers, slots, self.bbox_head.roi_feature_channels, device, cap=cap))
+        return OnlineState(TemporalCache(enc.num_layers, slots, self.bbox_head.roi_feature_channels, device, cap=cap,
+                                         ring=ring, long=long))
 
     @torch.no_grad()
     def simple_test_step(self, pts_xyz, pts_feats, pts_batch_idx, boxes, scores, labels, slot, state, gt_rois=None):
@@ -455,20 +458,30 @@ class TrackletRoIHeadOCC(nn.Module):
         """simple_test computed the way the method is deployed: the tracklet is fed to simple_test_step frame by frame in
         one slot of a fresh state, then test_occ / the exports run on the concatenated per-step features.  Same arguments,
         same result (the temporal transformer is causal: frame t never saw the later frames offline either); what
-        simple_test does when test_cfg.online is set.  The points are taken in the coordinate frame they come in."""
+        simple_test does when test_cfg.online is set.  The points are taken in the coordinate frame they come in.
+        Up to 256 frames: a cache of that many rows.  Above: with test_cfg.attn_window_size = W > 0 a ring cache of W rows
+        (any length), without a window a long cache of up to 4096 rows; past that an OcoccError."""
         from . import _lib as L
         from .tracklet import host_index
         assert len(tracklet_list) == 1, 'only support batch size 1'
         if self.test_cfg.get('tta', None) is not None:
             raise NotImplementedError('test_cfg.online with test_cfg.tta')
         num = len(tracklet_list[0])
-        if num > 256:
-            raise L.OcoccError(f'a tracklet of {num} frames: the K/V cache of online inference holds at most 256')
+        window = self.test_cfg.get('attn_window_size', -1)
+        if num <= 256:
+            cache_kw = dict(cap=max(num, 1))
+        elif window > 0:       # (only ever reads the last ``window`` frames: a ring of that many rows, any length)
+            cache_kw = dict(cap=window, ring=True)
+        elif num <= TemporalCache.MAX_LONG_CAP:
+            cache_kw = dict(cap=num, long=True)
+        else:
+            raise L.OcoccError(f'a tracklet of {num} frames without test_cfg.attn_window_size: the K/V cache of online '
+                               f'inference holds at most {TemporalCache.MAX_LONG_CAP} frames of history')
         L.require_device(pts_xyz, pts_feats, pts_batch_idx, pts_frame_inds)
         gt_rois, gt_occ_list, gt_occ_score_list = self._test_gt_rois(tracklet_list, gt_candidates_list, gt_occs_list,
                                                                      gt_occ_scores_list)
         rois, roi_frame_inds, cls_preds, labels_3d = self.tracklets2rois(tracklet_list)
-        state = self.online_begin(1, rois.device, cap=max(num, 1))
+        state = self.online_begin(1, rois.device, **cache_kw)
         # the points frame by frame: one stable sort, the counts in one read-back
         order = torch.sort(pts_frame_inds, stable=True).indices
         counts = torch.bincount(pts_frame_inds, minlength=num).tolist()

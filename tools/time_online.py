@@ -3,11 +3,16 @@
 the temporal K/V cache) at frame t = 1, 50 and 199 for 1 and 64 tracklets at a time on the ococcnet model, against what a
 user without it does at that frame: TrackletRoIHeadOCC.simple_test on the prefix of t + 1 frames, once per tracklet
 (simple_test takes one tracklet per call).
-    python tools/time_online.py [--slots 1 64] [--frames 1 50 199] [--points 256] [--reps 7] [--out profiles/online_step.md]
+    python tools/time_online.py [--slots 1 64] [--frames 1 50 199] [--long-frame 1000] [--points 256] [--reps 7] [--out FILE.md]
 Synthetic vehicle tracklets (oracle/synth.py) of --points points per frame, random weights.  For a step at frame t the
 cache is set to t cached frames of random keys and values -- what it holds does not change the work -- and pos is set back
 after every call.  Both paths are warmed up at every shape, then timed alternately; a call is timed with device events
-around it and with the host clock up to a device synchronise; median (min - max) of the repetitions.  A report, not a gate."""
+around it and with the host clock up to a device synchronise; median (min - max) of the repetitions.  A report, not a gate.
+
+Past 256 frames (--long-frame, default 1000; 0: skip): two more rows per tracklet count, a step at that frame of a ring cache
+of 16 rows with test_cfg.attn_window_size = 16 and of a long cache of --long-frame + 1 rows without a window (the step
+reads 16 and --long-frame cached frames).  The points and boxes are those of the last synthetic frame -- only the frame
+index the positional encoding gets and the cache counter say 1000 -- so no longer synthetic tracklets are built."""
 import argparse
 import os
 
@@ -44,10 +49,11 @@ def tracklets(slots, frames, points, dev, seed=0):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--slots', type=int, nargs='+', default=[1, 64])
-    ap.add_argument('--frames', type=int, nargs='+', default=[1, 50, 199])
+    ap.add_argument('--frames', type=int, nargs='*', default=[1, 50, 199])
     ap.add_argument('--points', type=int, default=256, help='points per frame and tracklet')
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--long-frame', type=int, default=1000, help='frame of the ring / long cache rows (0: none)')
     ap.add_argument('--out', default=None, help='also write the table to this markdown file')
     args = ap.parse_args()
     import torch
@@ -61,7 +67,7 @@ def main():
     cfg = ococcnet_model_cfg()
     cfg['test_cfg']['test_occ_iou'] = False          # (no labels here: the refinement alone, on both sides)
     rh = DETECTORS.build(cfg).to(dev).eval().roi_head
-    total = max(args.frames) + 1
+    total = max(args.frames, default=1) + 1
     lines = ['| tracklets | frame t | path | device events, ms: median (min - max) | host clock, ms |', '|---|---|---|---|---|']
     with torch.no_grad():
         for slots in args.slots:
@@ -72,14 +78,18 @@ def main():
                 v.normal_()
             labels = torch.zeros(slots, dtype=torch.long, device=dev)
             slot = list(range(slots))
-            for t in args.frames:
+
+            def frame_inputs(t):
                 lo = [0 if t == 0 else int(d['ends'][t - 1]) for d in trks]
                 pts = torch.cat([d['points'][a:int(d['ends'][t])] for d, a in zip(trks, lo)])
                 batch = torch.cat([torch.full((int(d['ends'][t]) - a,), b, dtype=torch.long, device=dev)
                                    for b, (d, a) in enumerate(zip(trks, lo))])
                 boxes = torch.stack([d['boxes'][t] for d in trks])
                 scores = torch.stack([d['scores'][t] for d in trks])
-                xyz, feats = pts[:, :3].contiguous(), pts[:, 3:].contiguous()
+                return pts[:, :3].contiguous(), pts[:, 3:].contiguous(), batch, boxes, scores
+
+            for t in args.frames:
+                xyz, feats, batch, boxes, scores = frame_inputs(t)
 
                 def step():
                     state.cache.pos.fill_(t)
@@ -110,6 +120,36 @@ def main():
                                    ('offline', f'`simple_test` on frames 0..{t}, once per tracklet')):
                     lines.append(f'| {slots} | {t} | {what} | {fmt(times[name][0])} | {fmt(times[name][1])} |')
                     print(lines[-1], flush=True)
+            del state
+            if args.long_frame > 0:
+                T = args.long_frame
+                xyz, feats, batch, boxes, scores = frame_inputs(total - 1)
+                cfgs = list({id(c): c for c in (rh.test_cfg, rh.bbox_head.test_cfg)}.values())
+                for what, kw, window in ((f'`simple_test_step`, ring cache of 16 rows, window 16', dict(cap=16, ring=True), 16),
+                                         (f'`simple_test_step`, long cache of {T + 1} rows, no window', dict(cap=T + 1, long=True),
+                                          -1)):
+                    st = rh.online_begin(slots, dev, **kw)
+                    for k, v in zip(st.cache.k, st.cache.v):
+                        k.normal_()
+                        v.normal_()
+                    for c in cfgs:
+                        c['attn_window_size'] = window
+
+                    def step_long():
+                        st.cache.pos.fill_(T)
+                        st.cache.pos_host[:] = [T] * slots
+                        return rh.simple_test_step(xyz, feats, batch, boxes, scores, labels, slot, st)
+
+                    try:
+                        for _ in range(args.warmup):
+                            step_long()
+                        e, h = timed(step_long, args.reps)
+                    finally:
+                        for c in cfgs:
+                            del c['attn_window_size']
+                    lines.append(f'| {slots} | {T} | {what} | {fmt(e)} | {fmt(h)} |')
+                    print(lines[-1], flush=True)
+                    del st
     text = '\n'.join(lines)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -64,7 +64,10 @@ __device__ __forceinline__ ln_f32x2 ln_gelu2_exp(ln_f32x2 z) {
 //   GELU(z) = max(z, 0) - |z| u(|z|),   u(a) = (1 - erf(a / sqrt 2)) / 2 = 1 / (2 P(a)^16)
 // Abramowitz & Stegun 7.1.28, erf(x) = 1 - (1 + a1 x + ... + a6 x^6)^-16, |error| <= 3e-7 (x >= 0); the coefficients
 // below are a_i / sqrt(2)^i.  No exponential, no sign select: 12 packed operations, 2 reciprocals and 4 single ones per
-// pair against 14 + 4 + 6 above.  |GELU error| <= 1.5e-7 |z|.
+// pair against 14 + 4 + 6 above.  |GELU error| <= 1.5e-7 |z| is the approximation's error in exact arithmetic; in
+// float32 with v_rcp_f32 (whose error the four squarings multiply by 16) gfx950 delivers 6.0e-7 at most, near z = 4,
+// and 4.1e-7 |z| at most, measured over z in [-12, 12] against exact erf (tests/test_gpu_layernorm_edges.py; the exp
+// form: 4.7e-7, ln_gelu_grad2 and norm_cdf / gelu_grad: 1.9e-7).
 __device__ __forceinline__ ln_f32x2 ln_gelu2(ln_f32x2 z) {
   ln_f32x2 a, r, relu;
   a.x = __builtin_fabsf(z.x);

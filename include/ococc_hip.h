@@ -1208,6 +1208,40 @@ int ococc_occ_mlp_train_fwd_bf16(const uint16_t* pe, int64_t rows, const float* 
                                  void* const* stats_out, float* out, ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Test-time tuning of the fused shape latent (OccBBoxHead.online_tuning, ococc_bbox_head.py:402-431;
+ * OccAutoEncoder.online_tuning_forward, occ_ae_head.py:346-391): what is specific to tuning around the backward chain of
+ * the frozen decoder.  Zero rows: OCOCC_OK without a launch.
+ *
+ * ococc_occ_tune_head_lnbwd_bf16 replaces, per iteration, the backward of loss_ae.backward() (occ_ae_head.py:381-385)
+ *   through CrossEntropyLoss(use_sigmoid, reduction 'none').mean(), the head Linear and the last LayerNorm + GELU of
+ *   conv_occ (occ_base.py:99-153): per row d = scale * weights[i] * (sigmoid(logits[i]) - labels[i]) (scale =
+ *   loss_weight / rows; weights null = 1), dy = d * head_weight (registers only), then the GELU and LayerNorm backward of
+ *   ococc_layernorm_act_bwd from the stored z (bf16 [rows, 1024]) and mean_rstd (f32 [rows, 2]) to dz (bf16 [rows, 1024]).
+ *   No parameter-gradient partials.  labels int32 [rows]; c must be 1024.
+ * ococc_segment_sum_bf16 replaces the gather's backward (roi_feats[pts_roi_inds], ococc_bbox_head.py:711): out[k, :] = sum
+ *   of the rows of x (bf16 [rows, 512]) whose index is k, f32 [num_segments, 512], accumulated in f32 in an order that
+ *   depends on the segment's extent alone (no atomics: two runs give equal bits).  index int32 [rows], non-decreasing; a
+ *   segment without rows gets a zero row; rows whose index is outside [0, num_segments) are left out.  c must be 512.
+ * ococc_latent_ln_adam_f32 replaces the backward of OccDecoder.ln (occ_base.py:104-106) and optimizer.step() /
+ *   scheduler.step() of torch.optim.Adam([roi_embed], lr=0.01) + StepLR (occ_ae_head.py:362-363, 386-387): per row of e
+ *   (f32 [rows, d], updated in place) it recomputes mean / rstd, takes d_n (the gradient of LN(e)) through the LayerNorm
+ *   backward with gamma to de (use_ln == 0: de = d_n, gamma may be null), and applies Adam's step t (counted from 1) in
+ *   place on e, m, v: m = m + (de - m)(1 - beta1), v = beta2 v + (1 - beta2) de^2,
+ *   e -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps).  lr is the step's learning rate (the schedule is the
+ *   caller's); lr, the betas and eps are doubles: 1 - beta, the bias corrections and the step size are worked out in double on
+ *   the host and rounded once.  de_out (f32 [rows, d], may be null) receives de.  d a multiple of 4 in [4, 2048].
+ * ------------------------------------------------------------------------ */
+int ococc_occ_tune_head_lnbwd_bf16(const float* logits, const int32_t* labels, const float* weights, float scale,
+                                   const float* head_weight, const uint16_t* z, const float* mean_rstd,
+                                   const float* gamma, const float* beta, int64_t rows, int32_t c, uint16_t* dz,
+                                   ococc_stream_t stream);
+int ococc_segment_sum_bf16(const uint16_t* x, const int32_t* index, int64_t rows, int32_t c, float* out,
+                           int64_t num_segments, ococc_stream_t stream);
+int ococc_latent_ln_adam_f32(float* e, const float* d_n, float* m, float* v, int64_t rows, int32_t d, const float* gamma,
+                             float ln_eps, int32_t use_ln, double lr, double beta1, double beta2, double eps, int32_t t,
+                             float* de_out, ococc_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * B6, element-wise halves of the SST input layer, one launch each (the mirror ran 20-50 torch operators per call):
  * ococc_sst_window_coors_i64: get_window_coors (mmdet3d/ops/sst/sst_ops.py:266-313) for BOTH window shifts.
  *   coors int64 [n, 4] (b, z, y, x); shapes as (x, y, z) HOST triples (2-D windows: pass window z = sparse z);

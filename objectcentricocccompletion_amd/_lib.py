@@ -206,6 +206,10 @@ SIGNATURES = {
                                              ctypes.POINTER(c_vp), c_f32, c_vp, c_vp, ctypes.c_uint32,
                                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
                                              ctypes.POINTER(c_vp), c_vp, c_vp]),
+    'ococc_occ_tune_head_lnbwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
+    'ococc_segment_sum_bf16': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    'ococc_latent_ln_adam_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_f32, c_i32, ctypes.c_double,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i32, c_vp, c_vp]),
     'ococc_sst_window_coors_i64': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_vp, c_vp, c_vp]),
     'ococc_sst_drop_level_i64': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
                                          ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_vp, c_vp, c_vp]),

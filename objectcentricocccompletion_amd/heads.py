@@ -683,16 +683,49 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
                                                                         roi_inds, rois)
         local_roi_feats, _, local_xyz = self.occ_ae_head.encode(pts_xyz, pts_features[:, :2], pts_info,
                                                                 roi_inds, rois)
-        return final_cluster_feats, nonempty_roi_mask, local_roi_feats
+        return final_cluster_feats, nonempty_roi_mask, local_roi_feats, local_xyz
 
-    def _fuse_and_predict(self, local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask):
-        """The per-RoI stages behind the temporal transformer: shape latent by ``fused_mode``, then score and box deltas."""
+    def online_tuning(self, shape_latent, local_xyz, rois, roi_inds, downsample_size=-1, balance_sample=False, num_iter=10):
+        """ococc_bbox_head.py:402-431: tune the fused shape latent of every RoI against the RoI's own observation -- the
+        pooled points rasterised into its 0.2 m grid (sample_observation), ``num_iter`` Adam steps on the BCE of the frozen
+        decoder at the sampled cells.  On the kernels of occ/latent_tune.py for the bf16 decoder on the device, through
+        OccAutoEncoder.online_tuning_forward (autograd) otherwise and with OCOCC_LATENT_TUNE_KERNELS=0.  Works under
+        torch.no_grad(); no points or no sampled cell: the latent comes back unchanged, and so does the latent of a RoI
+        that holds no point."""
+        from .occ import latent_tune
+        ae = self.occ_ae_head
+        if local_xyz.size(0) == 0 or shape_latent.size(0) == 0:
+            return shape_latent
+        smp_xyz, labels, smp_inds = ae.sample_observation(local_xyz, rois, roi_inds, downsample_size=downsample_size,
+                                                          balance_sample=balance_sample)
+        # a RoI that holds no point has no observation: its cells are left out (the reference's sampling would hand it
+        # free cells -- all of them, or the first one under balance_sample -- and move its latent towards "empty")
+        seen = torch.zeros(shape_latent.size(0), dtype=torch.bool, device=smp_inds.device)
+        seen[roi_inds.long()] = True
+        keep = seen[smp_inds.long()]
+        smp_xyz, labels, smp_inds = smp_xyz[keep], labels[keep], smp_inds[keep]
+        if smp_xyz.size(0) == 0:
+            return shape_latent
+        if latent_tune.supported(ae.occ_decoder, shape_latent, smp_xyz, labels, smp_inds):
+            return latent_tune.tune_latents(ae.occ_decoder, shape_latent, smp_xyz, labels, smp_inds, num_iter,
+                                            loss_weight=ae.loss_occ_ae.loss_weight).to(shape_latent.dtype)
+        log_once(('latent-tune', latent_tune.KERNELS, shape_latent.is_cuda, ae.occ_decoder.compute_dtype),
+                 'OccBBoxHead.online_tuning: the tuning kernels take the bf16 occupancy decoder (60 -> 512 -> 1024 -> 1024 -> 1) '
+                 'on a ROCm device%s; tuning through autograd (OccAutoEncoder.online_tuning_forward)'
+                 % ('' if latent_tune.KERNELS else ' and OCOCC_LATENT_TUNE_KERNELS=0 turns them off'))
+        return ae.online_tuning_forward(shape_latent, smp_xyz, labels, None, smp_inds, num_iter).detach()
+
+    def _fuse_and_predict(self, local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask, tune=None):
+        """The per-RoI stages behind the temporal transformer: shape latent by ``fused_mode`` (tuned by ``tune`` when given:
+        test_cfg.online_tuning), then score and box deltas."""
         if self.fused_mode == 'residual':
             shape_latent = local_roi_feats + self.conv_latent(roi_feats_fused)
         elif self.fused_mode == 'concat':
             shape_latent = self.conv_latent(torch.cat([local_roi_feats, roi_feats_fused], dim=1))
         else:  # concat_residual
             shape_latent = local_roi_feats + self.conv_latent(torch.cat([local_roi_feats, roi_feats_fused], dim=1))
+        if tune is not None:
+            shape_latent = tune(shape_latent)
         ret = dict(fused_roi_feats=shape_latent, nonempty_roi_mask=nonempty_roi_mask, ori_roi_feats=local_roi_feats)
         second = roi_feats_fused if self.rcnn_trans else final_cluster_feats
         fused = self.conv_fused(torch.cat([shape_latent, second], dim=1))
@@ -702,8 +735,8 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
     def forward(self, pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds):
         """ococc_bbox_head.py:319-400 -> dict(fused_roi_feats, nonempty_roi_mask, ori_roi_feats,
         cls_score, bbox_pred)."""
-        final_cluster_feats, nonempty_roi_mask, local_roi_feats = self._encode_rois(pts_xyz, pts_features, pts_info,
-                                                                                    roi_inds, rois)
+        final_cluster_feats, nonempty_roi_mask, local_roi_feats, local_xyz = self._encode_rois(
+            pts_xyz, pts_features, pts_info, roi_inds, rois)
         roi_feats_fused = self.transformer_forward(rois, roi_frame_inds, final_cluster_feats, nonempty_roi_mask)
         tail = None
         if local_roi_feats.requires_grad and roi_feats_fused.requires_grad and final_cluster_feats.requires_grad:
@@ -712,7 +745,12 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
             shape_latent, cls_score, bbox_pred = tail
             return dict(fused_roi_feats=shape_latent, nonempty_roi_mask=nonempty_roi_mask, ori_roi_feats=local_roi_feats,
                         cls_score=cls_score, bbox_pred=bbox_pred)
-        return self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
+        tune = None
+        if not self.training and self.test_cfg.get('online_tuning', None) is not None:
+            cfg = self.test_cfg['online_tuning']
+            tune = lambda latent: self.online_tuning(latent, local_xyz, rois, roi_inds, downsample_size=cfg['downsample_size'],
+                                                     balance_sample=cfg['balance_sample'], num_iter=cfg['num_iter'])
+        return self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask, tune)
 
     @torch.no_grad()
     def forward_step(self, pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds, slot, cache):
@@ -731,8 +769,8 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
                              'frame by frame')
         if self.test_cfg.get('online_tuning', False):
             raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference')
-        final_cluster_feats, nonempty_roi_mask, local_roi_feats = self._encode_rois(pts_xyz, pts_features, pts_info,
-                                                                                    roi_inds, rois)
+        final_cluster_feats, nonempty_roi_mask, local_roi_feats, _ = self._encode_rois(pts_xyz, pts_features, pts_info,
+                                                                                       roi_inds, rois)
         pos_embed = self._pos_embed(roi_frame_inds, rois[:, 1:])
         roi_feats_fused = self.trans_enc.step(final_cluster_feats, pos_embed, slot, cache,
                                               self.test_cfg.get('attn_window_size', -1))

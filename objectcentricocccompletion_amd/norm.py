@@ -68,18 +68,21 @@ def _flush_param_reduce(todo):
 _deferred.register('ln', _flush_param_reduce)
 
 
-def layernorm_act_backward(x2, dy2, w32, b32, stats, act, dx, weight=None, bias=None, drop=(0, 0)):
+def layernorm_act_backward(x2, dy2, w32, b32, stats, act, dx, weight=None, bias=None, drop=(0, 0), params=True):
     """dx into `dx`; -> (dgamma, dbeta) f32 [c].  With the parameters given (by our autograd Functions) and a
     backward pass running that accumulates into their .grad, only the per-block partial sums are computed now, the
     two sums join the pass's end-of-backward launch and reach .grad there (_deferred): (None, None) is returned.
-    Otherwise they are reduced right behind the kernel."""
+    Otherwise they are reduced right behind the kernel.  ``params=False`` (nobody asked for dgamma / dbeta: a frozen
+    LayerNorm): no reduce launch, (None, None)."""
     n, c = x2.shape
-    dgb = torch.empty((2, c), dtype=torch.float32, device=x2.device)  # overwritten by the kernel
-    dgamma, dbeta = dgb[0], dgb[1]
     dt = L.dtype_code(x2.dtype)
     ws = L.workspace(L.lib.ococc_layernorm_act_bwd_workspace_bytes(n, c), x2.device)
-    defer = False
-    if n > 0 and weight is not None and bias is not None and weight is not bias \
+    defer = not params
+    dgb = dgamma = dbeta = None
+    if params:
+        dgb = torch.empty((2, c), dtype=torch.float32, device=x2.device)  # overwritten by the kernel
+        dgamma, dbeta = dgb[0], dgb[1]
+    if params and n > 0 and weight is not None and bias is not None and weight is not bias \
             and _deferred.deferrable(weight, bias):
         rows = L.lib.ococc_layernorm_act_bwd_partial_rows(n, c, dt)
         defer = rows > 0 and _deferred.defer('ln', (ws, rows, c, dgb), [(weight, dgamma), (bias, dbeta)])

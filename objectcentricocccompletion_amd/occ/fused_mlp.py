@@ -199,9 +199,12 @@ class _OccMlpTrain(torch.autograd.Function):
         M, dev = pe.size(0), pe.device
         bf = torch.bfloat16
         d = dlogit.reshape(M, 1).to(bf)
+        # what nobody asked for is not computed (a frozen decoder under test-time tuning: only roi_part needs a gradient)
+        need = ctx.needs_input_grad
+        need_w, need_ln = need[3:6], [need[6 + 2 * l] or need[7 + 2 * l] for l in range(3)]
         # head: logit = y2 . w_head + b_head
-        d_head_w = wgrad_rows_bf16(d, ys[2]).to(head_w.dtype)
-        d_head_b = dlogit.sum().reshape(1)
+        d_head_w = wgrad_rows_bf16(d, ys[2]).to(head_w.dtype) if need[12] else None
+        d_head_b = dlogit.sum().reshape(1) if need[13] else None
         dy = d @ head_w.detach().to(bf).view(1, -1)                                  # [M, 1024]
         weights = (w_pe, w1, w2)
         grads_ln, dws = [None] * 6, [None] * 3
@@ -210,19 +213,25 @@ class _OccMlpTrain(torch.autograd.Function):
             dz = torch.empty_like(zs[l])
             lw, lb = ctx.ln_params[l]
             dg, db = layernorm_act_backward(zs[l], dy.contiguous(), gs[l], bs[l], stats[l], 1, dz, lw, lb,
-                                            drop=(thr, seeds[l]) if thr else (0, 0))
-            grads_ln[2 * l], grads_ln[2 * l + 1] = (None if dg is None else dg.to(lw.dtype)), (None if db is None else db.to(lb.dtype))
+                                            drop=(thr, seeds[l]) if thr else (0, 0), params=need_ln[l])
+            if need_ln[l]:
+                grads_ln[2 * l], grads_ln[2 * l + 1] = (None if dg is None else dg.to(lw.dtype)), (None if db is None else db.to(lb.dtype))
             if l > 0:
-                dws[l] = wgrad_rows_bf16(dz, ys[l - 1]).to(weights[l].dtype)         # [n_l, n_{l-1}]
+                if need_w[l]:
+                    dws[l] = wgrad_rows_bf16(dz, ys[l - 1]).to(weights[l].dtype)     # [n_l, n_{l-1}]
                 dy = dz @ weights[l].detach().to(bf)                                 # [M, n_{l-1}]
             else:
-                dz0 = dz.float()
+                dz0 = dz
         # first layer: z0 = pe W_pe^T + roi_part[idx]
-        pe32 = pe[:, :w_pe.shape[1]].float()
-        dws[0] = rows_wgrad(dz0, pe32).to(w_pe.dtype)
-        d_roi = torch.empty((K, dz0.shape[1]), dtype=torch.float32, device=dev)
-        L.check(L.lib.ococc_segment_reduce_f32(L.ptr(dz0), L.ptr(idx), M, dz0.shape[1], 0, None, L.ptr(d_roi), None, K,
-                                               L.stream()), 'occ_mlp_train_bwd: roi_part')
+        if need_w[0]:
+            pe32 = pe[:, :w_pe.shape[1]].float()
+            dws[0] = rows_wgrad(dz0.float(), pe32).to(w_pe.dtype)
+        d_roi = None
+        if need[1]:
+            # the bf16 rows summed per RoI in f32, in a fixed order (idx is non-decreasing): no f32 copy, no float atomics
+            d_roi = torch.empty((K, dz0.shape[1]), dtype=torch.float32, device=dev)
+            L.check(L.lib.ococc_segment_sum_bf16(L.ptr(dz0), L.ptr(idx), M, dz0.shape[1], L.ptr(d_roi), K, L.stream()),
+                    'occ_mlp_train_bwd: roi_part')
         return (None, d_roi, None, dws[0], dws[1], dws[2], grads_ln[0], grads_ln[1], grads_ln[2], grads_ln[3], grads_ln[4],
                 grads_ln[5], d_head_w, d_head_b, None, None, None, None)
 

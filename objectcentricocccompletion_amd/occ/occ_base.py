@@ -173,7 +173,9 @@ class OccDecoder(nn.Module):
 
     def forward(self, roi_features, smp_xyzs, pts_roi_inds):
         """roi_features [K,D], smp_xyzs [N,3], pts_roi_inds [N] in [0,K) -> logits [N, cls_dim]
-        (occ_base.py:100-118), first layer factorised as described in the module docstring."""
+        (occ_base.py:100-118), first layer factorised as described in the module docstring.  The bf16 path under autograd
+        (fused_mlp.occ_mlp_train) takes pts_roi_inds non-decreasing, as every caller here hands them (cells RoI after RoI):
+        its backward sums the rows of a RoI as one contiguous run."""
         if not isinstance(self.conv_occ, nn.Sequential):
             return self.conv_occ(self._ln(roi_features)[pts_roi_inds.long()])
         if self.compute_dtype == torch.bfloat16 and FUSED_MLP and smp_xyzs.is_cuda and not (

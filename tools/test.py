@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Test / evaluation entry point with the CLI of the reference's tools/test.py (:23-87):
     python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--save-occ DIR] [--save-gt-occ DIR] [--online] [--eval iou waymo waymo_native] [--matcher {score_first,hungarian}] [--format-only]
+                         [--online-tuning N [--tuning-samples S]] [--decoder-dtype {f32,bf16}]
                          [--eval-options k=v ...] [--cfg-options k=v ...] [--launcher {none,pytorch}]
                          [--tmpdir DIR] [--gpu-collect] [--local_rank N]
 The test dataset is the config's data.test (the reference's data/waymo layout); with --data-root DIR it reads the tree
@@ -71,7 +72,22 @@ def parse_args(argv=None):
                     help='refine every tracklet frame by frame over a temporal K/V cache, the way the method is deployed '
                     '(sets test_cfg.online; the tracklet is moved into the ego frame of its FIRST frame, the one an online '
                     'caller knows); metrics and files as without it')
+    ap.add_argument('--online-tuning', type=int, metavar='N', default=None,
+                    help='tune the fused shape latent of every RoI against its own observation with N Adam steps before the '
+                    'heads read it (sets test_cfg.online_tuning = dict(num_iter=N, downsample_size=S, balance_sample=True))')
+    ap.add_argument('--tuning-samples', type=int, metavar='S', default=None,
+                    help='at most S sampled cells per RoI under --online-tuning (default -1: no limit)')
+    ap.add_argument('--decoder-dtype', choices=('f32', 'bf16'), default='f32',
+                    help='compute dtype of the occupancy decoder (bf16: the fused decoder and tuning kernels)')
     args = ap.parse_args(argv)
+    if args.online and args.online_tuning is not None:
+        ap.error('--online-tuning is not built for frame-by-frame inference (--online)')
+    if args.online and args.decoder_dtype != 'f32':
+        ap.error('--decoder-dtype does not go with --online')
+    if args.tuning_samples is not None and args.online_tuning is None:
+        ap.error('--tuning-samples goes with --online-tuning')
+    if args.online_tuning is not None and args.online_tuning < 0:
+        ap.error('--online-tuning takes a number of iterations >= 0')
     if 'LOCAL_RANK' not in os.environ:
         os.environ['LOCAL_RANK'] = str(args.local_rank)
     if args.matcher and 'waymo_native' not in (args.eval or []):
@@ -177,6 +193,10 @@ def main(argv=None):
         config.merge_from_dict(cfg, {'model.test_cfg.gt_occ_save_root': args.save_gt_occ, 'model.test_cfg.save_gt_occ': True})
     if args.online:
         config.merge_from_dict(cfg, {'model.test_cfg.online': True})
+    if args.online_tuning is not None:
+        config.merge_from_dict(cfg, {'model.test_cfg.online_tuning': dict(
+            num_iter=args.online_tuning, downsample_size=-1 if args.tuning_samples is None else args.tuning_samples,
+            balance_sample=True)})
     rank, world, local_rank = init_dist(args.dist_backend) if args.launcher == 'pytorch' else (0, 1, 0)
     dev = torch.device('cuda', local_rank % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)
@@ -186,6 +206,11 @@ def main(argv=None):
     ck = torch.load(args.checkpoint, map_location=dev)
     model.load_state_dict(ck['state_dict'] if 'state_dict' in ck else ck)
     model.eval()
+    if args.decoder_dtype == 'bf16':
+        from objectcentricocccompletion_amd.occ.occ_base import OccDecoder
+        for m in model.modules():
+            if isinstance(m, OccDecoder):
+                m.compute_dtype = torch.bfloat16
     lo, hi = shard_range(len(ds), rank, world)
     t0 = time.perf_counter()
     part = run_shard(model, ds, lo, hi, dev, args.seed)

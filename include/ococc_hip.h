@@ -1154,6 +1154,27 @@ int ococc_temporal_attention_step_long_f32(const float* q, int64_t ldq, const fl
                                            int32_t head_dim, float scale, int32_t window, int32_t ring, float* out,
                                            int64_t ldo, ococc_stream_t stream);
 
+/* A9, online, several frames per call  the chunk mode of the same kernel template (csrc/causal_attn_step.hip): one call
+ * advances every slot by one or more frames -- a tracklet that arrives with history (track birth, catch-up), or a
+ * recorded one fed T frames at a time.  Arguments as above, and ``off`` [n] (device) after ``slot``.  The rows of one slot
+ * are consecutive and in frame order, off[i] = 0, 1, 2, ... inside the slot's run; row i is frame t = pos[s] + off[i] of
+ * slot s = slot[i] and
+ *   out[i] = softmax(scale q[i] . K[frames lo .. t]) V[frames lo .. t]  per head,  lo as above,
+ * with the frames < pos[s] taken from the cache (row f, ring != 0: row f % cap) and the frames pos[s] .. t from the call's
+ * own rows k_new / v_new[i - off[i] + (f - pos[s])] -- in the order, operation for operation, of the step exports, so a
+ * chunk returns bit for bit what the single steps return.  The attention kernel neither writes the cache nor reads a row
+ * at or past pos[s]; a second kernel on the same stream then writes k_new / v_new to the rows of the new frames (in a ring
+ * whose run is longer than cap only the frame that ends up in each row).  pos is not advanced.  n may exceed slots.
+ * cap <= 256 and ring == 0: one score per thread; otherwise the long instance (cap <= 4096).  A row is skipped (nothing
+ * written, out[i] untouched) when its slot is out of range, off[i] < 0 or > i, slot[i - off[i]] != slot[i], without ring
+ * t >= cap, or it has more keys than the instance holds.  cap > 4096, ring with window < 1 or window > cap,
+ * head_dim % 4 != 0 or > 384, null pointers, unaligned rows: OCOCC_EINVAL, nothing launched.  No dropout; deterministic. */
+int ococc_temporal_attention_chunk_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk, const float* v_new,
+                                       int64_t ldv, const int32_t* slot, const int32_t* off, const int32_t* pos,
+                                       float* k_cache, float* v_cache, int32_t n, int32_t slots, int32_t cap, int32_t heads,
+                                       int32_t head_dim, float scale, int32_t window, int32_t ring, float* out, int64_t ldo,
+                                       ococc_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * A11 / A10, fused  the occupancy decoder's per-query MLP, one launch per layer (or one for the whole MLP):
  *   y = dropout(act(LayerNorm(x W^T + bias + add_rows[add_index]))),  optionally  head = y . head_weight + head_bias

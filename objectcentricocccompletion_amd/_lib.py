@@ -188,6 +188,8 @@ SIGNATURES = {
                                                   c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_i64, c_vp]),
     'ococc_temporal_attention_step_long_f32': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32,
                                                        c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    'ococc_temporal_attention_chunk_f32': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                                   c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     'ococc_sir_layer_fused_check': (c_i32, []),
     'ococc_sir_layer_fused_debug': (c_i32, [c_i32, c_i32]),
     'ococc_point_mlp_wgrad_f32': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),

@@ -20,7 +20,19 @@
 //     new frame t overwrites frame t - cap, which a window <= cap no longer reads -- a windowed model follows a tracklet of
 //     any length (pos up to 2^31 - 1) in ``window`` rows per slot.  Without ``ring`` a model that attends to all history
 //     gets up to 4096 cached frames.  A workgroup still reads and writes only its own head's column slice.
+//
+// Several frames per slot in one call (ococc_temporal_attention_chunk_f32): the ``kChunk`` mode of the same body, one
+// instance per kMaxS.  Row i is frame t = pos[slot] + off[i] of its slot, the rows of a slot consecutive and in frame order.
+// The keys and values of the frames < pos[slot] come from the cache, those of the frames pos[slot]..t from the call's own
+// rows k_new / v_new[i - off[i] + (f - pos[slot])]; the sums run over the keys lo..t in the order of the step kernel, so a
+// chunk gives bit for bit what the single steps give.  This mode never writes the cache and never reads a cache row at or
+// past pos[slot]: in a ring the row frame t will occupy may still hold a frame that an earlier row of the same chunk reads
+// (any chunk longer than cap - window), so no workgroup may depend on another's write.  The new rows are appended by a
+// second small kernel on the same stream (append_chunk_kernel) once every attention workgroup is done; of the frames of
+// one slot that fall into the same ring row (a run longer than cap) only the last is written.
 #include "common.hpp"
+
+#include <type_traits>
 
 namespace {
 
@@ -47,6 +59,25 @@ struct StepArgs {
   float* out;
   int64_t ldo;
 };
+struct ChunkArgs : StepArgs {   // (a type of its own: the kernel arguments of the step instances stay as they are)
+  const int32_t* off;           // [n] the row's place in its slot's run: row i - off[i] is the run's first
+  int32_t max_keys;             // append_chunk_kernel: kMaxS of the attention instance, whose guards it repeats
+};
+
+// chunk mode: the frame of row i, t = pos[s] + off[i] of slot s, p = pos[s], ``first`` the first row of the slot's run.
+// false: the row is skipped (a host bug must not read or write outside the call's rows or the cache).
+__device__ __forceinline__ bool chunk_frame(const ChunkArgs& a, int i, int& s, int& p, int& first, int& t) {
+  s = a.slot[i];
+  if (s < 0 || s >= a.slots) return false;
+  const int o = a.off[i];
+  if (o < 0 || o > i) return false;
+  first = i - o;
+  if (a.slot[first] != s) return false;
+  p = a.pos[s];
+  if (p < 0 || o > 0x7fffffff - p) return false;
+  t = p + o;
+  return true;
+}
 
 __device__ __forceinline__ float dot4(const f32x4 a, const f32x4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
 __device__ __forceinline__ float sum16(float v) {
@@ -57,8 +88,8 @@ __device__ __forceinline__ float sum16(float v) {
   return v;
 }
 
-template <int kMaxS>
-__global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
+template <int kMaxS, bool kChunk = false>
+__global__ void __launch_bounds__(kST) attn_step_kernel(std::conditional_t<kChunk, ChunkArgs, StepArgs> a) {
   constexpr bool kLong = kMaxS > kST;   // several scores per thread, ring addressing
   __shared__ __attribute__((aligned(16))) float sq[kSMaxD];          // the query row, scaled
   __shared__ __attribute__((aligned(16))) float sk[kSMaxD];          // the new key
@@ -67,9 +98,12 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
   __shared__ float red[2 * (kST / 64)];
   __shared__ __attribute__((aligned(16))) float part[kSK * kSMaxD];  // the 16 partial context rows
   const int i = blockIdx.x, h = blockIdx.y;
-  const int s = a.slot[i];
+  int cs = 0, ct = 0, p = 0, first = 0;   // chunk mode: p = pos[s] frames are cached, row ``first`` is frame p
+  if constexpr (kChunk)
+    if (!chunk_frame(a, i, cs, p, first, ct)) return;
+  const int s = kChunk ? cs : a.slot[i];
   if (s < 0 || s >= a.slots) return;   // (the host checks both; a host bug must not write outside the cache)
-  const int t = a.pos[s];
+  const int t = kChunk ? ct : a.pos[s];
   const bool ring = kLong && a.ring != 0;
   if (t < 0 || (!ring && t >= a.cap)) return;
   const int lo = a.window > 0 && t - a.window + 1 > 0 ? t - a.window + 1 : 0;
@@ -90,8 +124,10 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
     *(f32x4*)(sq + tid * 4) = qv * a.scale;
     *(f32x4*)(sk + tid * 4) = kv;
     *(f32x4*)(sv + tid * 4) = vv;
-    *(f32x4*)(kc + (int64_t)trow * ldc + tid * 4) = kv;
-    *(f32x4*)(vc + (int64_t)trow * ldc + tid * 4) = vv;
+    if constexpr (!kChunk) {   // (chunk mode: append_chunk_kernel, afterwards)
+      *(f32x4*)(kc + (int64_t)trow * ldc + tid * 4) = kv;
+      *(f32x4*)(vc + (int64_t)trow * ldc + tid * 4) = vv;
+    }
   }
   __syncthreads();
 
@@ -106,6 +142,8 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
         int row = row0 + j;
         if (ring && row >= a.cap) row -= a.cap;
         const float* krow = kc + (int64_t)row * ldc;
+        if constexpr (kChunk)   // a frame of this call: its own row, not the cache
+          if (lo + j >= p) krow = a.k_new + (int64_t)(first + (lo + j - p)) * a.ldk + col0;
         for (int c4 = c0; c4 < D4; c4 += 16) acc += dot4(*(const f32x4*)(sq + c4 * 4), *(const f32x4*)(krow + c4 * 4));
       }
     }
@@ -160,6 +198,8 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
       int row = row0 + j;
       if (ring && row >= a.cap) row -= a.cap;
       const float* vrow = vc + (int64_t)row * ldc;
+      if constexpr (kChunk)
+        if (lo + j >= p) vrow = a.v_new + (int64_t)(first + (lo + j - p)) * a.ldv + col0;
 #pragma unroll
       for (int jj = 0; jj < kSNJ; ++jj) {
         const int c4 = c0 + 16 * jj;
@@ -181,6 +221,33 @@ __global__ void __launch_bounds__(kST) attn_step_kernel(StepArgs a) {
   }
 }
 
+// after the chunk instance of attn_step_kernel on the same stream: one workgroup per row copies the row's new key and
+// value (all heads) to the cache row of its frame.  The guards are those of the attention kernel: a row it skipped is
+// not appended.  Ring, run longer than cap: row i + cap of the same run is frame t + cap, which lands in the same cache
+// row -- row i is superseded and stays unwritten, as if the frames had been written in order.
+__global__ void __launch_bounds__(kST) append_chunk_kernel(ChunkArgs a) {
+  const int i = blockIdx.x;
+  int s, t, p, first;
+  if (!chunk_frame(a, i, s, p, first, t)) return;
+  const bool ring = a.ring != 0;
+  if (!ring && t >= a.cap) return;
+  const int lo = a.window > 0 && t - a.window + 1 > 0 ? t - a.window + 1 : 0;
+  const int nk = t - lo + 1;
+  if (nk > a.cap || nk > a.max_keys) return;
+  if (ring && (int64_t)i + a.cap < a.n && a.slot[i + a.cap] == s) return;
+  const int trow = ring ? t % a.cap : t;
+  const int64_t ldc = (int64_t)a.H * a.D;
+  const int E4 = (a.H * a.D) >> 2;
+  float* kc = a.k_cache + ((int64_t)s * a.cap + trow) * ldc;
+  float* vc = a.v_cache + ((int64_t)s * a.cap + trow) * ldc;
+  const float* kn = a.k_new + (int64_t)i * a.ldk;
+  const float* vn = a.v_new + (int64_t)i * a.ldv;
+  for (int c4 = threadIdx.x; c4 < E4; c4 += kST) {
+    *(f32x4*)(kc + c4 * 4) = *(const f32x4*)(kn + c4 * 4);
+    *(f32x4*)(vc + c4 * 4) = *(const f32x4*)(vn + c4 * 4);
+  }
+}
+
 // the launch behind both exports (their checks come first: nothing is dereferenced or launched before they pass)
 template <int kMaxS>
 int launch_step(const float* q, int64_t ldq, const float* k_new, int64_t ldk, const float* v_new, int64_t ldv,
@@ -196,6 +263,15 @@ int launch_step(const float* q, int64_t ldq, const float* k_new, int64_t ldk, co
   a.scale = scale; a.window = window; a.ring = ring;
   a.out = out; a.ldo = ldo;
   hipLaunchKernelGGL(attn_step_kernel<kMaxS>, dim3(n, H), dim3(kST), 0, (hipStream_t)stream_, a);
+  OCOCC_CHECK_LAUNCH();
+  return OCOCC_OK;
+}
+
+template <int kMaxS>
+int launch_chunk(const ChunkArgs& a, ococc_stream_t stream_) {
+  hipLaunchKernelGGL((attn_step_kernel<kMaxS, true>), dim3(a.n, a.H), dim3(kST), 0, (hipStream_t)stream_, a);
+  OCOCC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(append_chunk_kernel, dim3(a.n), dim3(kST), 0, (hipStream_t)stream_, a);
   OCOCC_CHECK_LAUNCH();
   return OCOCC_OK;
 }
@@ -242,4 +318,30 @@ extern "C" int ococc_temporal_attention_step_long_f32(const float* q, int64_t ld
   OCOCC_STEP_COMMON_CHECKS();
   return launch_step<kLongMaxS>(q, ldq, k_new, ldk, v_new, ldv, slot, pos, k_cache, v_cache, n, slots, cap, H, D, scale,
                                 window, ring != 0, out, ldo, stream_);
+}
+
+extern "C" int ococc_temporal_attention_chunk_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk,
+                                                  const float* v_new, int64_t ldv, const int32_t* slot, const int32_t* off,
+                                                  const int32_t* pos, float* k_cache, float* v_cache, int32_t n,
+                                                  int32_t slots, int32_t cap, int32_t H, int32_t D, float scale,
+                                                  int32_t window, int32_t ring, float* out, int64_t ldo,
+                                                  ococc_stream_t stream_) {
+  OCOCC_REQUIRE(n >= 0 && slots >= 1 && cap >= 1 && H >= 1 && D >= 1, "empty cache or negative row count");
+  OCOCC_REQUIRE(cap <= kLongMaxS, "caches of up to 4096 frames per slot");
+  OCOCC_REQUIRE(ring == 0 || (window >= 1 && window <= cap),
+                "a ring cache needs a window of 1 .. cap frames (the row of frame t overwrites frame t - cap)");
+  OCOCC_REQUIRE(D <= kSMaxD && D % 4 == 0, "head width a multiple of 4 up to 384");
+  OCOCC_STEP_COMMON_CHECKS();
+  OCOCC_REQUIRE(off, "null pointer");
+  const bool small = cap <= kSMaxS && ring == 0;   // one score per thread, as ococc_temporal_attention_step_f32
+  ChunkArgs a{};
+  a.q = q; a.k_new = k_new; a.v_new = v_new;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+  a.slot = slot; a.pos = pos; a.off = off;
+  a.k_cache = k_cache; a.v_cache = v_cache;
+  a.n = n; a.slots = slots; a.cap = cap; a.H = H; a.D = D;
+  a.scale = scale; a.window = window; a.ring = ring != 0;
+  a.out = out; a.ldo = ldo;
+  a.max_keys = small ? kSMaxS : kLongMaxS;
+  return small ? launch_chunk<kSMaxS>(a, stream_) : launch_chunk<kLongMaxS>(a, stream_);
 }

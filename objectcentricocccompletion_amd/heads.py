@@ -776,6 +776,30 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
                                               self.test_cfg.get('attn_window_size', -1))
         return self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
 
+    @torch.no_grad()
+    def forward_steps(self, pts_xyz, pts_features, pts_info, roi_inds, rois, slot_rows, cache):
+        """``forward_step`` for one OR MORE new frames per tracklet in one call: ``slot_rows`` is the slot of every row
+        and may repeat -- the rows of a slot are its new frames, consecutive and in frame order (TemporalCache.check_steps)
+        -- and the frame index of row j of the run of slot s is cache.pos_host[s] + j.  The temporal transformer runs
+        TransformerEncoder.steps (one attention launch per layer for all rows); everything else works per RoI.  The
+        refusals are those of ``forward_step``.  Returns the dict of ``forward`` for the n rows, in input order."""
+        from .tracklet import host_index
+        if self.training:
+            raise RuntimeError('OccBBoxHead.forward_steps is inference only: call .eval() first')
+        if self.test_cfg.get('allow_attn_future', False):
+            raise ValueError('test_cfg.allow_attn_future lets a frame attend to later frames: such a model cannot run '
+                             'frame by frame')
+        if self.test_cfg.get('online_tuning', False):
+            raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference')
+        slots, offsets, _ = cache.check_steps(slot_rows)
+        roi_frame_inds = host_index([cache.pos_host[s] + j for s, j in zip(slots, offsets)], rois.device)
+        final_cluster_feats, nonempty_roi_mask, local_roi_feats, _ = self._encode_rois(pts_xyz, pts_features, pts_info,
+                                                                                       roi_inds, rois)
+        pos_embed = self._pos_embed(roi_frame_inds, rois[:, 1:])
+        roi_feats_fused = self.trans_enc.steps(final_cluster_feats, pos_embed, slots, cache,
+                                               self.test_cfg.get('attn_window_size', -1))
+        return self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
+
     # ------------------------------------------------------------------ temporal transformer
     def get_occ(self, local_roi_feats, rois, transform=True, ori_roi_feats=None):
         """ococc_bbox_head.py:813-841: explicit occupancy of every RoI from the fused features (and, when

@@ -144,6 +144,37 @@ class TemporalCache(object):
         for s in slots:
             self.pos_host[s] += 1
 
+    def check_steps(self, slot_rows):
+        """the host-side checks of one chunked step (TransformerEncoder.steps) over ``slot_rows``, the slot of every row:
+        every slot in range, the rows of a slot consecutive (they are its new frames in order), room for the whole run
+        -- pos_host[s] + T_s <= cap, in a ring <= 2**31 - 1.  Returns (slots, offsets, runs): the row list as ints, the
+        place 0, 1, 2, ... of each row in its slot's run, and {slot: T_s} in order of appearance.  Modifies nothing."""
+        from .. import _lib as L
+        slots = [int(s) for s in slot_rows]
+        offsets, runs = [], {}
+        for i, s in enumerate(slots):
+            if not 0 <= s < self.slots:
+                raise L.OcoccError(f'TemporalCache: slot {s} outside 0..{self.slots - 1}')
+            if s in runs and slots[i - 1] != s:
+                raise L.OcoccError(f'TemporalCache: the rows of slot {s} are not consecutive in {slots}: the frames of a '
+                                   'slot come as one run, in frame order')
+            offsets.append(runs.get(s, 0))
+            runs[s] = offsets[-1] + 1
+        for s, T in runs.items():
+            if self.ring:
+                if self.pos_host[s] + T > self.MAX_FRAMES:
+                    raise L.OcoccError(f'TemporalCache: {T} more frames take slot {s} from {self.pos_host[s]} past '
+                                       '2**31 - 1 frames, the last its int32 counter holds (reset the slot)')
+            elif self.pos_host[s] + T > self.cap:
+                raise L.OcoccError(f'TemporalCache: slot {s} holds {self.pos_host[s]} frames, {T} more do not fit cap = '
+                                   f'{self.cap}; a tracklet longer than the cache is not supported (reset the slot or '
+                                   f'build the cache with a larger cap <= {self.MAX_LONG_CAP if self.long else 256})')
+        return slots, offsets, runs
+
+    def advance_steps(self, slots, slot_dev):
+        """``advance`` after a chunked step: one more frame per ROW of ``slots`` (a slot gains its run's T_s frames)"""
+        self.advance(slots, slot_dev)   # (index_add_ counts a slot once per row it has)
+
     def reset(self, slots=None):
         """forget the frames of ``slots`` (all when None): the slot can follow a new tracklet.  The cached rows are left
         as they are -- nothing reads a row at or past ``pos``."""
@@ -286,6 +317,34 @@ class MultiheadAttention(nn.Module):
         return gemm.linear(ctx, self.out_proj.weight, self.out_proj.bias)
 
 
+    @torch.no_grad()
+    def steps(self, x_qk, x_v, slot, off, cache_k, cache_v, pos, window=-1, ring=False):
+        """``step`` for one OR MORE new frames per tracklet in one launch (ococc_temporal_attention_chunk_f32): the rows
+        of a slot are consecutive and in frame order, ``off`` int32 [n] the place 0, 1, 2, ... of each row in its slot's
+        run (TemporalCache.check_steps).  Row i is frame pos[slot] + off[i]: it attends to the cached frames and to the
+        earlier rows of its own run; the keys and values of all rows are appended afterwards, inside the same call.  The
+        export picks the instance by cap and ``ring`` itself.  ``pos`` is left as it is."""
+        from .. import _lib as L
+        _eval_only(self, 'MultiheadAttention.steps')
+        L.require_device(x_qk, x_v, slot, off, cache_k, cache_v, pos)
+        n, E = x_qk.shape
+        assert E == self.embed_dim and x_v.shape == (n, E) and slot.shape == off.shape == (n,)
+        assert slot.dtype == off.dtype == pos.dtype == torch.int32 and cache_k.shape == cache_v.shape and cache_k.shape[2] == E
+        assert cache_k.dtype == cache_v.dtype == torch.float32 and cache_k.is_contiguous() and cache_v.is_contiguous()
+        assert pos.shape == (cache_k.shape[0],)
+        w, b = self.in_proj_weight, self.in_proj_bias
+        qk = gemm.linear(x_qk.float(), w[:2 * E], b[:2 * E])
+        v = gemm.linear(x_v.float(), w[2 * E:], b[2 * E:])
+        q, k = qk[:, :E], qk[:, E:]
+        ctx = torch.empty((n, E), dtype=torch.float32, device=qk.device)
+        L.check(L.lib.ococc_temporal_attention_chunk_f32(
+            q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), slot.data_ptr(), off.data_ptr(),
+            pos.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(), n, cache_k.shape[0], cache_k.shape[1], self.num_heads,
+            self.head_dim, float(self.head_dim) ** -0.5, int(window), int(bool(ring)), ctx.data_ptr(), ctx.stride(0),
+            L.stream()), 'temporal_attention_chunk')
+        return gemm.linear(ctx, self.out_proj.weight, self.out_proj.bias)
+
+
 class SimpleEncoderLayer(nn.Module):
     """Post-LN encoder layer with q = k = src + pos, v = src (layers.py:35-87): attention block, then feed-forward block,
     each `x <- LayerNorm(x + dropout(block(x)))` with the LayerNorm on the HIP kernel."""
@@ -327,6 +386,17 @@ class SimpleEncoderLayer(nn.Module):
         _eval_only(self, 'SimpleEncoderLayer.step')
         attended = self.self_attn.step(self.with_pos_embed(src, pos_enc), src, slot, cache_k, cache_v, pos, window, ring,
                                        long)
+        x = self._residual_norm(self.norm1, src, attended, self.dropout1)
+        return self._residual_norm(self.norm2, x, self._feed_forward(x), self.dropout2)
+
+
+    @torch.no_grad()
+    def steps(self, src, pos_enc, slot, off, cache_k, cache_v, pos, window=-1, ring=False):
+        """``step`` for one or more new frames per tracklet (MultiheadAttention.steps): everything but the attention
+        works per row"""
+        _eval_only(self, 'SimpleEncoderLayer.steps')
+        attended = self.self_attn.steps(self.with_pos_embed(src, pos_enc), src, slot, off, cache_k, cache_v, pos, window,
+                                        ring)
         x = self._residual_norm(self.norm1, src, attended, self.dropout1)
         return self._residual_norm(self.norm2, x, self._feed_forward(x), self.dropout2)
 
@@ -376,4 +446,35 @@ class TransformerEncoder(nn.Module):
         for i, layer in enumerate(self.layers):
             x = layer.step(x, pos_enc, slot_dev, cache.k[i], cache.v[i], cache.pos, window, ring, long)
         cache.advance(slots, slot_dev)
+        return x
+
+    @torch.no_grad()
+    def steps(self, src, pos_enc, slot_rows, cache, window=-1):
+        """One or more new frames for each of several tracklets in one call: src, pos_enc [n, E], one row per (tracklet,
+        frame); ``slot_rows``: the cache slot of each row, a list of ints (a tensor is read back), the rows of a slot
+        consecutive and in frame order -- [3, 3, 3, 0, 5, 5] gives slot 3 three frames, slot 0 one, slot 5 two.  Row j of
+        the run of slot s equals row pos[s] + j of ``forward`` over the frames 0..pos[s] + j of that tracklet under the
+        future mask (windowed by ``window`` > 0).  Every layer is one attention launch and one append launch whatever n
+        is; a ring cache takes runs longer than its cap.  Bumps ``cache.pos`` and its host mirror by the runs once, after
+        the last layer.  The host-side checks (a window a ring cache cannot serve, slots out of range, rows of a slot that
+        are not consecutive, a run past ``cache.cap``, CPU tensors) raise before anything is launched."""
+        from .. import _lib as L
+        from ..tracklet import host_index
+        _eval_only(self, 'TransformerEncoder.steps')
+        if cache.num_layers != self.num_layers:
+            raise L.OcoccError(f'TemporalCache of {cache.num_layers} layers for an encoder of {self.num_layers}')
+        ring = cache.ring
+        if ring and not 1 <= int(window) <= cache.cap:
+            raise L.OcoccError(f'a ring TemporalCache of cap = {cache.cap} rows serves windows of 1..{cache.cap} frames, not '
+                               f'window = {window}: the row of frame t overwrites frame t - cap')
+        slots, offsets, _ = cache.check_steps(slot_rows.tolist() if torch.is_tensor(slot_rows) else slot_rows)
+        if len(slots) != src.shape[0]:
+            raise L.OcoccError(f'{len(slots)} slots for {src.shape[0]} rows')
+        L.require_device(src, pos_enc, cache.pos)
+        both = host_index(slots + offsets, src.device, dtype=torch.int32)   # (one upload)
+        slot_dev, off_dev = both[:len(slots)], both[len(slots):]
+        x = src
+        for i, layer in enumerate(self.layers):
+            x = layer.steps(x, pos_enc, slot_dev, off_dev, cache.k[i], cache.v[i], cache.pos, window, ring)
+        cache.advance_steps(slots, slot_dev)
         return x

@@ -453,12 +453,57 @@ class TrackletRoIHeadOCC(nn.Module):
                     fused_roi_feats=res['fused_roi_feats'], ori_roi_feats=res['ori_roi_feats'])
 
     @torch.no_grad()
+    def simple_test_steps(self, pts_xyz, pts_feats, pts_row_idx, boxes, scores, labels, slot_rows, state, gt_rois=None):
+        """``simple_test_step`` for one OR MORE new frames per tracklet in one call -- a tracklet that arrives with
+        history (a track confirmed after several hits, a dropped batch), or a recorded one fed T frames at a time.  A row
+        is one (tracklet, frame): ``pts_row_idx`` the ROW 0..n-1 a point belongs to, boxes [n, 7], scores [n], labels [n]
+        of the rows, ``slot_rows`` the slot of every row in ``state``.  The rows of a slot are its new frames, consecutive
+        and in frame order ([3, 3, 3, 0, 5, 5]: three frames for slot 3, one for slot 0, two for slot 5); a slot's frames
+        continue where its earlier steps stopped.  Pooling, decode and the returned dict are those of simple_test_step,
+        n rows in input order; the temporal transformer takes all rows in one launch per layer
+        (OccBBoxHead.forward_steps).  The coordinate-frame rule of simple_test_step holds.
+
+        Reported on the host before anything is launched: slots out of range, rows of a slot that are not consecutive, a
+        run past the cache's cap (OcoccError), CPU tensors (OcoccError), training mode (RuntimeError)."""
+        from . import _lib as L
+        if self.training:
+            raise RuntimeError('simple_test_steps is inference only: call .eval() first')
+        slots, _, _ = state.cache.check_steps(slot_rows)
+        L.require_device(pts_xyz, pts_feats, pts_row_idx, boxes, scores, labels, state.cache.pos)
+        n = boxes.size(0)
+        if len(slots) != n or scores.size(0) != n or labels.size(0) != n:
+            raise L.OcoccError(f'{len(slots)} slots, {scores.size(0)} scores, {labels.size(0)} labels for {n} boxes')
+        if pts_xyz.size(0) == 0:   # (rows without points: one zero row, as the detector gives an empty sample)
+            pts_xyz, pts_feats, pts_row_idx = TrackletDetectorOCC.fake_points_for_empty_input(
+                [pts_xyz, pts_feats, pts_row_idx])
+        rois = bbox3d2roi([boxes[i:i + 1, :7] for i in range(n)])     # column 0: the row's own index
+        same = torch.zeros((n,), dtype=torch.long, device=boxes.device)   # (a row's points are its frame's: one frame key)
+        pooled = self._pool_points(pts_xyz, pts_feats, pts_row_idx.long(), torch.zeros_like(pts_row_idx, dtype=torch.long),
+                                   rois, scores, same)
+        res = self.bbox_head.forward_steps(*pooled, rois, slots, state.cache)
+        one = torch.cat([torch.zeros_like(rois[:, :1]), rois[:, 1:]], 1)   # (one group: get_bboxes splits by column 0)
+        out_boxes, out_scores, out_labels, valid = self.bbox_head.get_bboxes_from_tracklet(
+            one, res['cls_score'], res['bbox_pred'], res['nonempty_roi_mask'], labels, scores, None, gt_rois=gt_rois,
+            cfg=self.test_cfg)[0]
+        return dict(boxes=out_boxes, scores=out_scores, labels=out_labels, valid=valid,
+                    fused_roi_feats=res['fused_roi_feats'], ori_roi_feats=res['ori_roi_feats'])
+
+    def online_chunk(self):
+        """test_cfg.online_chunk: the frames simple_test_online feeds per call, an int >= 1 (default 1: single steps)"""
+        chunk = self.test_cfg.get('online_chunk', 1)
+        if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+            raise ValueError(f'test_cfg.online_chunk is the number of frames per call, an int >= 1, not {chunk!r}')
+        return chunk
+
+    @torch.no_grad()
     def simple_test_online(self, pts_xyz, pts_feats, pts_batch_idx, pts_frame_inds, img_metas, tracklet_list,
                            gt_candidates_list=None, gt_occs_list=None, gt_occ_scores_list=None, **kwargs):
         """simple_test computed the way the method is deployed: the tracklet is fed to simple_test_step frame by frame in
         one slot of a fresh state, then test_occ / the exports run on the concatenated per-step features.  Same arguments,
         same result (the temporal transformer is causal: frame t never saw the later frames offline either); what
         simple_test does when test_cfg.online is set.  The points are taken in the coordinate frame they come in.
+        test_cfg.online_chunk = T > 1: T frames per simple_test_steps call instead (the last call takes the rest), through
+        the same cache -- a ring of W rows takes chunks longer than W.
         Up to 256 frames: a cache of that many rows.  Above: with test_cfg.attn_window_size = W > 0 a ring cache of W rows
         (any length), without a window a long cache of up to 4096 rows; past that an OcoccError."""
         from . import _lib as L
@@ -466,6 +511,7 @@ class TrackletRoIHeadOCC(nn.Module):
         assert len(tracklet_list) == 1, 'only support batch size 1'
         if self.test_cfg.get('tta', None) is not None:
             raise NotImplementedError('test_cfg.online with test_cfg.tta')
+        chunk = self.online_chunk()
         num = len(tracklet_list[0])
         window = self.test_cfg.get('attn_window_size', -1)
         if num <= 256:
@@ -487,10 +533,20 @@ class TrackletRoIHeadOCC(nn.Module):
         counts = torch.bincount(pts_frame_inds, minlength=num).tolist()
         assert len(counts) == num, 'a point lies in a frame past the tracklet'
         steps = []
-        for t, sel in enumerate(order.split(counts)):
-            steps.append(self.simple_test_step(
-                pts_xyz[sel], pts_feats[sel], torch.zeros_like(pts_batch_idx[sel]), rois[t:t + 1, 1:8], cls_preds[t:t + 1],
-                labels_3d[t:t + 1], [0], state, gt_rois=None if gt_rois is None else gt_rois[t:t + 1]))
+        if chunk == 1:
+            for t, sel in enumerate(order.split(counts)):
+                steps.append(self.simple_test_step(
+                    pts_xyz[sel], pts_feats[sel], torch.zeros_like(pts_batch_idx[sel]), rois[t:t + 1, 1:8],
+                    cls_preds[t:t + 1], labels_3d[t:t + 1], [0], state, gt_rois=None if gt_rois is None else gt_rois[t:t + 1]))
+        else:   # T frames per call: a point's row is its frame's place in the chunk
+            first = 0
+            for t in range(0, num, chunk):
+                T = min(chunk, num - t)
+                sel = order[first:first + sum(counts[t:t + T])]
+                first += sel.numel()
+                steps.append(self.simple_test_steps(
+                    pts_xyz[sel], pts_feats[sel], pts_frame_inds[sel] - t, rois[t:t + T, 1:8], cls_preds[t:t + T],
+                    labels_3d[t:t + T], [0] * T, state, gt_rois=None if gt_rois is None else gt_rois[t:t + T]))
         cat = lambda k: torch.cat([s[k] for s in steps], 0)
         res = dict(fused_roi_feats=cat('fused_roi_feats'), ori_roi_feats=cat('ori_roi_feats'), nonempty_roi_mask=cat('valid'))
         decoded = [(cat('boxes'), cat('scores'), cat('labels'), cat('valid'))]

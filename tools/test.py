@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Test / evaluation entry point with the CLI of the reference's tools/test.py (:23-87):
-    python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--save-occ DIR] [--save-gt-occ DIR] [--online] [--eval iou waymo waymo_native] [--matcher {score_first,hungarian}] [--format-only]
+    python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--save-occ DIR] [--save-gt-occ DIR] [--online [--online-chunk T]] [--eval iou waymo waymo_native] [--matcher {score_first,hungarian}] [--format-only]
                          [--online-tuning N [--tuning-samples S]] [--decoder-dtype {f32,bf16}]
                          [--eval-options k=v ...] [--cfg-options k=v ...] [--launcher {none,pytorch}]
                          [--tmpdir DIR] [--gpu-collect] [--local_rank N]
@@ -72,6 +72,9 @@ def parse_args(argv=None):
                     help='refine every tracklet frame by frame over a temporal K/V cache, the way the method is deployed '
                     '(sets test_cfg.online; the tracklet is moved into the ego frame of its FIRST frame, the one an online '
                     'caller knows); metrics and files as without it')
+    ap.add_argument('--online-chunk', type=int, metavar='T', default=None,
+                    help='with --online: feed T frames of the tracklet per call instead of one (sets test_cfg.online_chunk; '
+                    'the same result, one attention launch per layer for the T frames)')
     ap.add_argument('--online-tuning', type=int, metavar='N', default=None,
                     help='tune the fused shape latent of every RoI against its own observation with N Adam steps before the '
                     'heads read it (sets test_cfg.online_tuning = dict(num_iter=N, downsample_size=S, balance_sample=True))')
@@ -84,6 +87,10 @@ def parse_args(argv=None):
         ap.error('--online-tuning is not built for frame-by-frame inference (--online)')
     if args.online and args.decoder_dtype != 'f32':
         ap.error('--decoder-dtype does not go with --online')
+    if args.online_chunk is not None and not args.online:
+        ap.error('--online-chunk goes with --online')
+    if args.online_chunk is not None and args.online_chunk < 1:
+        ap.error('--online-chunk takes a number of frames >= 1')
     if args.tuning_samples is not None and args.online_tuning is None:
         ap.error('--tuning-samples goes with --online-tuning')
     if args.online_tuning is not None and args.online_tuning < 0:
@@ -193,6 +200,8 @@ def main(argv=None):
         config.merge_from_dict(cfg, {'model.test_cfg.gt_occ_save_root': args.save_gt_occ, 'model.test_cfg.save_gt_occ': True})
     if args.online:
         config.merge_from_dict(cfg, {'model.test_cfg.online': True})
+    if args.online_chunk is not None:
+        config.merge_from_dict(cfg, {'model.test_cfg.online_chunk': args.online_chunk})
     if args.online_tuning is not None:
         config.merge_from_dict(cfg, {'model.test_cfg.online_tuning': dict(
             num_iter=args.online_tuning, downsample_size=-1 if args.tuning_samples is None else args.tuning_samples,

@@ -3,7 +3,8 @@
 the temporal K/V cache) at frame t = 1, 50 and 199 for 1 and 64 tracklets at a time on the ococcnet model, against what a
 user without it does at that frame: TrackletRoIHeadOCC.simple_test on the prefix of t + 1 frames, once per tracklet
 (simple_test takes one tracklet per call).
-    python tools/time_online.py [--slots 1 64] [--frames 1 50 199] [--long-frame 1000] [--points 256] [--reps 7] [--out FILE.md]
+    python tools/time_online.py [--slots 1 64] [--frames 1 50 199] [--long-frame 1000] [--catch-up 32] [--points 256]
+                                [--reps 7] [--out FILE.md]
 Synthetic vehicle tracklets (oracle/synth.py) of --points points per frame, random weights.  For a step at frame t the
 cache is set to t cached frames of random keys and values -- what it holds does not change the work -- and pos is set back
 after every call.  Both paths are warmed up at every shape, then timed alternately; a call is timed with device events
@@ -12,7 +13,12 @@ around it and with the host clock up to a device synchronise; median (min - max)
 Past 256 frames (--long-frame, default 1000; 0: skip): two more rows per tracklet count, a step at that frame of a ring cache
 of 16 rows with test_cfg.attn_window_size = 16 and of a long cache of --long-frame + 1 rows without a window (the step
 reads 16 and --long-frame cached frames).  The points and boxes are those of the last synthetic frame -- only the frame
-index the positional encoding gets and the cache counter say 1000 -- so no longer synthetic tracklets are built."""
+index the positional encoding gets and the cache counter say 1000 -- so no longer synthetic tracklets are built.
+
+Several frames per call (--catch-up, default 32; 0: skip): three more rows per tracklet count, bringing every tracklet from
+frame 0 to frame --catch-up of a reset cache -- by that many simple_test_step calls, by simple_test_steps calls of 8 frames
+per tracklet, and by one simple_test_steps call with all frames.  The inputs of every call are prepared beforehand; the
+three forms are warmed up, then timed alternately; the last column divides the median of the device events by the frames."""
 import argparse
 import os
 
@@ -54,6 +60,7 @@ def main():
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--long-frame', type=int, default=1000, help='frame of the ring / long cache rows (0: none)')
+    ap.add_argument('--catch-up', type=int, default=32, help='frames of the several-frames-per-call rows (0: none)')
     ap.add_argument('--out', default=None, help='also write the table to this markdown file')
     args = ap.parse_args()
     import torch
@@ -67,7 +74,9 @@ def main():
     cfg = ococcnet_model_cfg()
     cfg['test_cfg']['test_occ_iou'] = False          # (no labels here: the refinement alone, on both sides)
     rh = DETECTORS.build(cfg).to(dev).eval().roi_head
-    total = max(args.frames, default=1) + 1
+    total = max(max(args.frames, default=1) + 1, args.catch_up)
+    chunk_lines = ['| tracklets | frames | path | calls | device events, ms: median (min - max) | host clock, ms | '
+                   'per frame, ms |', '|---|---|---|---|---|---|---|']
     lines = ['| tracklets | frame t | path | device events, ms: median (min - max) | host clock, ms |', '|---|---|---|---|---|']
     with torch.no_grad():
         for slots in args.slots:
@@ -120,6 +129,49 @@ def main():
                                    ('offline', f'`simple_test` on frames 0..{t}, once per tracklet')):
                     lines.append(f'| {slots} | {t} | {what} | {fmt(times[name][0])} | {fmt(times[name][1])} |')
                     print(lines[-1], flush=True)
+            if args.catch_up > 0:
+                F = args.catch_up
+
+                def chunk_inputs(a, T):
+                    """the frames a..a+T-1 of every tracklet as rows b * T + (t - a): the rows of a slot consecutive"""
+                    lo = [0 if a == 0 else int(d['ends'][a - 1]) for d in trks]
+                    hi = [int(d['ends'][a + T - 1]) for d in trks]
+                    pts = torch.cat([d['points'][x:y] for d, x, y in zip(trks, lo, hi)])
+                    row = torch.cat([d['frame'][x:y].long() - a + b * T for b, (d, x, y) in enumerate(zip(trks, lo, hi))])
+                    return (pts[:, :3].contiguous(), pts[:, 3:].contiguous(), row, torch.cat([d['boxes'][a:a + T] for d in trks]),
+                            torch.cat([d['scores'][a:a + T] for d in trks]), torch.zeros(slots * T, dtype=torch.long, device=dev),
+                            [b for b in range(slots) for _ in range(T)])
+
+                single = [frame_inputs(t) for t in range(F)]
+                forms = [('step', f'{F} `simple_test_step` calls', F, None)]
+                for T in dict.fromkeys((min(8, F), F)):
+                    calls = [chunk_inputs(a, min(T, F - a)) for a in range(0, F, T)]
+                    forms.append((f'chunk{T}', f'`simple_test_steps`, {T} frames per tracklet and call', len(calls), calls))
+
+                def catch_up(calls):
+                    state.reset()
+                    if calls is None:
+                        for xyz, feats, batch, boxes, scores in single:
+                            rh.simple_test_step(xyz, feats, batch, boxes, scores, labels, slot, state)
+                    else:
+                        for xyz, feats, row, boxes, scores, lab, slot_rows in calls:
+                            rh.simple_test_steps(xyz, feats, row, boxes, scores, lab, slot_rows, state)
+                    assert state.frames == [F] * slots
+
+                for _ in range(args.warmup):
+                    for _, _, _, calls in forms:
+                        catch_up(calls)
+                times = {name: ([], []) for name, _, _, _ in forms}
+                for _ in range(args.reps):            # alternating, as above
+                    for name, _, _, calls in forms:
+                        e, h = timed(lambda: catch_up(calls), 1)
+                        times[name][0].extend(e)
+                        times[name][1].extend(h)
+                for name, what, ncalls, _ in forms:
+                    e, h = times[name]
+                    chunk_lines.append(f'| {slots} | {F} | {what} | {ncalls} | {fmt(e)} | {fmt(h)} | '
+                                       f'{sorted(e)[len(e) // 2] / F:.3f} |')
+                    print(chunk_lines[-1], flush=True)
             del state
             if args.long_frame > 0:
                 T = args.long_frame
@@ -151,6 +203,8 @@ def main():
                     print(lines[-1], flush=True)
                     del st
     text = '\n'.join(lines)
+    if len(chunk_lines) > 2:
+        text += '\n\n' + '\n'.join(chunk_lines)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, 'w') as f:

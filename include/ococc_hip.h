@@ -688,6 +688,31 @@ int ococc_occ_iou_count(const float* logits, const int64_t* labels, const float*
                         ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * sample masks of the train_cfg variants of OccBBoxHead.loss_occ (csrc/occ_loss_masks.hip), replacing the ATen chains of
+ *   mmdet3d/models/roi_heads/bbox_heads/ococc_bbox_head.py:706-710 (zeros_like, masked assignment, view, repeat),
+ *   :713-722 (no_loss_for_outside: neg, div, two compares, two all, &, float, *), :730-734 (no_loss_for_observed_feats:
+ *   get_cls_from_pred, ==, float, *), :749-753 (residual_loss: get_cls_from_pred, !=, sum) and :792 (weights > 0).
+ * Row i * K + k is sample k of positive RoI i.  xyz [M * K, 3] f32 the sample in the RoI frame; box_size [M, 3] f32
+ * (rois[pos][:, 4:7]); score [M] f32 the label confidence; ori_logits [M * K] f32 the decoder's logits of
+ * ori_roi_feats (cls_dim 1); labels [M * K] int64 (occupied: == 1).  flags: 1 outside | 2 observed | 4 unmatched;
+ * xyz / box_size are read only with 1, ori_logits only with 2 or 4, labels only with 4 (NULL otherwise).
+ *   weights [M * K] f32 = (score[i] > score_thresh)            strict; NaN is 0
+ *       [1] * (-size / 2 <= xyz <= size / 2 on all three axes)   f32 compares, bounds inclusive, a NaN coordinate is outside
+ *       [2] * (class of ori_logits == 0)
+ *   unmatched [M * K] u8 = (labels == 1) != (class of ori_logits)   written only with flag 4
+ *   counts [3] int64 (zeroed here): #(weights > 0), #unmatched, #(unmatched and weights > 0); the last two 0 without 4
+ * class = 1 / (1 + exp(-logit)) > pos_thresh in f32 (ATen's sigmoid; NaN is class 0), the device function of
+ * ococc_occ_iou_count.  16-byte loads and stores when every pointer is 16-byte aligned, element-wise ones otherwise.
+ * Ballots + popcounts per wave, one 64-bit vector atomic per wave and count; integer sums only: the same input gives
+ * the same bytes.  M == 0 or K == 0: no launch, counts zero.  One grid pass covers ococc_occ_loss_masks_pass_rows()
+ * rows; more rows take further trips of the grid-stride loop.
+ * ------------------------------------------------------------------------ */
+int64_t ococc_occ_loss_masks_pass_rows(void);
+int ococc_occ_loss_masks_f32(const float* xyz, const float* box_size, const float* score, const float* ori_logits,
+                             const int64_t* labels, int64_t M, int64_t K, float score_thresh, float pos_thresh,
+                             int32_t flags, float* weights, uint8_t* unmatched, int64_t* counts, ococc_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * completed-occupancy export (csrc/occ_export.hip): the dense-grid decode around the decoder and the compaction of its
  * occupied cells, behind OccDecoder.get_occ_packed and TrackletRoIHeadOCC.save_occ_from_tracklet
  *   (mmdet3d/models/roi_heads/tracklet_roi_head_occ.py:612-745).

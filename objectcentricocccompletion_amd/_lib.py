@@ -122,6 +122,9 @@ SIGNATURES = {
     'ococc_frame_assign_i32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32,
                                        c_i64, c_i64, c_i32, c_i32, ctypes.c_float * 5, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     'ococc_occ_iou_count': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_vp, c_i64, c_i64, c_vp]),
+    'ococc_occ_loss_masks_pass_rows': (c_i64, []),
+    'ococc_occ_loss_masks_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp,
+                                         c_vp]),
     'ococc_dense_grid_cells_f32': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i64, c_i64, c_vp, c_vp, c_vp]),
     'ococc_occ_select_max_tiles': (c_i64, [c_i64, c_i32]),
     'ococc_occ_select_count': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp, c_vp]),

@@ -57,6 +57,9 @@ class _GraphTable(dict):
         return (_GraphTable, ())
 
 
+# OCOCC_OCC_LOSS_KERNEL=0: the sample masks of loss_occ's train_cfg variants as the ATen chain (occ_ops.occ_loss_masks_aten,
+# also what CPU tensors take) instead of csrc/occ_loss_masks.hip
+OCC_LOSS_KERNEL = os.environ.get('OCOCC_OCC_LOSS_KERNEL', '1') != '0'
 HOST_POSITIVE_COUNTS = True   # False: OccBBoxHead.loss reads its two positive counts back from the device (tests)
 
 
@@ -1153,15 +1156,32 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
     def loss_occ(self, rois, roi_features, ori_roi_feats, pos_batch_idx, pos_gt_bboxes, reg_mask,
                  nonempty_roi_mask, gt_smp_local_coords, gt_smp_occ_labels, gt_occ_label_scores,
                  transform_occ=False, roi_frame_inds=None, do_aug=False, num_pos=None):
-        """ococc_bbox_head.py:608-811 (default train_cfg switches of ococcnet.py: no residual /
-        contrastive / outside / observed-feature variants)."""
+        """ococc_bbox_head.py:608-811, with the four train_cfg variants of the reference:
+          contrastive_loss            + loss_contrastive_feats = mse(roi_features, ori_roi_feats.detach()) * contrastive_loss_weight
+          no_loss_for_outside         a sample outside its RoI's box (-size / 2 <= xyz <= size / 2, inclusive) has weight 0
+          no_loss_for_observed_feats  a sample the decoder already calls occupied from ori_roi_feats has weight 0
+          residual_loss               + num_unmatched and loss_rcnn_occ_residual: loss_occ_comp of decoder(fused - ori) over the
+                                      samples whose label differs from the ori class ('residual' in fused_mode, as upstream)
+        The masks and their counts are one launch (occ_ops.occ_loss_masks; the operator chain occ_loss_masks_aten on CPU
+        tensors and with OCOCC_OCC_LOSS_KERNEL=0); with no switch on neither is called and nothing differs from the
+        plain loss.  The ori decode runs once for both switches that need it, under no_grad through
+        decoder(features, points, RoI index), in the module's current mode as upstream: in train() the decoder's dropout
+        applies to it too.  loss_rcnn_occ_residual is not compacted to the unmatched samples (a read-back upstream): the
+        entry is the scalar that the mean over the reference's vector gives -- the masked sum over the device-side count
+        (the masked sum itself for reduction='sum') -- and 0 with a live graph when no sample is unmatched."""
         losses = {}
+        cfg = self.train_cfg
+        contrastive, residual = cfg.get('contrastive_loss', False), cfg.get('residual_loss', False)
+        outside, observed = cfg.get('no_loss_for_outside', False), cfg.get('no_loss_for_observed_feats', False)
         decoder = self.occ_ae_head.occ_decoder
         reg_mask[~nonempty_roi_mask] = 0
         pos_inds = reg_mask > 0
         num_occupied = (gt_smp_occ_labels == 1).sum().float()
         losses['num_occupied'] = num_occupied
         losses['num_free'] = gt_smp_occ_labels.numel() - num_occupied
+        if contrastive:   # over all RoIs, with or without a positive one (:636-639)
+            losses['loss_contrastive_feats'] = nn.functional.mse_loss(roi_features, ori_roi_feats.detach()) \
+                * cfg.get('contrastive_loss_weight', 1.0)
         pos_rows = _true_rows(pos_inds, num_pos)   # (``num_pos``: the caller has counted them; else one read-back)
         num_pos = pos_rows.numel()
         if pos_rows.numel() == 0:
@@ -1169,6 +1189,9 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
             losses['loss_rcnn_occ'] = decoder(roi_features, roi_features.new_zeros(roi_features.size(0), 3), idx) * 0
             for k in ('recall_neg', 'recall_pos', 'precision_neg', 'precision_pos'):
                 losses[k] = roi_features.new_ones(1)
+            if residual:   # (:652-659)
+                losses['loss_rcnn_occ_residual'] = decoder(roi_features, roi_features.new_zeros(roi_features.size(0), 3), idx) * 0
+                losses['num_unmatched'] = roi_features.new_zeros(1)
             return losses
         pos_roi_features = roi_features[pos_rows]  # [M, D]
         rb = rois[:, 0].int()
@@ -1183,11 +1206,28 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
             occ_smp_xyz[..., 2] = -occ_smp_xyz[..., 2]
         scores = self.filter_pos_assigned_but_empty_rois(gt_occ_label_scores, pos_batch_idx, pos_inds, rb)
         M, K, _ = occ_targets.shape
-        occ_weights = (scores > self.occ_label_thresh).to(scores.dtype).view(M, 1).repeat(1, K)
         # decoder with (features, points, RoI index): no [M,K,D] copies (reference :711,:740)
         idx = torch.arange(M, device=rois.device).repeat_interleave(K)
+        if outside or observed or residual:
+            assert not residual or 'residual' in self.fused_mode, f'{self.fused_mode}'
+            occ_labels = (occ_targets[..., -1] == 1).long()
+            pos_ori_feats = ori_roi_feats[pos_rows].detach() if (observed or residual) else None
+            occ_weights, unmatched, mask_counts = self._occ_loss_masks(
+                decoder, pos_ori_feats, occ_smp_xyz.reshape(M * K, 3), idx, rois[pos_rows][:, 4:7], scores, occ_labels,
+                outside, observed, residual)
+            occ_weights = occ_weights.view(M, K)
+        else:
+            occ_weights = (scores > self.occ_label_thresh).to(scores.dtype).view(M, 1).repeat(1, K)
         occ_preds = decoder(pos_roi_features, occ_smp_xyz.reshape(M * K, 3), idx)
         occ_labels = (occ_targets[..., -1] == 1).long()
+        if residual:   # (:741-775)
+            losses['num_unmatched'] = mask_counts[1].float()
+            residual_preds = decoder(pos_roi_features - pos_ori_feats, occ_smp_xyz.reshape(M * K, 3), idx)
+            masked = self.loss_occ_comp(residual_preds.view(-1), occ_labels.view(-1),
+                                        occ_weights.view(-1) * unmatched.to(occ_weights.dtype), reduction_override='none').sum()
+            if self.loss_occ_comp.reduction != 'sum':   # 'none' (the mean the trainer takes of the vector) and 'mean'
+                masked = masked / mask_counts[1].clamp(min=1).to(masked.dtype)
+            losses['loss_rcnn_occ_residual'] = masked
         losses['loss_rcnn_occ'] = self.loss_occ_comp(occ_preds.view(-1), occ_labels.view(-1), occ_weights.view(-1))
         with torch.no_grad():
             pred_cls = decoder.get_cls_from_pred(occ_preds.view(-1, 1)) if decoder.cls_dim == 1 \
@@ -1202,3 +1242,17 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
             ratios = c[num] / (c[den] + 1e-6)
             losses['recall_neg'], losses['recall_pos'], losses['precision_neg'], losses['precision_pos'] = ratios.unbind(0)
         return losses
+
+    def _occ_loss_masks(self, decoder, pos_ori_feats, xyz, idx, box_size, scores, occ_labels, outside, observed, unmatched):
+        """(weights [M * K] f32, unmatched [M * K] uint8 or None, counts [3] int64) of loss_occ's variants: the ori decode
+        (once, under no_grad, in the decoder's current mode) and the masks of occ_ops.occ_loss_masks / _aten."""
+        ori_logits = None
+        if observed or unmatched:
+            if decoder.cls_dim != 1:
+                raise NotImplementedError('no_loss_for_observed_feats / residual_loss take the one-logit decoder (cls_dim 1)')
+            with torch.no_grad():
+                ori_logits = decoder(pos_ori_feats, xyz, idx).float().view(-1)
+        masks = occ_ops.occ_loss_masks if (OCC_LOSS_KERNEL and xyz.is_cuda) else occ_ops.occ_loss_masks_aten
+        return masks(scores.reshape(-1).float(), self.occ_label_thresh, occ_labels.view(-1), xyz=xyz if outside else None,
+                     box_size=box_size if outside else None, ori_logits=ori_logits, pos_thresh=decoder.pos_thresh,
+                     outside=outside, observed=observed, unmatched=unmatched)

@@ -94,6 +94,80 @@ def occ_iou_count(logits, labels, counts, row0, pos_thresh, roi_xyz=None, half_s
     return counts
 
 
+def _loss_mask_shapes(L, what, xyz, box_size, score, labels, ori_logits, outside, observed, unmatched):
+    """(M, K) of the sample masks' inputs, or OcoccError: score [M] f32, labels [M * K] int64, and -- where a switch reads
+    them -- xyz [M * K, 3] f32, box_size [M, 3] f32, ori_logits [M * K] f32."""
+    if score is None or labels is None or score.dtype != torch.float32 or labels.dtype != torch.int64:
+        raise L.OcoccError(f'{what}: score is f32 [M] and labels int64 [M * K]')
+    M, N = score.numel(), labels.numel()
+    if (N % M if M else N) != 0:
+        raise L.OcoccError(f'{what}: {N} labels for {M} RoIs')
+    K = N // M if M else 0
+    if outside and (xyz is None or box_size is None or xyz.dtype != torch.float32 or box_size.dtype != torch.float32
+                    or xyz.numel() != N * 3 or box_size.numel() != M * 3 or xyz.size(-1) != 3 or box_size.size(-1) != 3):
+        raise L.OcoccError(f'{what}: no_loss_for_outside needs xyz f32 [{M} * {K}, 3] and box_size f32 [{M}, 3]')
+    if (observed or unmatched) and (ori_logits is None or ori_logits.dtype != torch.float32 or ori_logits.numel() != N):
+        raise L.OcoccError(f'{what}: the observed / unmatched masks need ori_logits f32 [{M} * {K}] of the one-logit decoder')
+    return M, K
+
+
+def occ_loss_masks(score, score_thresh, labels, xyz=None, box_size=None, ori_logits=None, pos_thresh=0.5, outside=False,
+                   observed=False, unmatched=False):
+    """The sample weights of OccBBoxHead.loss_occ under its train_cfg switches in one launch (csrc/occ_loss_masks.hip),
+    sample k of positive RoI i in row i * K + k:
+        weights [M * K] f32 = (score[i] > score_thresh)                                   (ococc_bbox_head.py:708-710)
+            * (-box_size[i] / 2 <= xyz <= box_size[i] / 2 on all axes)  with ``outside``   (:713-722; NaN is outside)
+            * (class of ori_logits == 0)                                  with ``observed``  (:723-734)
+        unmatched [M * K] uint8 = (labels == 1) != (class of ori_logits), with ``unmatched`` (:749-752), else None
+        counts [3] int64 on the device: #(weights > 0), #unmatched, #(unmatched and weights > 0)
+    class = sigmoid(logit) > pos_thresh, decided as ATen decides it (NaN: class 0).  Nothing is read back; two calls give
+    the same bits.  ``occ_loss_masks_aten`` is the same result as a torch operator chain."""
+    from .. import _lib as L
+    L.require_device(score, labels, xyz, box_size, ori_logits)
+    M, K = _loss_mask_shapes(L, 'occ_loss_masks', xyz, box_size, score, labels, ori_logits, outside, observed, unmatched)
+    dev = score.device
+    flags = (1 if outside else 0) | (2 if observed else 0) | (4 if unmatched else 0)
+    weights = L.empty((M * K,), torch.float32, dev)
+    um = L.empty((M * K,), torch.uint8, dev) if unmatched else None
+    counts = L.empty((3,), torch.int64, dev)
+    c = lambda t, on: t.contiguous() if (on and t is not None) else None
+    xyz, box_size = c(xyz, outside), c(box_size, outside)
+    ori_logits, lab = c(ori_logits, observed or unmatched), c(labels, unmatched)
+    L.check(L.lib.ococc_occ_loss_masks_f32(L.ptr(xyz), L.ptr(box_size), L.ptr(score.contiguous()), L.ptr(ori_logits), L.ptr(lab),
+                                           M, K, float(score_thresh), float(pos_thresh), flags, L.ptr(weights), L.ptr(um),
+                                           L.ptr(counts), L.stream()), 'occ_loss_masks')
+    return weights, um, counts
+
+
+def occ_loss_masks_aten(score, score_thresh, labels, xyz=None, box_size=None, ori_logits=None, pos_thresh=0.5,
+                        outside=False, observed=False, unmatched=False):
+    """``occ_loss_masks`` as the reference's operator chain (ococc_bbox_head.py:706-710, 713-722, 730-734, 749-753, 792),
+    on any device: what OccBBoxHead.loss_occ takes on CPU tensors or with OCOCC_OCC_LOSS_KERNEL=0, and the yardstick of the
+    kernel."""
+    from .. import _lib as L
+    M, K = _loss_mask_shapes(L, 'occ_loss_masks_aten', xyz, box_size, score, labels, ori_logits, outside, observed, unmatched)
+    score = score.reshape(-1)
+    occ_weights = torch.zeros_like(score)
+    occ_weights[score > score_thresh] = 1
+    occ_weights = occ_weights.view(M, 1).repeat(1, K)
+    if outside:
+        xyz, size = xyz.reshape(M, K, 3), box_size.reshape(M, 3)
+        inside = (xyz >= -size[:, None, :] / 2).all(dim=-1) & (xyz <= size[:, None, :] / 2).all(dim=-1)
+        occ_weights = occ_weights * inside.float()
+    if observed or unmatched:
+        ori_cls = (ori_logits.reshape(M, K).sigmoid() > pos_thresh).long()     # get_cls_from_pred, cls_dim 1
+    if observed:
+        occ_weights = occ_weights * (ori_cls == 0).float()
+    weights = occ_weights.view(-1)
+    valid = weights > 0
+    um = None
+    zero = valid.sum() * 0
+    if unmatched:
+        um = (labels.reshape(-1) == 1).long() != ori_cls.view(-1)
+    counts = torch.stack([valid.sum(), um.sum() if unmatched else zero, (um & valid).sum() if unmatched else zero])
+    return weights, um.to(torch.uint8) if unmatched else None, counts
+
+
 def dense_grid_layout(bbox_sizes, voxel_size, scale_wlh=[1.0, 1.0, 1.0], offset_wlh=[0.0, 0.0, 0.0]):
     """The grid of every box as the kernels of csrc/occ_export.hip take it: (enlarged sizes [R, 3] f32, dims [R, 3] i32,
     start [R + 1] i64 the exclusive prefix of the cells per box, total).  Built on the device with the expressions of

@@ -114,6 +114,10 @@ SIGNATURES = {
     'ococc_tracklet_crop_fill': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp,
                                          c_vp]),
     'ococc_tracklet_nonempty': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp]),
+    'ococc_scene_rows_workspace_bytes': (c_i64, [c_i64, c_i64]),
+    'ococc_scene_rows_count': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, ctypes.POINTER(c_f32), c_vp, c_vp, c_i64, c_vp]),
+    'ococc_scene_rows_fill': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, ctypes.POINTER(c_f32), c_i32, c_vp, c_i32, c_i64,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'ococc_track_extend_f64': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp,
                                        c_vp, c_i64, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp]),
     'ococc_frame_match_workspace_bytes': (c_i64, [c_i64]),

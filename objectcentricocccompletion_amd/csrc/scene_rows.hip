@@ -1,0 +1,257 @@
+// One sensor frame's scene cloud into the step rows of online inference (TrackletRoIHeadOCC.simple_test_scene_step): per
+// (enlarged) tracklet box the points inside it, in the cloud's order, moved into the box's own fixed frame, range-filtered,
+// capped and decorated -- what the offline chain makes of a frame with tools/ctrl/generate_track_input.py:84-99 (the crop),
+// LoadTrackletPoints (tracklet_pipelines.py:26-91: the cap), TrackletPoseTransform (tracklet_pipelines.py:228-303),
+// PointDecoration and PointsRangeFilter, each a pass of its own over the points.  Here: one count launch, one read-back of
+// counts [n], one fill launch that writes the ROWS (xyz, features, row index), not indices.
+//
+// The plan is that of tracklet_crop.hip: a workgroup of 4 waves takes 4096 consecutive points (and, by blockIdx.y, a span
+// of the boxes: the points of one frame alone would leave most CUs idle -- box_span), each wave 1024 consecutive ones ("wave tile": 16 rounds of 64, lane = point, kept in registers, every point read once per pass however many boxes
+// there are); the boxes are staged 64 at a time in LDS (centre, half sizes, cos / sin, the conservative BEV radius, and the
+// box's 3x4 matrix) and read as broadcasts.  Per box and round one ballot: its popcount is the count, the popcount below the
+// lane the rank -- (wave tile, round, lane) is ascending point order, so no sort.  The count pass leaves the per-(wave tile,
+// box) counts in the workspace [wave tiles, n] i32 (box-minor); the fill pass sums the earlier wave tiles in front of its
+// own ranks.
+//
+// Membership of point p in box b, the same in both passes:
+//   1. the box test of tracklet_crop_kernel on the UNTRANSFORMED point, restated below expression for expression (the two
+//      files are held to bit equality by tests/test_gpu_scene_rows.py): |z - (z_bottom + h/2)| <= h/2, the radius reject,
+//      (dx, dy) turned by rot = (float)((double)yaw + pi/2), strict inequalities in BEV.  A NaN x or y is in no box; a NaN z
+//      passes the height test as it does there (!(|dz| > h/2)) and is dropped by the range, when one is given.
+//   2. with a range: the WRITTEN xyz strictly inside (x0, y0, z0, x1, y1, z1) (PointsRangeFilter).
+// The written xyz: with transforms, row b's row-major 3x4 matrix m applied as x' = fmaf(z, m02, fmaf(y, m01, fmaf(x, m00,
+// m03))) (y', z' with rows 1, 2); the identity returns the input bits (a -0.0 comes out as +0.0); without, the input bits.
+//
+// Cap (fill only; counts stay uncapped): box b has m = scan_all[b+1] - scan_all[b] members; with cap > 0 and m > cap its
+// member j (cloud order) is kept iff (j+1)*cap/m > j*cap/m (int64 floor division) and goes to place j*cap/m of the box --
+// exactly cap rows, ascending, an even pick where LoadTrackletPoints draws a random subset.
+//
+// Algorithmic bytes per pass: N * 12 B of xyz per span of boxes (rows C * 4 B apart: N * C * 4 B of cache lines, 24 B at
+// C = 6; the spans after the first read them from L2), n * (28 + 48) B
+// of boxes and matrices per workgroup (L2); count: + T * n * 4 B workspace out, n * 8 B counts (integer atomics, the only
+// ones); fill: + about T/2 * n * 4 B workspace in per wave tile (L2), M * A * 4 B of attributes in (the lines of the xyz) and
+// M * (12 + (A + K) * 4 + 8) B of rows out.  T = ceil(N / 1024) wave tiles, M = scan_out[n].  Vector stores only.
+#include "common.hpp"
+
+namespace {
+
+constexpr int kRounds = 16;                 // points per lane
+constexpr int kWaveTile = 64 * kRounds;     // 1024 points per wave
+constexpr int kWaves = 4;
+constexpr int kBlockTile = kWaveTile * kWaves;
+constexpr int kChunk = 64;                  // boxes staged at a time: one per lane
+
+struct Range6 {
+  float v[6];
+};
+
+// XR: a transform or a range is given (without either, the test is tracklet_crop_kernel's alone and needs fewer registers)
+template <bool FILL, bool XR>
+__global__ void __launch_bounds__(64 * kWaves)
+scene_rows_kernel(const float* __restrict__ points, int64_t n, int32_t C, const float* __restrict__ boxes, int32_t nb,
+                  int32_t span, const float* __restrict__ transforms, Range6 range, int32_t has_range, int32_t* __restrict__ tile_counts,
+                  unsigned long long* __restrict__ counts, int32_t A, const float* __restrict__ row_feats, int32_t K,
+                  int64_t cap, const int64_t* __restrict__ scan_all, const int64_t* __restrict__ scan_out,
+                  float* __restrict__ out_xyz, float* __restrict__ out_feats, int64_t* __restrict__ out_row) {
+  __shared__ float sb[9][kChunk];    // cx, cy, cz, hl, hw, hh, cos, sin, r^2
+  __shared__ float sm[12][kChunk];   // the box's 3x4 matrix, row-major
+  const int64_t tile0 = (int64_t)blockIdx.x * kBlockTile;
+  if (tile0 >= n) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t w0 = tile0 + (int64_t)wave * kWaveTile;   // index of this wave's first point
+  const int64_t wt = (int64_t)blockIdx.x * kWaves + wave;  // wave tile
+  const bool xform = XR && transforms != nullptr;
+
+  float px[kRounds], py[kRounds], pz[kRounds];
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+    const int64_t i = w0 + r * 64 + lane;
+    if (i < n) {
+      const float* q = points + i * C;
+      px[r] = q[0], py[r] = q[1], pz[r] = q[2];
+    } else {
+      px[r] = 0.f, py[r] = 0.f, pz[r] = INFINITY;   // fails the height test of every box
+    }
+  }
+
+  // this workgroup's boxes: [blockIdx.y * span, b_end)
+  const int b_end = (int)min((int64_t)nb, ((int64_t)blockIdx.y + 1) * span);
+  for (int c0 = blockIdx.y * span; c0 < b_end; c0 += kChunk) {
+    const int cn = min(kChunk, b_end - c0);
+    __syncthreads();
+    if (tid < cn) {
+      // (tracklet_crop_kernel's staging, expression for expression)
+      const float* b = boxes + (int64_t)(c0 + tid) * 7;
+      const float hh = b[5] * 0.5f, hl = b[4] * 0.5f, hw = b[3] * 0.5f;
+      const float rot = (float)((double)b[6] + 1.5707963267948966);
+      sb[0][tid] = b[0], sb[1][tid] = b[1], sb[2][tid] = b[2] + hh;
+      sb[3][tid] = hl, sb[4][tid] = hw, sb[5][tid] = hh;
+      sb[6][tid] = cosf(rot), sb[7][tid] = sinf(rot);
+      sb[8][tid] = (hl * hl + hw * hw) * 1.001f + 1e-6f;   // |local|^2 < hl^2 + hw^2 inside; the slack covers rounding
+      if (xform) {
+        const float* m = transforms + (int64_t)(c0 + tid) * 12;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) sm[k][tid] = m[k];
+      }
+    }
+    __syncthreads();
+
+    // lane j: where box c0 + j's members of this wave tile start (in members of the box), the box's member count, its
+    // first output row and its output end
+    int64_t base = 0, total = 0, start = 0, end = 0;
+    if (FILL) {
+      if (lane < cn) {
+        const int64_t b = c0 + lane;
+        total = scan_all[b + 1] - scan_all[b];
+        start = scan_out[b], end = scan_out[b + 1];
+        for (int64_t k = 0; k < wt; ++k) base += tile_counts[k * nb + b];
+      }
+    }
+    int mine = 0;                // lane j: count of box c0 + j in this wave tile
+    for (int j = 0; j < cn; ++j) {
+      const float cx = sb[0][j], cy = sb[1][j], cz = sb[2][j], hl = sb[3][j], hw = sb[4][j], hh = sb[5][j];
+      const float ca = sb[6][j], sa = sb[7][j], r2 = sb[8][j];
+      const int64_t base_j = FILL ? __shfl(base, j, 64) : 0, total_j = FILL ? __shfl(total, j, 64) : 0;
+      const int64_t start_j = FILL ? __shfl(start, j, 64) : 0, end_j = FILL ? __shfl(end, j, 64) : 0;
+      const bool pick = FILL && cap > 0 && total_j > cap;   // wave-uniform
+      int cnt = 0;               // wave-uniform
+#pragma unroll
+      for (int r = 0; r < kRounds; ++r) {
+        // (tracklet_crop_kernel's test, expression for expression)
+        const float dx = px[r] - cx, dy = py[r] - cy;
+        bool in = !(fabsf(pz[r] - cz) > hh) && !(dx * dx + dy * dy > r2);
+        if (in) {
+          const float lx = dx * ca + dy * (-sa), ly = dx * sa + dy * ca;
+          in = (lx > -hl) & (lx < hl) & (ly > -hw) & (ly < hw);
+        }
+        float ox = px[r], oy = py[r], oz = pz[r];
+        if (XR && __ballot(in)) {   // wave-uniform: most (box, round) pairs have no point in the box
+          if (in && xform) {
+            ox = fmaf(pz[r], sm[2][j], fmaf(py[r], sm[1][j], fmaf(px[r], sm[0][j], sm[3][j])));
+            oy = fmaf(pz[r], sm[6][j], fmaf(py[r], sm[5][j], fmaf(px[r], sm[4][j], sm[7][j])));
+            oz = fmaf(pz[r], sm[10][j], fmaf(py[r], sm[9][j], fmaf(px[r], sm[8][j], sm[11][j])));
+          }
+          if (in && has_range)
+            in = (ox > range.v[0]) & (oy > range.v[1]) & (oz > range.v[2]) & (ox < range.v[3]) & (oy < range.v[4]) &
+                 (oz < range.v[5]);
+        }
+        const unsigned long long bal = __ballot(in);
+        if (FILL && in) {
+          const int64_t jm = base_j + cnt + __popcll(bal & ((1ull << lane) - 1ull));   // member index in the box
+          int64_t pos = jm;
+          bool keep = jm < total_j;            // (counts and scans of the same input: always)
+          if (pick) {
+            pos = jm * cap / total_j;
+            keep = keep && (jm + 1) * cap / total_j > pos;
+          }
+          pos += start_j;
+          if (keep && pos < end_j) {           // (pos < end_j: scan_out of the same counts and cap)
+            const int64_t i = w0 + r * 64 + lane;
+            float* o = out_xyz + pos * 3;
+            o[0] = ox, o[1] = oy, o[2] = oz;
+            out_row[pos] = c0 + j;
+            float* f = out_feats + pos * (A + K);
+            const float* q = points + i * C + 3;
+            for (int a = 0; a < A; ++a) f[a] = q[a];
+            const float* rf = row_feats + (int64_t)(c0 + j) * K;
+            for (int k = 0; k < K; ++k) f[A + k] = rf[k];
+          }
+        }
+        cnt += __popcll(bal);
+      }
+      if (lane == j) mine = cnt;
+    }
+    if (!FILL && lane < cn) {
+      const int64_t b = c0 + lane;
+      tile_counts[wt * nb + b] = mine;   // zeros too: the fill pass reads every earlier wave tile
+      if (mine) atomicAdd(&counts[b], (unsigned long long)mine);
+    }
+  }
+}
+
+// 1: nothing to do (an empty cloud or no boxes), 0: launch, < 0: reported
+int rows_check(const float* points, int64_t n, int32_t c, const float* boxes, int64_t b, const void* workspace,
+               int64_t workspace_bytes, const char* fn) {
+  if (n < 0 || b < 0) return ococc_fail(OCOCC_EINVAL, fn, "negative size");
+  if (n > 2147483647LL || b > 2147483647LL) return ococc_fail(OCOCC_EINVAL, fn, "at most 2^31 - 1 points and boxes");
+  if (c < 3) return ococc_fail(OCOCC_EINVAL, fn, "points need at least 3 columns");
+  if (b == 0 || n == 0) return 1;
+  if (!points || !boxes || !workspace) return ococc_fail(OCOCC_EINVAL, fn, "null pointer");
+  if (workspace_bytes < ococc_scene_rows_workspace_bytes(n, b))
+    return ococc_fail(OCOCC_EINVAL, fn, "workspace too small: ococc_scene_rows_workspace_bytes(num_points, num_boxes)");
+  return OCOCC_OK;
+}
+
+// Boxes per workgroup (blockIdx.y takes `span` consecutive boxes).  One sensor frame is few workgroups along the points
+// (37 at 150 000 points), so the boxes are split until about two workgroups per CU are in flight, 8 boxes at the least;
+// every split re-reads the cloud (L2), which is small beside the box tests it spreads.
+int32_t box_span(int64_t n, int64_t b) {
+  const int64_t tiles = ococc_cdiv(n, kBlockTile);
+  int64_t parts = ococc_cdiv(512, tiles);
+  if (parts > ococc_cdiv(b, 8)) parts = ococc_cdiv(b, 8);
+  if (parts > 65535) parts = 65535;
+  return (int32_t)ococc_cdiv(b, parts < 1 ? 1 : parts);
+}
+
+Range6 range_arg(const float* range) {
+  Range6 r = {{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}};
+  if (range) memcpy(r.v, range, sizeof(r.v));
+  return r;
+}
+
+}  // namespace
+
+extern "C" int64_t ococc_scene_rows_workspace_bytes(int64_t num_points, int64_t num_boxes) {
+  if (num_points < 0 || num_boxes < 0) return -1;
+  return ococc_cdiv(num_points, kBlockTile) * kWaves * num_boxes * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int ococc_scene_rows_count(const float* points, int64_t num_points, int32_t point_dim,
+                                      const float* crop_boxes, int64_t num_boxes, const float* transforms,
+                                      const float* range, int64_t* counts, void* workspace, int64_t workspace_bytes,
+                                      ococc_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const int rc = rows_check(points, num_points, point_dim, crop_boxes, num_boxes, workspace, workspace_bytes, __func__);
+  if (rc < 0) return rc;
+  if (num_boxes > 0) {
+    OCOCC_REQUIRE(counts, "null counts");
+    OCOCC_HIP(hipMemsetAsync(counts, 0, num_boxes * sizeof(int64_t), stream));
+  }
+  if (rc == 1) return OCOCC_OK;
+  const auto kernel = (transforms || range) ? scene_rows_kernel<false, true> : scene_rows_kernel<false, false>;
+  const int32_t span = box_span(num_points, num_boxes);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)ococc_cdiv(num_points, kBlockTile), (unsigned)ococc_cdiv(num_boxes, span)),
+                     dim3(64 * kWaves), 0, stream, points, num_points, point_dim, crop_boxes, (int32_t)num_boxes, span,
+                     transforms, range_arg(range), (int32_t)(range != nullptr), (int32_t*)workspace,
+                     (unsigned long long*)counts, 0,
+                     (const float*)nullptr, 0, (int64_t)0, (const int64_t*)nullptr, (const int64_t*)nullptr,
+                     (float*)nullptr, (float*)nullptr, (int64_t*)nullptr);
+  OCOCC_CHECK_LAUNCH();
+  return OCOCC_OK;
+}
+
+extern "C" int ococc_scene_rows_fill(const float* points, int64_t num_points, int32_t point_dim, const float* crop_boxes,
+                                     int64_t num_boxes, const float* transforms, const float* range, int32_t attr_dims,
+                                     const float* row_feats, int32_t row_feat_dim, int64_t max_points,
+                                     const int64_t* scan_all, const int64_t* scan_out, float* out_xyz, float* out_feats,
+                                     int64_t* out_row, const void* workspace, int64_t workspace_bytes,
+                                     ococc_stream_t stream_) {
+  const int rc = rows_check(points, num_points, point_dim, crop_boxes, num_boxes, workspace, workspace_bytes, __func__);
+  if (rc < 0) return rc;
+  OCOCC_REQUIRE(attr_dims >= 0 && row_feat_dim >= 0 && 3 + (int64_t)attr_dims <= point_dim,
+                "attr_dims and row_feat_dim are >= 0, and 3 + attr_dims <= point_dim");
+  OCOCC_REQUIRE(max_points <= 2147483647LL, "max_points is at most 2^31 - 1 (<= 0: no cap)");
+  if (rc == 1) return OCOCC_OK;
+  OCOCC_REQUIRE(scan_all && scan_out && out_xyz && out_row, "null scan_all, scan_out, out_xyz or out_row");
+  OCOCC_REQUIRE(row_feat_dim == 0 || row_feats, "null row_feats");
+  OCOCC_REQUIRE(attr_dims + row_feat_dim == 0 || out_feats, "null out_feats");
+  const auto kernel = (transforms || range) ? scene_rows_kernel<true, true> : scene_rows_kernel<true, false>;
+  const int32_t span = box_span(num_points, num_boxes);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)ococc_cdiv(num_points, kBlockTile), (unsigned)ococc_cdiv(num_boxes, span)),
+                     dim3(64 * kWaves), 0, (hipStream_t)stream_, points, num_points, point_dim, crop_boxes,
+                     (int32_t)num_boxes, span, transforms, range_arg(range), (int32_t)(range != nullptr),
+                     (int32_t*)const_cast<void*>(workspace), (unsigned long long*)nullptr, attr_dims, row_feats, row_feat_dim, max_points, scan_all, scan_out,
+                     out_xyz, out_feats, out_row);
+  OCOCC_CHECK_LAUNCH();
+  return OCOCC_OK;
+}

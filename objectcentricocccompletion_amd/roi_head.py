@@ -65,10 +65,13 @@ def check_save_gt_occ_cfg(test_cfg):
 class OnlineState(object):
     """What frame-by-frame inference keeps between steps (TrackletRoIHeadOCC.online_begin): ``cache``, the TemporalCache of
     the temporal transformer, and ``frames``, the steps taken per slot (a list of ints on the host: the cache's own
-    ``pos_host``, since a slot's frame index is the number of frames it has cached)."""
+    ``pos_host``, since a slot's frame index is the number of frames it has cached).  ``origin``: per slot the inverse of
+    the ego pose at the slot's first step (world -> the slot's fixed frame, a float64 4x4 array on the host), kept by
+    simple_test_scene_step, None for a slot that is free or was stepped through simple_test_step."""
 
     def __init__(self, cache):
         self.cache = cache
+        self.origin = [None] * cache.slots
 
     @property
     def frames(self):
@@ -80,6 +83,8 @@ class OnlineState(object):
 
     def reset(self, slots=None):
         self.cache.reset(slots)
+        for s in (range(self.cache.slots) if slots is None else [int(s) for s in slots]):
+            self.origin[s] = None
 
 
 @HEADS.register_module()
@@ -487,6 +492,91 @@ class TrackletRoIHeadOCC(nn.Module):
             cfg=self.test_cfg)[0]
         return dict(boxes=out_boxes, scores=out_scores, labels=out_labels, valid=valid,
                     fused_roi_feats=res['fused_roi_feats'], ori_roi_feats=res['ori_roi_feats'])
+
+    # PointsRangeFilter's range in the ococcnet pipelines (ococcnet_cfg.py) and LoadTrackletPoints' max_points there
+    SCENE_ROWS_DEFAULTS = dict(extra_width=1.0, max_points=1024, attr_dims=2,
+                               point_cloud_range=(-204.7, -204.7, -3.99, 204.7, 204.7, 7.99))
+
+    @staticmethod
+    def _boxes_through(boxes, m12):
+        """boxes [n, 7] through the per-row 3x4 matrices m12 [n, 12] (float64, on the boxes' device) with the arithmetic
+        of Tracklet.frame_transform: the centre through the matrix, the yaw by atan2 of the transformed heading vector
+        (sin, cos, 0), the sizes kept; batched over the rows as Tracklet.shared2ego, in float64, rounded once."""
+        m = m12.view(-1, 3, 4)
+        b = boxes[:, :7].double()
+        centre = (m[:, :, :3] * b[:, None, :3]).sum(-1) + m[:, :, 3]
+        hv = torch.stack([torch.sin(b[:, 6]), torch.cos(b[:, 6])], 1)
+        t = (m[:, :2, :2] * hv[:, None, :]).sum(-1)
+        return torch.cat([centre, b[:, 3:6], torch.atan2(t[:, 0], t[:, 1])[:, None]], 1).to(boxes.dtype)
+
+    @torch.no_grad()
+    def simple_test_scene_step(self, points, pose, boxes, scores, labels, slot, state, gt_rois=None):
+        """simple_test_step from what a sensor frame brings: ``points`` [N, >= 3 + attr] f32, the scene cloud of the frame in
+        its own ego frame; ``pose``, the 4x4 ego -> world of the frame (numpy or torch); ``boxes`` [n, 7], ``scores`` [n],
+        ``labels`` [n], the tracker's output for the frame in the same ego frame; ``slot`` and ``state`` as in
+        simple_test_step.  Nothing has to be cropped, transformed, decorated or filtered beforehand.
+
+        The fixed frame simple_test_step asks for is, per slot, the ego frame of the slot's FIRST step: the state keeps
+        ``origin[slot]`` = inverse(pose) of that step (set when the slot's frame counter is 0, cleared by
+        ``state.reset``).  Row i gets M_i = float32(origin[slot_i] @ pose); all pose arithmetic is float64 on the host and
+        the matrices of a call go up in one copy.  scene_rows.scene_step_rows crops the cloud into the enlarged boxes, moves
+        the points through M_i, decorates, filters and caps them (test_cfg.scene_rows: extra_width 1.0, max_points 1024,
+        attr_dims 2, point_cloud_range that of the config's PointsRangeFilter); the boxes go through M_i as
+        Tracklet.frame_transform moves them; then simple_test_step runs on the rows, unchanged.  ``gt_rois``, if given, is
+        in the slots' fixed frames.
+
+        Returns the dict of simple_test_step (boxes in the slots' fixed frames) and two more keys: ``boxes_ego`` [n, 7], the
+        refined boxes back in the frame's ego frame through inverse(M_i), rows with valid == False their input box bit for
+        bit; ``num_points`` [n] i64 on the host, the points in each enlarged box before the cap.
+
+        Reported on the host before anything is launched: what simple_test_step reports, a pose that is not 4x4 or not
+        finite (OcoccError), a slot in mid-tracklet without an origin -- it was stepped through simple_test_step
+        (OcoccError)."""
+        import numpy as np
+        from . import _lib as L
+        from .scene_rows import scene_step_rows
+        from .tracklet import host_index
+        if self.training:
+            raise RuntimeError('simple_test_scene_step is inference only: call .eval() first')
+        pose64 = np.asarray(pose.detach().cpu().numpy() if torch.is_tensor(pose) else pose, dtype=np.float64)
+        if pose64.shape != (4, 4) or not np.isfinite(pose64).all():
+            raise L.OcoccError(f'pose must be a finite 4x4 ego -> world matrix, got shape {pose64.shape}')
+        slots = state.cache.check_step(slot)
+        first = None                                                    # inverse(pose), if a slot starts here
+        origins = []
+        for s in slots:
+            if state.frames[s] == 0:
+                if first is None:
+                    try:
+                        first = np.linalg.inv(pose64)
+                    except np.linalg.LinAlgError:
+                        raise L.OcoccError('pose is singular: not an ego -> world transform')
+                origins.append(first)
+            elif state.origin[s] is None:
+                raise L.OcoccError(f'slot {s} holds {state.frames[s]} frames and no origin: it was stepped through '
+                                   'simple_test_step, whose caller keeps the fixed frame (reset the slot)')
+            else:
+                origins.append(state.origin[s])
+        L.require_device(points, boxes, scores, labels, state.cache.pos)
+        n, dev = boxes.size(0), boxes.device
+        if len(slots) != n or scores.size(0) != n or labels.size(0) != n:
+            raise L.OcoccError(f'{len(slots)} slots, {scores.size(0)} scores, {labels.size(0)} labels for {n} boxes')
+        cfg = dict(self.SCENE_ROWS_DEFAULTS, **(self.test_cfg.get('scene_rows', None) or {}))
+        for s in slots:
+            if state.frames[s] == 0:
+                state.origin[s] = first
+        to_fixed = np.stack([o @ pose64 for o in origins]) if n else np.zeros((0, 4, 4))
+        mats = host_index(np.stack([to_fixed[:, :3].reshape(n, 12), np.linalg.inv(to_fixed)[:, :3].reshape(n, 12)]), dev,
+                          dtype=torch.float64)                         # [2, n, 12]: M and inverse(M), one copy
+        fixed_boxes = self._boxes_through(boxes, mats[0])
+        xyz, feats, row, counts = scene_step_rows(
+            points, boxes, scores, transforms=mats[0].float(), extra_width=cfg['extra_width'], attr_dims=cfg['attr_dims'],
+            point_cloud_range=cfg['point_cloud_range'], max_points=cfg['max_points'], deco_boxes=fixed_boxes)
+        out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois)
+        out['boxes_ego'] = torch.where(out['valid'].to(dev).bool()[:, None], self._boxes_through(out['boxes'], mats[1]),
+                                       boxes[:, :7])
+        out['num_points'] = counts
+        return out
 
     def online_chunk(self):
         """test_cfg.online_chunk: the frames simple_test_online feeds per call, an int >= 1 (default 1: single steps)"""

@@ -1,0 +1,104 @@
+"""The first stage of online inference from sensor frames: one scene cloud, in the ego frame it was taken in, and the
+tracker's boxes of that frame -> the step rows TrackletRoIHeadOCC.simple_test_step takes (csrc/scene_rows.hip).
+
+Offline, the same rows come out of a chain of passes: the crop into the enlarged boxes
+(tools/ctrl/generate_track_input.py:84-99, csrc/tracklet_crop.hip), the per-tracklet .npy files and their cap of 1024
+points per frame (LoadTrackletPoints), the move into the tracklet's fixed frame (TrackletPoseTransform), the decoration
+with yaw / 3.1415, size / 10 and score (PointDecoration), the range filter (PointsRangeFilter) and the row index.  Here a
+frame is one count launch, one read-back of the counts and one fill launch that writes the rows.
+
+Two deviations from the offline chain, both because a step must be reproducible: where LoadTrackletPoints draws a random
+subset of max_points points, the kernel takes an even pick in the cloud's order (point j of m is kept iff
+(j+1)*cap//m > j*cap//m), and there is no PointShuffle (the rows keep the cloud's order)."""
+import torch
+
+from . import _lib as L
+from .ctrl_prep import enlarged_boxes
+
+EXTRA_WIDTH = 1.0            # box.extra_width of tools/ctrl/data_configs/*.yaml: the margin generate_track_input crops with
+ROW_FEAT_DIM = 5             # yaw / 3.1415, w / 10, l / 10, h / 10, score
+
+
+def even_pick(m, cap):
+    """The cap's rule on the host: [(j, place)] of the members of a box of m points that survive a cap of ``cap`` rows, in
+    Python ints -- what ococc_scene_rows_fill computes in int64."""
+    if cap <= 0 or m <= cap:
+        return [(j, j) for j in range(m)]
+    return [(j, j * cap // m) for j in range(m) if (j + 1) * cap // m > j * cap // m]
+
+
+def decoration(boxes, scores):
+    """PointDecoration's yaw, size and score columns of n boxes as one [n, 5] f32 tensor, with its own expressions: the yaw
+    divided in double precision (``float(box[6]) / 3.1415``), the sizes in f32 (``boxes[:, 3:6] / 10``), the score as it
+    is.  The divisors are tensors: ATen turns a division by a host scalar into a multiplication by its reciprocal."""
+    dev = boxes.device
+    yaw = (boxes[:, 6].double() / L.const_tensor([3.1415], dev, torch.float64)).float()
+    size = boxes[:, 3:6].float() / L.const_tensor([10.0], dev)
+    return torch.cat([yaw[:, None], size, scores.float().reshape(-1, 1)], 1)
+
+
+def scene_step_rows(points, boxes, scores, transforms=None, extra_width=EXTRA_WIDTH, attr_dims=2, point_cloud_range=None,
+                    max_points=-1, deco_boxes=None):
+    """points [N, >= 3 + attr_dims] f32: the scene cloud of one sensor frame; boxes [n, 7] f32 (x, y, z_bottom, w, l, h,
+    yaw): the proposals in the cloud's frame, scores [n].  Row b takes the points inside ``enlarged_boxes(boxes,
+    extra_width)[b]`` (a point may be in several rows), in the cloud's order.
+
+    transforms [n, 12] f32 (or [n, 3, 4]): per row the row-major 3x4 matrix its points go through (f32 fused
+    multiply-adds); None leaves them.  With transforms the decoration is taken from ``deco_boxes`` [n, 7], the boxes in
+    the TARGET frame (default: ``boxes``, for a caller that passes none or has them there already).
+    point_cloud_range (x0, y0, z0, x1, y1, z1): only points whose written xyz lies strictly inside are rows.
+    max_points = cap > 0: at most cap rows per box, an even pick in the cloud's order (even_pick).
+
+    Returns (xyz [M, 3] f32, feats [M, attr_dims + 5] f32 = the point's columns 3 : 3 + attr_dims, then yaw / 3.1415,
+    size / 10, score of its row, row [M] i64, counts [n] i64 on the HOST: the members per box BEFORE the cap).  Rows are
+    sorted by (row, point index).  One count launch, one read-back, one fill launch."""
+    L.require_device(points, boxes, scores, transforms, deco_boxes)
+    if points.dim() != 2 or points.dtype != torch.float32 or points.size(1) < 3 + int(attr_dims) or attr_dims < 0:
+        raise L.OcoccError(f'points must be [N, >= 3 + attr_dims = {3 + int(attr_dims)}] float32, got {tuple(points.shape)} '
+                           f'{points.dtype}')
+    if boxes.dim() != 2 or boxes.size(1) < 7:
+        raise L.OcoccError(f'boxes must be [n, 7], got {tuple(boxes.shape)}')
+    n, N, dev = boxes.size(0), points.size(0), points.device
+    if scores.numel() != n or (deco_boxes is not None and tuple(deco_boxes.shape[:1]) != (n,)):
+        raise L.OcoccError(f'{scores.numel()} scores (and deco_boxes) for {n} boxes')
+    if transforms is not None:
+        if transforms.numel() != n * 12 or transforms.dtype != torch.float32:
+            raise L.OcoccError(f'transforms must be [n, 12] float32, got {tuple(transforms.shape)} {transforms.dtype}')
+        transforms = transforms.reshape(n, 12).contiguous()
+    rng = None
+    if point_cloud_range is not None:
+        if len(point_cloud_range) != 6:
+            raise L.OcoccError('point_cloud_range is (x0, y0, z0, x1, y1, z1)')
+        rng = L.f6(point_cloud_range)
+    cap = int(max_points)
+    if cap > 2 ** 31 - 1:
+        raise L.OcoccError('max_points is at most 2**31 - 1')
+    points = points.contiguous()
+    boxes = boxes[:, :7].contiguous().float()
+    crop = enlarged_boxes(boxes, extra_width)
+    row_feats = decoration(boxes if deco_boxes is None else deco_boxes[:, :7].float(), scores).contiguous()
+    A, K = int(attr_dims), row_feats.size(1)
+    counts = torch.zeros((n,), dtype=torch.int64, device=dev)
+    empty = lambda: (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, A + K), dtype=torch.float32, device=dev),
+                     torch.zeros((0,), dtype=torch.int64, device=dev), counts.cpu())
+    if n == 0 or N == 0:
+        return empty()
+    ws_bytes = int(L.lib.ococc_scene_rows_workspace_bytes(N, n))
+    ws = L.workspace(ws_bytes, dev)
+    L.check(L.lib.ococc_scene_rows_count(L.ptr(points), N, points.size(1), L.ptr(crop), n, L.ptr(transforms), rng,
+                                         L.ptr(counts), L.ptr(ws), ws_bytes, L.stream()), 'scene_rows_count')
+    counts_host = counts.cpu()                                   # the read-back
+    scans = torch.zeros((2, n + 1), dtype=torch.int64)
+    torch.cumsum(counts_host, 0, out=scans[0, 1:])
+    torch.cumsum(counts_host.clamp(max=cap) if cap > 0 else counts_host, 0, out=scans[1, 1:])
+    M = int(scans[1, -1])
+    if M == 0:
+        return empty()
+    scans_dev = scans.to(dev)                                    # (one upload for both)
+    xyz = L.empty((M, 3), torch.float32, dev)
+    feats = L.empty((M, A + K), torch.float32, dev)
+    row = L.empty((M,), torch.int64, dev)
+    L.check(L.lib.ococc_scene_rows_fill(L.ptr(points), N, points.size(1), L.ptr(crop), n, L.ptr(transforms), rng, A,
+                                        L.ptr(row_feats), K, cap, L.ptr(scans_dev[0]), L.ptr(scans_dev[1]), L.ptr(xyz),
+                                        L.ptr(feats), L.ptr(row), L.ptr(ws), ws_bytes, L.stream()), 'scene_rows_fill')
+    return xyz, feats, row, counts_host

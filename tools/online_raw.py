@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""Online inference replayed from RAW data: the tracker's result (.bin) and the scene clouds of a track-input yaml
+(tools/ctrl/data_configs/*.yaml: bin_path, mm_data_root with idx2timestamp.pkl / idx2contextname.pkl and the velodyne
+clouds) stepped through frame by frame, the way the method is deployed -- no track-input database, no per-tracklet files:
+
+    python tools/online_raw.py <config> <checkpoint> <raw.yaml> [--slots 64] [--out FILE.bin] [--poses poses.pkl]
+                               [--cfg-options k=v ...]
+
+Per segment and frame, in time order: the frame's scene cloud is loaded once, every track that starts at the frame gets a
+free slot of the temporal K/V cache, TrackletRoIHeadOCC.simple_test_scene_step refines all live tracks in one call (crop,
+pose transform, decoration, range filter and cap on the device: csrc/scene_rows.hip), and a track's slot is released after
+its last frame.  More live tracks than slots is an error that names --slots.  The cache is chosen from the longest track as
+simple_test_online chooses it: plain up to 256 frames, a ring with test_cfg.attn_window_size, else a long cache.
+
+The refined objects (``boxes_ego``: each in its own frame's ego frame) are written as a Waymo metrics file; an object whose
+enlarged box held no point keeps the tracker's box and score, as do objects of types the yaml's ``type`` list leaves out.
+Config and checkpoint are loaded as tools/test.py loads them."""
+import argparse
+import os
+
+os.environ.setdefault('DEBUG_CLR_GRAPH_PACKET_CAPTURE', '0')  # before the HIP runtime loads: objectcentricocccompletion_amd/graph.py
+import pickle
+import sys
+from collections import defaultdict
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+WAYMO_TYPE_TO_LABEL = {1: 0, 2: 1, 4: 2}     # vehicle, pedestrian, cyclist -> index into ('Car', 'Pedestrian', 'Cyclist')
+
+
+def choose_cache(roi_head, longest):
+    """the cache keywords of online_begin for tracks of up to ``longest`` frames, as simple_test_online picks them"""
+    from objectcentricocccompletion_amd import _lib as L
+    from objectcentricocccompletion_amd.occ.layers import TemporalCache
+    window = roi_head.test_cfg.get('attn_window_size', -1)
+    if longest <= 256:
+        return dict(cap=max(longest, 1))
+    if window > 0:
+        return dict(cap=window, ring=True)
+    if longest <= TemporalCache.MAX_LONG_CAP:
+        return dict(cap=longest, long=True)
+    raise L.OcoccError(f'a track of {longest} frames without test_cfg.attn_window_size: the K/V cache of online inference '
+                       f'holds at most {TemporalCache.MAX_LONG_CAP} frames of history')
+
+
+def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None):
+    """``model``: a TrackletDetectorOCC in eval mode on a ROCm device; ``raw_yaml``: the track-input yaml (path or mapping,
+    ctrl_prep.load_config); ``poses``: {timestamp: 4x4 ego -> world} or the path of its pickle (default: the yaml's
+    ``poses_path``, else <mm_data_root>/poses.pkl).  Returns (records, state): one record per object of the tracker's
+    file, tracks in order of first appearance and frames ascending -- dict(segment, id, type, timestamp, box [7] f32 in the
+    frame's ego frame, score, num_points: the points in the enlarged box before the cap, refined: whether the head's
+    result was taken) -- and the OnlineState, every slot released.  With ``out`` the records are written there as a Waymo
+    metrics file."""
+    import numpy as np
+    import torch
+    from objectcentricocccompletion_amd import _lib as L
+    from objectcentricocccompletion_amd import ctrl_prep, waymo_io
+    cfg, _ = ctrl_prep.load_config(raw_yaml)
+    rh = model.roi_head
+    dev = torch.device(device) if device is not None else next(model.parameters()).device
+    tracklets = waymo_io.generate_tracklets(waymo_io.read_bin(ctrl_prep.bin_path_for_split(cfg)))
+    refine_types = set(cfg.get('type') or (1, 2, 4))
+    mm_root = cfg.get('mm_data_root', ctrl_prep.MM_DATA_ROOT)
+    ts2idx, _ = ctrl_prep.load_frame_index(mm_root)
+    pc_root = ctrl_prep.velodyne_dir(cfg)
+    if poses is None or isinstance(poses, (str, os.PathLike)):
+        with open(poses or cfg.get('poses_path') or os.path.join(mm_root, 'poses.pkl'), 'rb') as f:
+            poses = pickle.load(f)
+    live = [k for k, t in enumerate(tracklets) if t.type in refine_types and len(t)]
+    state = rh.online_begin(int(slots), dev, **choose_cache(rh, max((len(tracklets[k]) for k in live), default=1)))
+    boxes_out = [t.boxes[:, :7].clone() for t in tracklets]
+    scores_out = [t.scores.clone().float() for t in tracklets]
+    num_points = [[0] * len(t) for t in tracklets]
+    refined = [[False] * len(t) for t in tracklets]
+    by_seg = defaultdict(list)
+    for k in live:
+        by_seg[tracklets[k].segment_name].append(k)
+    for seg, ks in by_seg.items():
+        at = defaultdict(list)                       # timestamp -> [(tracklet, position in the tracklet)]
+        for k in ks:
+            for i, ts in enumerate(tracklets[k].ts_list):
+                at[ts].append((k, i))
+        missing = [ts for ts in at if ts not in ts2idx or ts not in poses]
+        if missing:
+            raise KeyError(f'{len(missing)} timestamps of segment {seg} have no frame in idx2timestamp.pkl or no pose '
+                           f'(e.g. {sorted(missing)[0]})')
+        free, slot_of = list(range(state.slots))[::-1], {}
+        for ts in sorted(at):
+            rows = at[ts]
+            for k, i in rows:
+                if i == 0:
+                    if not free:
+                        raise L.OcoccError(f'segment {seg} has more than {state.slots} live tracks at timestamp {ts}: '
+                                           'raise --slots')
+                    slot_of[k] = free.pop()
+            cloud = np.fromfile(os.path.join(pc_root, f'{ts2idx[ts]}.bin'), dtype=np.float32).reshape(-1, 6)
+            boxes = torch.stack([tracklets[k].boxes[i, :7].float() for k, i in rows]).to(dev)
+            scores = torch.stack([tracklets[k].scores[i].float() for k, i in rows]).to(dev)
+            labels = torch.tensor([WAYMO_TYPE_TO_LABEL[tracklets[k].type] for k, _ in rows], dtype=torch.long).to(dev)
+            res = rh.simple_test_scene_step(torch.from_numpy(cloud).to(dev), np.asarray(poses[ts], dtype=np.float64), boxes,
+                                            scores, labels, [slot_of[k] for k, _ in rows], state)
+            valid = res['valid'].to(dev).bool()
+            back = torch.cat([res['boxes_ego'], torch.where(valid, res['scores'].float(), scores)[:, None],
+                              valid[:, None].float()], 1).cpu()           # one read-back per frame
+            done = []
+            for r, (k, i) in enumerate(rows):
+                boxes_out[k][i], scores_out[k][i] = back[r, :7], back[r, 7]
+                refined[k][i], num_points[k][i] = bool(back[r, 8]), int(res['num_points'][r])
+                if i == len(tracklets[k]) - 1:
+                    done.append(slot_of.pop(k))
+            if done:
+                state.reset(done)
+                free.extend(done)
+    records, chunks = [], []
+    for k, t in enumerate(tracklets):
+        b, s = boxes_out[k].numpy(), scores_out[k].numpy()
+        for i, ts in enumerate(t.ts_list):
+            records.append(dict(segment=t.segment_name, id=t.id, type=t.type, timestamp=ts, box=b[i], score=float(s[i]),
+                                num_points=num_points[k][i], refined=refined[k][i]))
+            if out:
+                chunks.append(waymo_io._f_bytes(1, waymo_io.lidar2waymo_box(b[i], s[i], t.type, t.segment_name, ts, t.id)))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'wb') as f:
+            f.write(b''.join(chunks))
+    return records, state
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('config', help='model config file path (tools/test.py)')
+    ap.add_argument('checkpoint', help='checkpoint file (tools/train.py: a dict with state_dict)')
+    ap.add_argument('raw_yaml', help='track-input yaml: bin_path, mm_data_root, split, type')
+    ap.add_argument('--slots', type=int, default=64, help='tracks followed at the same time (9.4 MB of K/V cache each at 256 frames)')
+    ap.add_argument('--out', default=None, help='the refined objects as a Waymo metrics file (default: <bin stem>_online.bin)')
+    ap.add_argument('--poses', default=None, help='poses.pkl: {timestamp: 4x4 ego -> world} (default: the yaml\'s poses_path, '
+                    'else <mm_data_root>/poses.pkl)')
+    ap.add_argument('--cfg-options', nargs='+', default=[], help='k=v overrides merged into the config')
+    args = ap.parse_args(argv)
+    if args.slots < 1:
+        ap.error('--slots takes a number of tracks >= 1')
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import importlib.util
+
+    import torch
+    from objectcentricocccompletion_amd import config, ctrl_prep, heads, point_pool, roi_head  # noqa: F401 (registers)
+    from objectcentricocccompletion_amd.registry import DETECTORS
+    spec = importlib.util.spec_from_file_location('ococc_tools_test', os.path.join(ROOT, 'tools', 'test.py'))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    cfg = config.fromfile(args.config)
+    config.merge_from_dict(cfg, tool.parse_kv(args.cfg_options))
+    dev = torch.device('cuda', torch.cuda.current_device())
+    model = DETECTORS.build(cfg['model']).to(dev)
+    ck = torch.load(args.checkpoint, map_location=dev)
+    model.load_state_dict(ck['state_dict'] if 'state_dict' in ck else ck)
+    model.eval()
+    raw, _ = ctrl_prep.load_config(args.raw_yaml)
+    out = args.out or os.path.splitext(ctrl_prep.bin_path_for_split(raw))[0] + '_online.bin'
+    records, _ = replay(model, args.raw_yaml, slots=args.slots, out=out, poses=args.poses, device=dev)
+    print(f'{len(records)} objects, {sum(r["refined"] for r in records)} refined; wrote {out}')
+    return out
+
+
+if __name__ == '__main__':
+    main()

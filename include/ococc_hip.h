@@ -795,6 +795,47 @@ int ococc_occ_select_fill(const float* logits, int64_t n, const int64_t* start, 
                           int32_t cols, float* out, int64_t n_out, ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * completed occupancy of one online step (csrc/occ_frame.hip): the cells the decoder predicts occupied joined with the
+ * cells the sensor hit in this frame, behind occ_ops.occ_frame_select, OccDecoder.get_frame_occ and the ``occ=True``
+ * results of TrackletRoIHeadOCC.simple_test_step / simple_test_steps / simple_test_scene_step.  The flat cell list
+ * (sizes, dims, start), its tiles of 1024 cells of one RoI and ococc_occ_select_max_tiles are those of the export above.
+ *
+ * ococc_occ_frame_mark replaces the rasterisation of OccAutoEncoder.sample_observation
+ *   (mmdet3d/models/roi_heads/bbox_heads/occ_ae_head.py:65-126 with quantize_points, mmdet3d/ops/occ/occ_ops.py:53-93):
+ *   local_xyz [M, 3] f32 the pooled points in the box frame (after the compensate_encoder_coors turn), pts_roi [M] i32
+ *   the RoI of each.  Per axis floor((p - (-size / 2)) / voxel_size) in f32, each operation rounded on its own, the
+ *   quotient a true division; a point whose index is < 0 or >= dim on any axis, whose coordinate is NaN or whose RoI
+ *   is outside [0, R) marks nothing.  observed [n] u8 (n = start[R]) is zeroed here, then 1 where a point fell into
+ *   the cell: byte stores of one value, no atomic.  M == 0: the memset only.
+ *
+ * ococc_occ_frame_count / ococc_occ_frame_fill replace the sigmoid / compare / boolean index / transform of get_occ
+ *   (mmdet3d/models/occ/occ_base.py:238-342) for the union of prediction and observation.  A cell is selected when
+ *   (1 / (1 + exp(-logit)) > pos_thresh or observed[cell] != 0) and row_keep[RoI] != 0; observed NULL: no observation;
+ *   row_keep [R] u8 NULL: every RoI kept (test_cfg.filter_empty_roi without a host decision).
+ *   count writes tile_start [R + 1] i64, tile_counts [max_tiles] i32 and roi_counts [R] i64 (zeroed here) as
+ *   ococc_occ_select_count does.  fill, given tile_scan [max_tiles] i64 the exclusive prefix of tile_counts, writes per
+ *   selected cell, in cell order, out [n_out, 4] f32 (16-byte aligned, one 16-byte store per row) and flags [n_out] u8:
+ *     columns 0-2 the cell centre in the LiDAR frame by the arithmetic of ococc_occ_select_fill with to_lidar (rois rows
+ *     of roi_stride >= 7 floats, cos_yaw / sin_yaw [R] the caller's), then with transforms [R, 12] f32 (row-major 3x4,
+ *     NULL: none) x' = ((t0 x + t1 y) + t2 z) + t3 and likewise y', z', each operation rounded once;
+ *     column 3 the sigmoid of the logit; flags bit 0 predicted, bit 1 observed.
+ *   With transforms NULL and nothing observed the xyz columns are those of ococc_occ_select_fill bit for bit.
+ * Integer atomics only; the same input gives the same bytes.  R == 0 or n == 0 is an empty result, not an error.
+ * ------------------------------------------------------------------------ */
+int ococc_occ_frame_mark(const float* local_xyz, const int32_t* pts_roi, int64_t M, const float* sizes,
+                         const int32_t* dims, const int64_t* start, int32_t R, float voxel_size, uint8_t* observed,
+                         int64_t n, ococc_stream_t stream);
+int ococc_occ_frame_count(const float* logits, const uint8_t* observed, const uint8_t* row_keep, int64_t n,
+                          const int64_t* start, int32_t R, float pos_thresh, int64_t* tile_start, int32_t* tile_counts,
+                          int64_t max_tiles, int64_t* roi_counts, ococc_stream_t stream);
+int ococc_occ_frame_fill(const float* logits, const uint8_t* observed, const uint8_t* row_keep, int64_t n,
+                         const int64_t* start, const int64_t* tile_start, int32_t R, float pos_thresh,
+                         const int64_t* tile_scan, int64_t max_tiles, const float* sizes, const int32_t* dims,
+                         float voxel_size, const float* rois, int64_t roi_stride, const float* cos_yaw,
+                         const float* sin_yaw, const float* transforms, float* out, uint8_t* flags, int64_t n_out,
+                         ococc_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * ground-truth occupancy export (csrc/gt_occ_crop.hip): the occupied label cells of one object, moved into the LiDAR
  * frame of every frame that has a GT box and cropped to that frame's proposal box, behind bbox.crop_gt_occ_packed and
  * TrackletRoIHeadOCC.save_gt_occ_from_tracklet.  Replaces the save_gt_occ=True branch of save_occ_from_tracklet

@@ -4,7 +4,7 @@
 thread_local char ococc_err_buf[512] = {0};
 
 extern "C" const char* ococc_last_error(void) { return ococc_err_buf; }
-extern "C" int ococc_version(void) { return 106; /* 106: ococc_temporal_attention_chunk_f32 (csrc/causal_attn_step.hip) added */ }
+extern "C" int ococc_version(void) { return 107; /* 107: ococc_occ_frame_mark / _count / _fill (csrc/occ_frame.hip) added */ }
 extern "C" const char* ococc_arch(void) { return "gfx950"; }
 
 extern "C" int ococc_timer_create(void** timer) {

@@ -25,6 +25,7 @@
 // No float atomics; integer counts: the same input gives the same bytes.  Vector stores only.
 #include "common.hpp"
 #include "occ_math.hpp"
+#include "occ_tiles.hpp"   // roi_of, cell_centre, tile_table_kernel: shared with occ_frame.hip
 
 // every float product and sum below is rounded on its own, as the ATen chain rounds them: hipcc's default contracts
 // a * b + c into a fused multiply-add (also through __fmul_rn / __fadd_rn, whose bodies sit in front of this pragma)
@@ -37,29 +38,6 @@ constexpr int kTile = kOccCompactTile;   // 1024 cells per wave
 constexpr int kWaves = kOccCompactWaves;
 constexpr int kBlock = 64 * kWaves;
 constexpr int kLdsStart = 2048;       // entries of start kept in LDS by the cells kernel
-
-// the largest r in [0, R) with table[r] <= i, for an ascending table [R + 1] with table[0] <= i: the RoI of cell i (of
-// tile i); RoIs without cells (equal neighbours) are stepped over.  Reads entries 1 .. R - 1 only.
-__device__ __forceinline__ int roi_of(const int64_t* table, int R, int64_t i) {
-  int lo = 0, hi = R;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (table[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-struct Cell { float x, y, z; };
-
-// box-frame centre of cell `local` of an RoI with grid (., dy, dz): x slowest, z fastest
-__device__ __forceinline__ Cell cell_centre(uint32_t local, const float* __restrict__ size,
-                                            const int32_t* __restrict__ dim, float voxel_size) {
-  const uint32_t dy = (uint32_t)max(dim[1], 1), dz = (uint32_t)max(dim[2], 1);
-  const uint32_t ix = local / (dy * dz), rem = local - ix * (dy * dz);
-  const uint32_t iy = rem / dz, iz = rem - iy * dz;
-  return {ococc_cell_centre((int)ix, size[0], voxel_size), ococc_cell_centre((int)iy, size[1], voxel_size),
-          ococc_cell_centre((int)iz, size[2], voxel_size)};
-}
 
 template <bool LDS>
 __global__ void __launch_bounds__(kBlock)
@@ -78,28 +56,6 @@ dense_grid_cells_kernel(const float* __restrict__ sizes, const int32_t* __restri
     float* o = centers + (i - lo) * 3;
     o[0] = c.x, o[1] = c.y, o[2] = c.z;
     roi_index[i - lo] = r;
-  }
-}
-
-// tile_start [R + 1]: exclusive prefix of ceil((start[r + 1] - start[r]) / 1024).  One wave, 64 RoIs per step.
-__global__ void __launch_bounds__(64)
-tile_table_kernel(const int64_t* __restrict__ start, int R, int64_t* __restrict__ tile_start) {
-  const int lane = threadIdx.x;
-  int64_t carry = 0;
-  if (lane == 0) tile_start[0] = 0;
-  for (int base = 0; base < R; base += 64) {
-    const int r = base + lane;
-    int64_t v = 0;
-    if (r < R) {
-      const int64_t k = start[r + 1] - start[r];
-      v = k > 0 ? (k + kTile - 1) / kTile : 0;
-    }
-    for (int d = 1; d < 64; d <<= 1) {
-      const int64_t u = __shfl_up(v, d, 64);
-      if (lane >= d) v += u;
-    }
-    if (r < R) tile_start[r + 1] = carry + v;
-    carry += __shfl(v, 63, 64);
   }
 }
 

@@ -556,6 +556,18 @@ class OccAutoEncoder(nn.Module, SparseHeadMixin):
         return self.occ_decoder.get_occ_packed(local_roi_feats, rois, self.voxel_size, self.scale_wlh, self.offset_wlh,
                                                transform=transform, roi_values=roi_values)
 
+    def get_frame_occ(self, local_roi_feats, rois, local_xyz, pts_roi_inds, row_keep=None, transforms=None, observed=True,
+                      chunk=1 << 20):
+        """The completed occupancy of one online step (OccDecoder.get_frame_occ): the occupied cells of get_occ_packed
+        joined with the cells sample_observation labels 1 for ``local_xyz`` -- the rotated coordinates ``encode``
+        returns --, as (out [n, 4], flags [n] uint8, counts per RoI)."""
+        if not self.compensate_encoder_coors:   # (sample_observation's turn: encode left the coordinates as pooled)
+            r = const_tensor((np.pi / 2,), local_xyz.device, local_xyz.dtype)
+            local_xyz = rotation_3d_in_axis(local_xyz[None, :, :], r, axis=2).squeeze(0)
+        return self.occ_decoder.get_frame_occ(local_roi_feats, rois, self.voxel_size, self.scale_wlh, self.offset_wlh,
+                                              local_xyz, pts_roi_inds, row_keep=row_keep, transforms=transforms,
+                                              observed=observed, chunk=chunk)
+
     def get_roi_occ(self, local_roi_feats, rois, transform=True, return_score=False):
         """occ_ae_head.py:440-449."""
         return self.occ_decoder.get_roi_occ(local_roi_feats, rois, self.voxel_size, self.scale_wlh,
@@ -756,7 +768,7 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
         return self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask, tune)
 
     @torch.no_grad()
-    def forward_step(self, pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds, slot, cache):
+    def forward_step(self, pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds, slot, cache, return_points=False):
         """``forward`` for ONE new frame of each of n tracklets that arrive frame by frame: rois [n, 8] (column 0 the row's
         own index), roi_frame_inds [n] the frame number of each (= the frames its slot has been stepped through), ``slot``
         the list of the rows' cache slots, ``cache`` the TemporalCache of ``trans_enc`` (occ/layers.py).  Every stage but
@@ -764,7 +776,9 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
         the cached ones (TransformerEncoder.step), which under the causal mask of ``get_future_mask`` -- windowed by
         test_cfg.attn_window_size as there -- is row t of the full pass over frames 0..t.  Returns the dict of ``forward``
         for the n new RoIs.  test_cfg.allow_attn_future makes the model non-causal: ValueError; test_cfg.online_tuning
-        (test-time tuning of the latent) is not built for single steps: NotImplementedError."""
+        (test-time tuning of the latent) is not built for single steps: NotImplementedError.  ``return_points`` adds two
+        keys, ``local_xyz`` [M, 3] and ``roi_inds`` [M]: the pooled points in their boxes' frames as the occupancy
+        auto-encoder saw them, the input of get_frame_occ."""
         if self.training:
             raise RuntimeError('OccBBoxHead.forward_step is inference only: call .eval() first')
         if self.test_cfg.get('allow_attn_future', False):
@@ -772,20 +786,24 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
                              'frame by frame')
         if self.test_cfg.get('online_tuning', False):
             raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference')
-        final_cluster_feats, nonempty_roi_mask, local_roi_feats, _ = self._encode_rois(pts_xyz, pts_features, pts_info,
-                                                                                       roi_inds, rois)
+        final_cluster_feats, nonempty_roi_mask, local_roi_feats, local_xyz = self._encode_rois(
+            pts_xyz, pts_features, pts_info, roi_inds, rois)
         pos_embed = self._pos_embed(roi_frame_inds, rois[:, 1:])
         roi_feats_fused = self.trans_enc.step(final_cluster_feats, pos_embed, slot, cache,
                                               self.test_cfg.get('attn_window_size', -1))
-        return self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
+        ret = self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
+        if return_points:   # (what get_frame_occ rasterises: the auto-encoder's box-frame points and their rows)
+            ret.update(local_xyz=local_xyz, roi_inds=roi_inds)
+        return ret
 
     @torch.no_grad()
-    def forward_steps(self, pts_xyz, pts_features, pts_info, roi_inds, rois, slot_rows, cache):
+    def forward_steps(self, pts_xyz, pts_features, pts_info, roi_inds, rois, slot_rows, cache, return_points=False):
         """``forward_step`` for one OR MORE new frames per tracklet in one call: ``slot_rows`` is the slot of every row
         and may repeat -- the rows of a slot are its new frames, consecutive and in frame order (TemporalCache.check_steps)
         -- and the frame index of row j of the run of slot s is cache.pos_host[s] + j.  The temporal transformer runs
         TransformerEncoder.steps (one attention launch per layer for all rows); everything else works per RoI.  The
-        refusals are those of ``forward_step``.  Returns the dict of ``forward`` for the n rows, in input order."""
+        refusals are those of ``forward_step``, and so is ``return_points``.  Returns the dict of ``forward`` for the n rows,
+        in input order."""
         from .tracklet import host_index
         if self.training:
             raise RuntimeError('OccBBoxHead.forward_steps is inference only: call .eval() first')
@@ -796,12 +814,15 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
             raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference')
         slots, offsets, _ = cache.check_steps(slot_rows)
         roi_frame_inds = host_index([cache.pos_host[s] + j for s, j in zip(slots, offsets)], rois.device)
-        final_cluster_feats, nonempty_roi_mask, local_roi_feats, _ = self._encode_rois(pts_xyz, pts_features, pts_info,
-                                                                                       roi_inds, rois)
+        final_cluster_feats, nonempty_roi_mask, local_roi_feats, local_xyz = self._encode_rois(
+            pts_xyz, pts_features, pts_info, roi_inds, rois)
         pos_embed = self._pos_embed(roi_frame_inds, rois[:, 1:])
         roi_feats_fused = self.trans_enc.steps(final_cluster_feats, pos_embed, slots, cache,
                                                self.test_cfg.get('attn_window_size', -1))
-        return self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
+        ret = self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
+        if return_points:
+            ret.update(local_xyz=local_xyz, roi_inds=roi_inds)
+        return ret
 
     # ------------------------------------------------------------------ temporal transformer
     def get_occ(self, local_roi_feats, rois, transform=True, ori_roi_feats=None):
@@ -816,6 +837,14 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
     def get_occ_packed(self, local_roi_feats, rois, transform=True, roi_values=None):
         """get_occ of the fused features as one array and the rows per RoI (OccDecoder.get_occ_packed)."""
         return self.occ_ae_head.get_occ_packed(local_roi_feats, rois, transform=transform, roi_values=roi_values)
+
+    def get_frame_occ(self, local_roi_feats, rois, local_xyz, pts_roi_inds, row_keep=None, transforms=None, observed=True,
+                      chunk=1 << 20):
+        """The completed occupancy of one online step from the fused features and the step's pooled points
+        (OccAutoEncoder.get_frame_occ): ``local_xyz`` and ``pts_roi_inds`` as forward_step(..., return_points=True)
+        hands them out."""
+        return self.occ_ae_head.get_frame_occ(local_roi_feats, rois, local_xyz, pts_roi_inds, row_keep=row_keep,
+                                              transforms=transforms, observed=observed, chunk=chunk)
 
     def transformer_forward(self, rois, roi_frame_inds, roi_feats, nonempty_roi_mask, trans_enc=None):
         if not self.training or self.train_cfg.get('fixed_length', True):

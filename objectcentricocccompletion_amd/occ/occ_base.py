@@ -28,6 +28,9 @@ FUSED_WHOLE_MLP = True   # ... and in ONE launch when the widths are the referen
 FUSED_TRAIN_MLP = os.environ.get('OCOCC_FUSED_TRAIN_MLP', '1') == '1'   # ... and the bf16 TRAINING forward on that launch too (fused_mlp.occ_mlp_train)
 # get_occ_packed on the kernels of csrc/occ_export.hip (0: the ATen chain of get_occ, also taken by two-logit decoders)
 OCC_EXPORT_KERNEL = os.environ.get('OCOCC_OCC_EXPORT_KERNEL', '1') != '0'
+# get_frame_occ on the kernels of csrc/occ_frame.hip (0: the operator chain occ_ops.occ_frame_select_aten, also taken by
+# two-logit decoders and CPU tensors)
+OCC_FRAME_KERNEL = os.environ.get('OCOCC_OCC_FRAME_KERNEL', '1') != '0'
 FUSED_MLP = True   # bf16 inference of OccDecoder on the per-layer kernels of occ/fused_mlp.py (False: library GEMMs + LN kernels)
 
 
@@ -354,6 +357,41 @@ class OccDecoder(nn.Module):
         logits = (torch.cat(out, 0) if len(out) > 1 else out[0]) if out else rois.new_zeros((0, 1))
         return occ_ops.occ_select(logits, sizes, dims, start, total, voxel_size, self.pos_thresh,
                                   rois if transform else None, roi_values)
+
+    def get_frame_occ(self, roi_feats, rois, voxel_size, scale_wlh, offset_wlh, local_xyz, pts_roi_inds, row_keep=None,
+                      transforms=None, observed=True, chunk=1 << 20):
+        """The completed occupancy of one online step as ONE array: (out [n, 4] f32 -- x, y, z in the LiDAR frame of
+        ``rois`` [R, 8 or 10], through ``transforms`` [R, 12] when given, and the cell's probability --, flags [n] uint8
+        with bit 0 for a predicted and bit 1 for an observed cell, counts per RoI as a list of int), RoI after RoI in
+        cell order.  A cell is kept when the decode of ``roi_feats`` finds it occupied or (``observed``) one of the pooled
+        points ``local_xyz`` [M, 3] of ``pts_roi_inds`` [M] fell into it -- the cells sample_observation labels 1 --, and
+        the ``row_keep`` byte of its RoI (None: all) is non-zero.  Layout and chunked decode are those of get_occ_packed;
+        then occ_ops.occ_frame_select (csrc/occ_frame.hip): two read-backs (the number of cells, the counts).  Two-logit
+        decoders and OCOCC_OCC_FRAME_KERNEL=0 take occ_ops.occ_frame_select_aten behind the same decode (the decode itself
+        has no CPU form: CPU tensors are refused by the cells kernel's wrapper)."""
+        from .. import _lib as L
+        R = rois.size(0)
+        assert roi_feats.size(0) == R, f'{roi_feats.size(0)}, {R}'
+        assert R == 0 or rois.size(1) in (8, 10)
+        if R == 0:
+            return rois.new_zeros((0, 4)), torch.zeros((0,), dtype=torch.uint8, device=rois.device), []
+        kernel = OCC_FRAME_KERNEL and self.cls_dim == 1 and roi_feats.is_cuda
+        if not kernel:
+            L.log_once(('occ-frame', OCC_FRAME_KERNEL, self.cls_dim, roi_feats.is_cuda),
+                       'OccDecoder.get_frame_occ: the kernels of csrc/occ_frame.hip take the one-logit decoder on a ROCm '
+                       'device%s; running the operator chain occ_ops.occ_frame_select_aten'
+                       % ('' if OCC_FRAME_KERNEL else ' and OCOCC_OCC_FRAME_KERNEL=0 turns them off'))
+        rois = rois.float().contiguous()
+        sizes, dims, start, total = occ_ops.dense_grid_layout(rois[:, 4:7], voxel_size, scale_wlh, offset_wlh)
+        out = []
+        with torch.no_grad():
+            for lo in range(0, total, chunk):
+                centers, index = occ_ops.dense_grid_cells(sizes, dims, start, voxel_size, lo, min(lo + chunk, total), total)
+                out.append(self.forward(roi_feats, centers, index))
+        logits = (torch.cat(out, 0) if len(out) > 1 else out[0]) if out else rois.new_zeros((0, self.cls_dim))
+        select = occ_ops.occ_frame_select if kernel else occ_ops.occ_frame_select_aten
+        return select(logits, sizes, dims, start, total, voxel_size, self.pos_thresh, rois, local_xyz.float(), pts_roi_inds,
+                      scale_wlh, offset_wlh, row_keep=row_keep, transforms=transforms, observed=observed)
 
     def _get_occ_packed_aten(self, roi_feats, rois, voxel_size, scale_wlh, offset_wlh, transform, roi_values):
         sizes = rois[:, 4:7]

@@ -255,3 +255,127 @@ def occ_select(logits, sizes, dims, start, total, voxel_size, pos_thresh, rois=N
                                         L.ptr(cos), L.ptr(sin), L.ptr(roi_values), cols, L.ptr(out), n_occ, L.stream()),
             'occ_select_fill')
     return out, counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# completed occupancy of one online step (csrc/occ_frame.hip)
+def _frame_select_shapes(L, what, logits, sizes, dims, start, total, rois, local_xyz, pts_roi, row_keep, transforms,
+                         two_logits):
+    """(R, M) of the inputs of occ_frame_select / occ_frame_select_aten, or OcoccError."""
+    R = _check_layout(L, what, sizes, dims, start)
+    wide = (1, 2) if two_logits else (1,)
+    if logits.dtype != torch.float32 or logits.dim() > 2 or (logits.dim() == 2 and logits.size(1) not in wide):
+        raise L.OcoccError(f'{what}: logits {tuple(logits.shape)} {logits.dtype} are not f32 [N] or [N, 1]'
+                           + (' (or [N, 2] of the two-logit decoder)' if two_logits else ''))
+    n = logits.size(0) if logits.dim() == 2 else logits.numel()
+    if n != int(total):
+        raise L.OcoccError(f'{what}: {n} logits for a layout of {int(total)} cells')
+    if rois is None or rois.dtype != torch.float32 or rois.dim() != 2 or rois.size(0) != R or rois.size(1) < 8:
+        raise L.OcoccError(f'{what}: rois are f32 [{R}, >= 8] (batch, x, y, z, w, l, h, yaw): the pose of every grid')
+    if local_xyz is None or pts_roi is None or local_xyz.dtype != torch.float32 or local_xyz.dim() != 2 \
+            or local_xyz.size(1) != 3 or pts_roi.dtype not in (torch.int32, torch.int64) \
+            or tuple(pts_roi.shape) != (local_xyz.size(0),):
+        raise L.OcoccError(f'{what}: local_xyz is f32 [M, 3] and pts_roi int32 (or int64) [M]')
+    if row_keep is not None and (row_keep.dtype not in (torch.uint8, torch.bool) or tuple(row_keep.shape) != (R,)):
+        raise L.OcoccError(f'{what}: row_keep is uint8 (or bool) [{R}]')
+    if transforms is not None and (transforms.dtype != torch.float32 or transforms.numel() != R * 12
+                                   or transforms.size(0) != R):
+        raise L.OcoccError(f'{what}: transforms are f32 [{R}, 12] (or [{R}, 3, 4]), row-major 3x4')
+    return R, local_xyz.size(0)
+
+
+def occ_frame_select(logits, sizes, dims, start, total, voxel_size, pos_thresh, rois, local_xyz, pts_roi,
+                     scale_wlh=[1.0, 1.0, 1.0], offset_wlh=[0.0, 0.0, 0.0], row_keep=None, transforms=None, observed=True):
+    """The completed occupancy of one step from the flat cell list of dense_grid_layout (``sizes`` are its enlarged
+    sizes: rois[:, 4:7] * scale_wlh + offset_wlh): every cell that is predicted occupied (sigmoid(logit) > pos_thresh,
+    as ATen decides it) or -- with ``observed`` -- holds one of the pooled points ``local_xyz`` [M, 3] (box frame, the
+    coordinates OccAutoEncoder.sample_observation quantises; ``pts_roi`` [M] their RoI), of every RoI whose ``row_keep``
+    byte is non-zero (None: all).  Returns (out [N, 4] f32: x, y, z in the LiDAR frame of ``rois`` [R, >= 8] -- through
+    ``transforms`` [R, 12], row-major 3x4, when given -- and sigmoid(logit); flags [N] uint8, bit 0 predicted, bit 1
+    observed; counts per RoI as a list of int), rows in cell order, RoI after RoI.  One memset and one mark launch, one
+    count launch, one scan, one fill launch (csrc/occ_frame.hip); the one read-back is the per-RoI counts.
+    ``occ_frame_select_aten`` is the same result as a torch operator chain."""
+    from .. import _lib as L
+    R, M = _frame_select_shapes(L, 'occ_frame_select', logits, sizes, dims, start, total, rois, local_xyz, pts_roi,
+                                row_keep, transforms, two_logits=False)
+    L.require_device(logits, sizes, dims, start, rois, local_xyz, pts_roi, row_keep, transforms)
+    dev = logits.device
+    n = int(total)
+    if R == 0:
+        return L.empty((0, 4), torch.float32, dev), L.empty((0,), torch.uint8, dev), []
+    logits, sizes, dims, start = logits.contiguous(), sizes.contiguous(), dims.contiguous(), start.contiguous()
+    rois = rois.contiguous()
+    seen = None
+    if observed:
+        seen = L.empty((n,), torch.uint8, dev)
+        L.check(L.lib.ococc_occ_frame_mark(L.ptr(local_xyz.contiguous()), L.ptr(pts_roi.to(torch.int32).contiguous()), M,
+                                           L.ptr(sizes), L.ptr(dims), L.ptr(start), R, float(voxel_size), L.ptr(seen), n,
+                                           L.stream()), 'occ_frame_mark')
+    if row_keep is not None:
+        row_keep = row_keep.contiguous().view(torch.uint8) if row_keep.dtype == torch.bool else row_keep.contiguous()
+    tiles = int(L.lib.ococc_occ_select_max_tiles(n, R))
+    tile_start = L.empty((R + 1,), torch.int64, dev)
+    tile_counts = L.empty((tiles,), torch.int32, dev)
+    roi_counts = L.empty((R,), torch.int64, dev)
+    L.check(L.lib.ococc_occ_frame_count(L.ptr(logits), L.ptr(seen), L.ptr(row_keep), n, L.ptr(start), R, float(pos_thresh),
+                                        L.ptr(tile_start), L.ptr(tile_counts), tiles, L.ptr(roi_counts), L.stream()),
+            'occ_frame_count')
+    scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts  # exclusive: where a tile's cells start
+    cos, sin = torch.cos(rois[:, 7]).contiguous(), torch.sin(rois[:, 7]).contiguous()
+    if transforms is not None:
+        transforms = transforms.contiguous()
+    counts = [int(v) for v in roi_counts.tolist()]                      # the one read-back
+    n_out = sum(counts)
+    out = L.empty((n_out, 4), torch.float32, dev)
+    flags = L.empty((n_out,), torch.uint8, dev)
+    L.check(L.lib.ococc_occ_frame_fill(L.ptr(logits), L.ptr(seen), L.ptr(row_keep), n, L.ptr(start), L.ptr(tile_start), R,
+                                       float(pos_thresh), L.ptr(scan), tiles, L.ptr(sizes), L.ptr(dims), float(voxel_size),
+                                       L.ptr(rois), rois.size(1), L.ptr(cos), L.ptr(sin), L.ptr(transforms), L.ptr(out),
+                                       L.ptr(flags), n_out, L.stream()), 'occ_frame_fill')
+    return out, flags, counts
+
+
+def occ_frame_select_aten(logits, sizes, dims, start, total, voxel_size, pos_thresh, rois, local_xyz, pts_roi,
+                          scale_wlh=[1.0, 1.0, 1.0], offset_wlh=[0.0, 0.0, 0.0], row_keep=None, transforms=None,
+                          observed=True):
+    """``occ_frame_select`` as an operator chain on any device: the rasterisation of OccAutoEncoder.sample_observation
+    (quantize_points' expression with a true division on every device, flat cell ids, one scatter), OccDecoder._occupied,
+    a boolean index, OccDecoder._to_lidar and a batched matrix product.  What CPU tensors, two-logit decoders (logits [N, 2]) and OCOCC_OCC_FRAME_KERNEL=0 take, and
+    what the kernels are timed against.  ``sizes``, ``dims`` and ``start`` are checked and ``start`` is used; the cell
+    centres come from dense_voxel_centers_batched of the same rois, scale_wlh and offset_wlh."""
+    from .. import _lib as L
+    from .occ_base import OccDecoder
+    R, M = _frame_select_shapes(L, 'occ_frame_select_aten', logits, sizes, dims, start, total, rois, local_xyz, pts_roi,
+                                row_keep, transforms, two_logits=True)
+    dev = logits.device
+    if R == 0:
+        return logits.new_zeros((0, 4)), torch.zeros((0,), dtype=torch.uint8, device=dev), []
+    centers, box, _ = dense_voxel_centers_batched(rois[:, 4:7], voxel_size, scale_wlh, offset_wlh)
+    if logits.dim() == 2 and logits.size(1) == 2:
+        pred, prob = logits[:, 1] > logits[:, 0], logits.softmax(-1)[:, 1]
+    else:
+        prob = logits.sigmoid().view(-1)
+        pred = prob > pos_thresh
+    seen = torch.zeros(int(total), dtype=torch.bool, device=dev)
+    if observed and M:
+        idx = pts_roi.long()
+        # quantize_points' expression with the voxel as a TENSOR divisor: on a device ATen divides by a host scalar through
+        # its reciprocal, which moves a point that sits on a cell face (2.0 / 0.2f is 10, 2.0 * (1 / 0.2f) is 9.9999998);
+        # tensor / tensor is a true division everywhere, as on the host and in the mark kernel
+        size = rois[:, 4:7] * const_tensor(scale_wlh, dev).view(1, 3) + const_tensor(offset_wlh, dev).view(1, 3)
+        coors = torch.floor((local_xyz - (-size / 2)[idx]) / const_tensor((voxel_size,), dev)).to(torch.long)
+        d = dims.long()[idx]
+        valid = ((coors < d) & (coors >= 0)).all(dim=1)
+        flat = start[idx] + (coors[:, 0] * d[:, 1] + coors[:, 1]) * d[:, 2] + coors[:, 2]
+        seen[flat[valid]] = True
+    sel = pred | seen
+    if row_keep is not None:
+        sel = sel & (row_keep != 0)[box]
+    pbox = box[sel]
+    pts = OccDecoder._to_lidar(centers[sel], pbox, rois[:, 1:4], rois[:, 4:7], rois[:, 7])
+    if transforms is not None:
+        m = transforms.reshape(R, 3, 4)[pbox]
+        pts = torch.bmm(m[:, :, :3], pts[:, :, None]).squeeze(2) + m[:, :, 3]
+    out = torch.cat([pts, prob[sel].view(-1, 1)], 1)
+    flags = pred[sel].to(torch.uint8) | (seen[sel].to(torch.uint8) << 1)
+    return out, flags, torch.bincount(pbox, minlength=R).tolist()

@@ -417,7 +417,8 @@ class TrackletRoIHeadOCC(nn.Module):
                                          ring=ring, long=long))
 
     @torch.no_grad()
-    def simple_test_step(self, pts_xyz, pts_feats, pts_batch_idx, boxes, scores, labels, slot, state, gt_rois=None):
+    def simple_test_step(self, pts_xyz, pts_feats, pts_batch_idx, boxes, scores, labels, slot, state, gt_rois=None,
+                         occ=False, occ_transforms=None):
         """One new frame of n tracklets: the frame's points (pts_batch_idx: the ROW 0..n-1 a point belongs to), the
         proposal boxes [n, 7], scores [n] and labels [n] of this frame, ``slot`` the list of the rows' slots in ``state``
         (online_begin).  Pools the frame's points into the frame's boxes, appends the RoI score / corner offsets as
@@ -425,6 +426,15 @@ class TrackletRoIHeadOCC(nn.Module):
         decodes with get_bboxes_from_tracklet.  The frame index of a row is the number of steps its slot has taken, which is
         what tracklets2rois gives offline.  Returns dict(boxes [n, 7], scores [n], labels [n], valid [n] -- RoIs without
         points are flagged, the caller keeps their proposal --, fused_roi_feats [n, D], ori_roi_feats [n, D]).
+
+        ``occ=True`` adds the completed occupancy of the frame (``_step_occ``; csrc/occ_frame.hip): ``occ`` [N, 4] f32, the
+        centres of the cells that the fused latent decodes as occupied or that one of the frame's points fell into, in the
+        frame the inputs came in (through ``occ_transforms`` [n, 12] f32, a row-major 3x4 matrix per row, when given), and
+        the cell's probability; ``occ_flags`` [N] uint8, bit 0 predicted and bit 1 observed; ``occ_counts``, the rows per
+        input row as a list of int on the host.  Rows in input order, cells in grid order; the grid is that of the row's
+        INPUT box, which the latent is relative to (as save_occ_from_tracklet takes the proposal RoIs).
+        test_cfg.filter_empty_roi empties the rows whose box held no point; test_cfg.online_occ = dict(observed=True,
+        chunk=1 << 20) turns the observed cells off or sets the decode's chunk.  Without ``occ`` nothing of this is launched.
 
         ALL frames of a tracklet must be given in ONE fixed coordinate frame: the encoders see absolute coordinates, so the
         cached keys and values belong to the frame they were computed in.  (The offline pipeline moves a tracklet into the
@@ -449,16 +459,21 @@ class TrackletRoIHeadOCC(nn.Module):
         same = torch.zeros_like(frames)                                  # (the points are this frame's: one frame key)
         pooled = self._pool_points(pts_xyz, pts_feats, pts_batch_idx.long(), torch.zeros_like(pts_batch_idx, dtype=torch.long),
                                    rois, scores, same)
-        res = self.bbox_head.forward_step(*pooled, rois, frames, slots, state.cache)
+        occ_cfg = self.online_occ_cfg() if occ else None               # (a wrong test_cfg.online_occ: before any launch)
+        res = self.bbox_head.forward_step(*pooled, rois, frames, slots, state.cache, **({'return_points': True} if occ else {}))
         one = torch.cat([torch.zeros_like(rois[:, :1]), rois[:, 1:]], 1)   # (one group: get_bboxes splits by column 0)
         out_boxes, out_scores, out_labels, valid = self.bbox_head.get_bboxes_from_tracklet(
             one, res['cls_score'], res['bbox_pred'], res['nonempty_roi_mask'], labels, scores, None, gt_rois=gt_rois,
             cfg=self.test_cfg)[0]
-        return dict(boxes=out_boxes, scores=out_scores, labels=out_labels, valid=valid,
-                    fused_roi_feats=res['fused_roi_feats'], ori_roi_feats=res['ori_roi_feats'])
+        out = dict(boxes=out_boxes, scores=out_scores, labels=out_labels, valid=valid,
+                   fused_roi_feats=res['fused_roi_feats'], ori_roi_feats=res['ori_roi_feats'])
+        if occ:
+            out.update(self._step_occ(res, rois, occ_cfg, occ_transforms))
+        return out
 
     @torch.no_grad()
-    def simple_test_steps(self, pts_xyz, pts_feats, pts_row_idx, boxes, scores, labels, slot_rows, state, gt_rois=None):
+    def simple_test_steps(self, pts_xyz, pts_feats, pts_row_idx, boxes, scores, labels, slot_rows, state, gt_rois=None,
+                          occ=False):
         """``simple_test_step`` for one OR MORE new frames per tracklet in one call -- a tracklet that arrives with
         history (a track confirmed after several hits, a dropped batch), or a recorded one fed T frames at a time.  A row
         is one (tracklet, frame): ``pts_row_idx`` the ROW 0..n-1 a point belongs to, boxes [n, 7], scores [n], labels [n]
@@ -466,7 +481,8 @@ class TrackletRoIHeadOCC(nn.Module):
         and in frame order ([3, 3, 3, 0, 5, 5]: three frames for slot 3, one for slot 0, two for slot 5); a slot's frames
         continue where its earlier steps stopped.  Pooling, decode and the returned dict are those of simple_test_step,
         n rows in input order; the temporal transformer takes all rows in one launch per layer
-        (OccBBoxHead.forward_steps).  The coordinate-frame rule of simple_test_step holds.
+        (OccBBoxHead.forward_steps).  The coordinate-frame rule of simple_test_step holds, and ``occ=True`` adds its three
+        keys ``occ``, ``occ_flags`` and ``occ_counts`` for the n rows.
 
         Reported on the host before anything is launched: slots out of range, rows of a slot that are not consecutive, a
         run past the cache's cap (OcoccError), CPU tensors (OcoccError), training mode (RuntimeError)."""
@@ -485,13 +501,38 @@ class TrackletRoIHeadOCC(nn.Module):
         same = torch.zeros((n,), dtype=torch.long, device=boxes.device)   # (a row's points are its frame's: one frame key)
         pooled = self._pool_points(pts_xyz, pts_feats, pts_row_idx.long(), torch.zeros_like(pts_row_idx, dtype=torch.long),
                                    rois, scores, same)
-        res = self.bbox_head.forward_steps(*pooled, rois, slots, state.cache)
+        occ_cfg = self.online_occ_cfg() if occ else None
+        res = self.bbox_head.forward_steps(*pooled, rois, slots, state.cache, **({'return_points': True} if occ else {}))
         one = torch.cat([torch.zeros_like(rois[:, :1]), rois[:, 1:]], 1)   # (one group: get_bboxes splits by column 0)
         out_boxes, out_scores, out_labels, valid = self.bbox_head.get_bboxes_from_tracklet(
             one, res['cls_score'], res['bbox_pred'], res['nonempty_roi_mask'], labels, scores, None, gt_rois=gt_rois,
             cfg=self.test_cfg)[0]
-        return dict(boxes=out_boxes, scores=out_scores, labels=out_labels, valid=valid,
-                    fused_roi_feats=res['fused_roi_feats'], ori_roi_feats=res['ori_roi_feats'])
+        out = dict(boxes=out_boxes, scores=out_scores, labels=out_labels, valid=valid,
+                   fused_roi_feats=res['fused_roi_feats'], ori_roi_feats=res['ori_roi_feats'])
+        if occ:
+            out.update(self._step_occ(res, rois, occ_cfg))
+        return out
+
+    def online_occ_cfg(self):
+        """test_cfg.online_occ: an optional dict, ``observed`` (default True: the cells the frame's points fell into join
+        the predicted ones) and ``chunk`` (cells per decoder call, default 1 << 20 as get_occ_packed)"""
+        cfg = self.test_cfg.get('online_occ', None) or {}
+        if not isinstance(cfg, dict) or set(cfg) - {'observed', 'chunk'}:
+            raise ValueError(f'test_cfg.online_occ is a dict with the keys observed and chunk, not {cfg!r}')
+        chunk = cfg.get('chunk', 1 << 20)
+        if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+            raise ValueError(f'test_cfg.online_occ.chunk is the number of cells per decoder call, an int >= 1, not {chunk!r}')
+        return dict(observed=bool(cfg.get('observed', True)), chunk=chunk)
+
+    def _step_occ(self, res, rois, cfg, transforms=None):
+        """The three ``occ`` keys of a step from what the head returned with return_points: the grid of every row's INPUT
+        box decoded from the fused latent, joined with the cells the row's pooled points fell into
+        (OccBBoxHead.get_frame_occ); test_cfg.filter_empty_roi goes down as the kernels' row_keep bytes."""
+        keep = res['nonempty_roi_mask'] if self.test_cfg.get('filter_empty_roi', False) else None
+        out, flags, counts = self.bbox_head.get_frame_occ(res['fused_roi_feats'], rois, res['local_xyz'], res['roi_inds'],
+                                                          row_keep=keep, transforms=transforms, observed=cfg['observed'],
+                                                          chunk=cfg['chunk'])
+        return dict(occ=out, occ_flags=flags, occ_counts=counts)
 
     # PointsRangeFilter's range in the ococcnet pipelines (ococcnet_cfg.py) and LoadTrackletPoints' max_points there
     SCENE_ROWS_DEFAULTS = dict(extra_width=1.0, max_points=1024, attr_dims=2,
@@ -510,7 +551,7 @@ class TrackletRoIHeadOCC(nn.Module):
         return torch.cat([centre, b[:, 3:6], torch.atan2(t[:, 0], t[:, 1])[:, None]], 1).to(boxes.dtype)
 
     @torch.no_grad()
-    def simple_test_scene_step(self, points, pose, boxes, scores, labels, slot, state, gt_rois=None):
+    def simple_test_scene_step(self, points, pose, boxes, scores, labels, slot, state, gt_rois=None, occ=False):
         """simple_test_step from what a sensor frame brings: ``points`` [N, >= 3 + attr] f32, the scene cloud of the frame in
         its own ego frame; ``pose``, the 4x4 ego -> world of the frame (numpy or torch); ``boxes`` [n, 7], ``scores`` [n],
         ``labels`` [n], the tracker's output for the frame in the same ego frame; ``slot`` and ``state`` as in
@@ -527,7 +568,9 @@ class TrackletRoIHeadOCC(nn.Module):
 
         Returns the dict of simple_test_step (boxes in the slots' fixed frames) and two more keys: ``boxes_ego`` [n, 7], the
         refined boxes back in the frame's ego frame through inverse(M_i), rows with valid == False their input box bit for
-        bit; ``num_points`` [n] i64 on the host, the points in each enlarged box before the cap.
+        bit; ``num_points`` [n] i64 on the host, the points in each enlarged box before the cap.  ``occ=True`` adds
+        ``occ_ego`` [N, 4], the rows of simple_test_step's ``occ`` in the frame's ego frame -- through float32(inverse(M_i)),
+        the matrix ``boxes_ego`` uses, applied in the fill kernel --, ``occ_flags`` and ``occ_counts``.
 
         Reported on the host before anything is launched: what simple_test_step reports, a pose that is not 4x4 or not
         finite (OcoccError), a slot in mid-tracklet without an origin -- it was stepped through simple_test_step
@@ -572,7 +615,12 @@ class TrackletRoIHeadOCC(nn.Module):
         xyz, feats, row, counts = scene_step_rows(
             points, boxes, scores, transforms=mats[0].float(), extra_width=cfg['extra_width'], attr_dims=cfg['attr_dims'],
             point_cloud_range=cfg['point_cloud_range'], max_points=cfg['max_points'], deco_boxes=fixed_boxes)
-        out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois)
+        if occ:
+            out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois,
+                                        occ=True, occ_transforms=mats[1].float())
+            out['occ_ego'] = out.pop('occ')
+        else:
+            out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois)
         out['boxes_ego'] = torch.where(out['valid'].to(dev).bool()[:, None], self._boxes_through(out['boxes'], mats[1]),
                                        boxes[:, :7])
         out['num_points'] = counts

@@ -4,7 +4,7 @@
 clouds) stepped through frame by frame, the way the method is deployed -- no track-input database, no per-tracklet files:
 
     python tools/online_raw.py <config> <checkpoint> <raw.yaml> [--slots 64] [--out FILE.bin] [--poses poses.pkl]
-                               [--cfg-options k=v ...]
+                               [--save-occ DIR] [--cfg-options k=v ...]
 
 Per segment and frame, in time order: the frame's scene cloud is loaded once, every track that starts at the frame gets a
 free slot of the temporal K/V cache, TrackletRoIHeadOCC.simple_test_scene_step refines all live tracks in one call (crop,
@@ -14,6 +14,10 @@ simple_test_online chooses it: plain up to 256 frames, a ring with test_cfg.attn
 
 The refined objects (``boxes_ego``: each in its own frame's ego frame) are written as a Waymo metrics file; an object whose
 enlarged box held no point keeps the tracker's box and score, as do objects of types the yaml's ``type`` list leaves out.
+With --save-occ DIR every step also returns the completed occupancy of its frame (simple_test_scene_step(..., occ=True):
+``occ_ego``, csrc/occ_frame.hip) and the tool writes ``<DIR>/<segment>/<timestamp>/<type>_<id>.bin`` per frame and object,
+float32 [n, 4]: the cells in the frame's ego frame and the object's refined score of that frame in column 3 -- the layout
+tools/test.py --save-occ writes and occ_export.load_frame_occ reads.  Boxes, scores and cells of a frame come down in one copy.
 Config and checkpoint are loaded as tools/test.py loads them."""
 import argparse
 import os
@@ -44,18 +48,19 @@ def choose_cache(roi_head, longest):
                        f'holds at most {TemporalCache.MAX_LONG_CAP} frames of history')
 
 
-def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None):
+def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_occ=None):
     """``model``: a TrackletDetectorOCC in eval mode on a ROCm device; ``raw_yaml``: the track-input yaml (path or mapping,
     ctrl_prep.load_config); ``poses``: {timestamp: 4x4 ego -> world} or the path of its pickle (default: the yaml's
     ``poses_path``, else <mm_data_root>/poses.pkl).  Returns (records, state): one record per object of the tracker's
     file, tracks in order of first appearance and frames ascending -- dict(segment, id, type, timestamp, box [7] f32 in the
     frame's ego frame, score, num_points: the points in the enlarged box before the cap, refined: whether the head's
     result was taken) -- and the OnlineState, every slot released.  With ``out`` the records are written there as a Waymo
-    metrics file."""
+    metrics file.  With ``save_occ`` (a directory) the completed occupancy of every refined frame is written below it, one
+    file per frame and object (occ_export.write_tracklet_occ), and every record gets ``occ_cells``, the rows of its file."""
     import numpy as np
     import torch
     from objectcentricocccompletion_amd import _lib as L
-    from objectcentricocccompletion_amd import ctrl_prep, waymo_io
+    from objectcentricocccompletion_amd import ctrl_prep, occ_export, waymo_io
     cfg, _ = ctrl_prep.load_config(raw_yaml)
     rh = model.roi_head
     dev = torch.device(device) if device is not None else next(model.parameters()).device
@@ -73,6 +78,7 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None):
     scores_out = [t.scores.clone().float() for t in tracklets]
     num_points = [[0] * len(t) for t in tracklets]
     refined = [[False] * len(t) for t in tracklets]
+    occ_cells = [[0] * len(t) for t in tracklets]
     by_seg = defaultdict(list)
     for k in live:
         by_seg[tracklets[k].segment_name].append(k)
@@ -99,14 +105,27 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None):
             scores = torch.stack([tracklets[k].scores[i].float() for k, i in rows]).to(dev)
             labels = torch.tensor([WAYMO_TYPE_TO_LABEL[tracklets[k].type] for k, _ in rows], dtype=torch.long).to(dev)
             res = rh.simple_test_scene_step(torch.from_numpy(cloud).to(dev), np.asarray(poses[ts], dtype=np.float64), boxes,
-                                            scores, labels, [slot_of[k] for k, _ in rows], state)
+                                            scores, labels, [slot_of[k] for k, _ in rows], state,
+                                            **({'occ': True} if save_occ else {}))
             valid = res['valid'].to(dev).bool()
             back = torch.cat([res['boxes_ego'], torch.where(valid, res['scores'].float(), scores)[:, None],
-                              valid[:, None].float()], 1).cpu()           # one read-back per frame
+                              valid[:, None].float()], 1)
+            if save_occ:                                                  # boxes, scores and cells: still one read-back per frame
+                flat = torch.cat([back.reshape(-1), res['occ_ego'].reshape(-1)]).cpu()
+                back, cells = flat[:back.numel()].view(-1, 9), flat[back.numel():].view(-1, 4).numpy()
+                cuts = np.cumsum([0] + list(res['occ_counts']))
+            else:
+                back = back.cpu()                                         # one read-back per frame
             done = []
             for r, (k, i) in enumerate(rows):
                 boxes_out[k][i], scores_out[k][i] = back[r, :7], back[r, 7]
                 refined[k][i], num_points[k][i] = bool(back[r, 8]), int(res['num_points'][r])
+                if save_occ:
+                    mine = cells[cuts[r]:cuts[r + 1]].copy()
+                    mine[:, 3] = float(back[r, 7])                        # the score column of the exported files
+                    occ_export.write_tracklet_occ(save_occ, seg, [ts], tracklets[k].type, tracklets[k].id, mine,
+                                                  [len(mine)])
+                    occ_cells[k][i] = len(mine)
                 if i == len(tracklets[k]) - 1:
                     done.append(slot_of.pop(k))
             if done:
@@ -118,6 +137,8 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None):
         for i, ts in enumerate(t.ts_list):
             records.append(dict(segment=t.segment_name, id=t.id, type=t.type, timestamp=ts, box=b[i], score=float(s[i]),
                                 num_points=num_points[k][i], refined=refined[k][i]))
+            if save_occ:
+                records[-1]['occ_cells'] = occ_cells[k][i]
             if out:
                 chunks.append(waymo_io._f_bytes(1, waymo_io.lidar2waymo_box(b[i], s[i], t.type, t.segment_name, ts, t.id)))
     if out:
@@ -136,6 +157,9 @@ def parse_args(argv=None):
     ap.add_argument('--out', default=None, help='the refined objects as a Waymo metrics file (default: <bin stem>_online.bin)')
     ap.add_argument('--poses', default=None, help='poses.pkl: {timestamp: 4x4 ego -> world} (default: the yaml\'s poses_path, '
                     'else <mm_data_root>/poses.pkl)')
+    ap.add_argument('--save-occ', metavar='DIR', default=None,
+                    help='write the completed occupancy of every frame and object below DIR: <segment>/<timestamp>/<type>_<id>.bin, '
+                    'float32 [n, 4] in the frame\'s ego frame, the refined score in column 3 (occ_export.load_frame_occ reads it)')
     ap.add_argument('--cfg-options', nargs='+', default=[], help='k=v overrides merged into the config')
     args = ap.parse_args(argv)
     if args.slots < 1:
@@ -162,8 +186,10 @@ def main(argv=None):
     model.eval()
     raw, _ = ctrl_prep.load_config(args.raw_yaml)
     out = args.out or os.path.splitext(ctrl_prep.bin_path_for_split(raw))[0] + '_online.bin'
-    records, _ = replay(model, args.raw_yaml, slots=args.slots, out=out, poses=args.poses, device=dev)
+    records, _ = replay(model, args.raw_yaml, slots=args.slots, out=out, poses=args.poses, device=dev, save_occ=args.save_occ)
     print(f'{len(records)} objects, {sum(r["refined"] for r in records)} refined; wrote {out}')
+    if args.save_occ:
+        print(f'{sum(r.get("occ_cells", 0) for r in records)} occupancy cells in {args.save_occ}')
     return out
 
 

@@ -413,6 +413,20 @@ def workspace(nbytes, device):
     return empty((max(int(nbytes), 1),), torch.uint8, device)
 
 
+def count_scan_fill(tiles, groups, cols, device, count, fill):
+    """The host side of an ordered compaction in two launches (csrc/wave_compact.hpp): ``count(tile_counts,
+    group_counts)`` launches the count pass, the exclusive scan of tile_counts [tiles] says where each tile's survivors
+    start, the counts per group [groups] are the ONE read-back, and ``fill(scan, out, n)`` launches the fill pass into
+    out [n, cols] f32.  Returns (out, the counts per group as a list of int, what ``fill`` returned)."""
+    tile_counts = empty((tiles,), torch.int32, device)
+    group_counts = empty((groups,), torch.int64, device)
+    count(tile_counts, group_counts)
+    scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts
+    counts = [int(v) for v in group_counts.tolist()]
+    out = empty((sum(counts), cols), torch.float32, device)
+    return out, counts, fill(scan, out, out.size(0))
+
+
 _logged = set()
 
 

@@ -131,18 +131,14 @@ def gt_occ_crop_kernels(cells, gt_boxes, roi_boxes, cos_gt, sin_gt, cos_roi, sin
     (gb, ldg), (rb, ldr) = _rows7(gt_boxes), _rows7(roi_boxes)
     trig = [t.contiguous().view(-1) for t in trig]
     tiles = int(L.lib.ococc_gt_occ_crop_tiles(N, K))
-    tile_counts = L.empty((tiles,), torch.int32, dev)
-    frame_counts = L.empty((N,), torch.int64, dev)
-    L.check(L.lib.ococc_gt_occ_crop_count(L.ptr(cells), K, L.ptr(gb), ldg, L.ptr(rb), ldr, N, *(L.ptr(t) for t in trig[:4]),
-                                          L.ptr(tile_counts), tiles, L.ptr(frame_counts), L.stream()), 'gt_occ_crop_count')
-    scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts   # exclusive: where a tile's cells start
-    counts = [int(v) for v in frame_counts.tolist()]                       # the one read-back
-    M = sum(counts)
-    out = L.empty((M, 4), torch.float32, dev)
-    L.check(L.lib.ococc_gt_occ_crop_fill(L.ptr(cells), K, L.ptr(gb), ldg, L.ptr(rb), ldr, N, *(L.ptr(t) for t in trig[:4]),
-                                         L.ptr(scan), tiles, L.ptr(trig[4]) if values is not None else None, L.ptr(out), M,
-                                         L.stream()), 'gt_occ_crop_fill')
-    return out, counts
+    boxes = (L.ptr(cells), K, L.ptr(gb), ldg, L.ptr(rb), ldr, N, *(L.ptr(t) for t in trig[:4]))
+    return L.count_scan_fill(
+        tiles, N, 4, dev,
+        lambda tile_counts, frame_counts: L.check(L.lib.ococc_gt_occ_crop_count(
+            *boxes, L.ptr(tile_counts), tiles, L.ptr(frame_counts), L.stream()), 'gt_occ_crop_count'),
+        lambda scan, out, M: L.check(L.lib.ococc_gt_occ_crop_fill(
+            *boxes, L.ptr(scan), tiles, L.ptr(trig[4]) if values is not None else None, L.ptr(out), M, L.stream()),
+            'gt_occ_crop_fill'))[:2]
 
 
 def crop_gt_occ_packed(cells, gt_boxes, roi_boxes, values=None):

@@ -9,10 +9,9 @@
 //
 //   count : one wave per tile, 16 rounds of 64 pairs, lane = pair, one ballot per round; popcounts summed ->
 //           tile_counts [N * T] i32 and one 64-bit integer atomic per tile into frame_counts [N].
-//   fill  : the same tiles; with scan = exclusive prefix of tile_counts, a kept cell lands at
-//           scan[tile] + (kept cells of earlier rounds) + popcount(ballot below the lane): (tile, round, lane) IS
-//           ascending cell order inside a frame and frame order across frames (the idiom of occ_export.hip and
-//           tracklet_crop.hip).  The LiDAR-frame point is recomputed, column 3 is value[n] or 1.
+//   fill  : the same tiles; with scan = exclusive prefix of tile_counts, a kept cell lands where wave_tile_compact
+//           (wave_compact.hpp) ranks it: cell order inside a frame and frame order across frames.  The LiDAR-frame
+//           point is recomputed, column 3 is value[n] or 1.
 //
 // Algorithmic bytes: 12 B in per pair in each launch (the K cells are read N times; K * 12 B stays in L2), 4 B out per
 // tile, 16 B out per kept pair.  Memory bound and small.  No float atomics; integer counts: the same input gives the
@@ -20,15 +19,15 @@
 // caller's.
 #include "common.hpp"
 #include "occ_math.hpp"
+#include "wave_compact.hpp"
 
 // every float product and sum below is rounded on its own, as the ATen comparator (bbox.crop_gt_occ_aten) rounds them
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kRounds = kOccCompactRounds;
-constexpr int kTile = kOccCompactTile;   // 1024 pairs per wave
-constexpr int kWaves = kOccCompactWaves;
+constexpr int kTile = kCompactTile;   // 1024 pairs per wave
+constexpr int kWaves = kCompactWaves;
 constexpr int kBlock = 64 * kWaves;
 
 struct CropArgs {
@@ -55,6 +54,8 @@ struct CropArgs {
   int64_t n_out;
 };
 
+struct Pt { float x, y, z; };
+
 template <bool FILL>
 __global__ void __launch_bounds__(kBlock) gt_occ_crop_kernel(CropArgs a) {
   const int lane = threadIdx.x & 63;
@@ -74,34 +75,25 @@ __global__ void __launch_bounds__(kBlock) gt_occ_crop_kernel(CropArgs a) {
   const float val = FILL ? (a.value ? a.value[n] : 1.0f) : 0.f;
   const int64_t base = FILL ? a.scan[t] : 0;
 
-  int cnt = 0;
-#pragma unroll 4
-  for (int k = 0; k < kRounds; ++k) {
-    const int64_t cell = c0 + k * 64 + lane;
-    float x = 0.f, y = 0.f, z = 0.f;
-    bool in = false;
-    if (cell < cend) {
-      const float* p = a.cells + cell * 3;
-      x = p[0], y = p[1], z = p[2];
-      ococc_box_to_lidar(x, y, z, cg, sg, gx, gy, gz, ghh);
-      // check_pt_in_box3d: inclusive on the z faces, strict on the side faces
-      const float dz = z - cz, dx = x - rx, dy = y - ry;
-      const float xc = dx * ca, ys = dy * (-sa), xs = dx * sa, yc = dy * ca;
-      const float lx = xc + ys, ly = xs + yc;
-      in = !(fabsf(dz) > hh) && (lx > -hl) && (lx < hl) && (ly > -hw) && (ly < hw);
-    }
-    const unsigned long long bal = __ballot(in);
-    if (FILL && in) {
-      const int64_t pos = base + cnt + __popcll(bal & ((1ull << lane) - 1ull));
-      if (pos < a.n_out)   // (count, scan and fill of the same input: always)
-        *reinterpret_cast<f32x4*>(a.out + pos * 4) = f32x4{x, y, z, val};
-    }
-    cnt += __popcll(bal);
-  }
-  if (!FILL && lane == 0) {
-    a.tile_counts[t] = cnt;
-    if (cnt) atomicAdd(a.frame_counts + n, (unsigned long long)cnt);
-  }
+  wave_tile_compact<FILL, Pt>(
+      lane, base, a.n_out, a.tile_counts + t, a.frame_counts + n,
+      [&](int i, Pt& p) {
+        const int64_t cell = c0 + i;
+        bool in = false;
+        if (cell < cend) {
+          const float* q = a.cells + cell * 3;
+          p.x = q[0], p.y = q[1], p.z = q[2];
+          ococc_box_to_lidar(p.x, p.y, p.z, cg, sg, gx, gy, gz, ghh);
+          // check_pt_in_box3d: inclusive on the z faces, strict on the side faces
+          const float dz = p.z - cz, dx = p.x - rx, dy = p.y - ry;
+          const float xc = dx * ca, ys = dy * (-sa), xs = dx * sa, yc = dy * ca;
+          const float lx = xc + ys, ly = xs + yc;
+          // (& and not &&: behind a branch on the height test the count pass loads z first and x, y after it)
+          in = !(fabsf(dz) > hh) & (lx > -hl) & (lx < hl) & (ly > -hw) & (ly < hw);
+        }
+        return in;
+      },
+      [&](int, const Pt& p, int64_t pos) { *reinterpret_cast<f32x4*>(a.out + pos * 4) = f32x4{p.x, p.y, p.z, val}; });
 }
 
 // the argument checks both launches share; 1: nothing to launch, 0: go on, < 0: an error

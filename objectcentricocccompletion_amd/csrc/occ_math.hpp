@@ -21,12 +21,6 @@ __device__ __forceinline__ float ococc_cell_centre(int c, float size, float voxe
   return lo + voxel_size / 2.0f;
 }
 
-// The tiles of the order-preserving compactions (occ_export.hip, gt_occ_crop.hip): one wave per tile of 16 rounds of 64
-// consecutive elements, one ballot per round; kOccCompactWaves tiles per block.
-constexpr int kOccCompactRounds = 16;
-constexpr int kOccCompactTile = 64 * kOccCompactRounds;   // 1024 elements per wave
-constexpr int kOccCompactWaves = 4;
-
 // A point of a box's gravity-centred frame in the LiDAR frame (OccDecoder._to_lidar, occ_base.py:220-230, 330-336;
 // tracklet_roi_head_occ.py:665-670): rotation_3d_in_axis(axis=2) with the transposed matrix, x c + y s and -x s + y c,
 // then + the bottom centre (bx, by, bz), then z + half_h; (c, s) the cos / sin of the yaw

@@ -1,10 +1,11 @@
-// What the order-preserving compactions over the flat cell list share (occ_export.hip, occ_frame.hip): the RoI search
-// over a prefix table, the centre of a cell from its id, and the one-wave kernel that derives the tile table.
+// What the kernels over the flat cell list share (occ_export.hip, occ_frame.hip): the RoI search over a prefix table, the
+// centre of a cell from its id, and the host side of the one select kernel (occ_export.hip) that compacts the list.
 // The list: RoI after RoI, x slowest and z fastest inside an RoI; start [R + 1] i64 the exclusive prefix of the cells
-// per RoI; tiles of kOccCompactTile consecutive cells of ONE RoI (occ_math.hpp).
+// per RoI; tiles of kCompactTile consecutive cells of ONE RoI (wave_compact.hpp).
 #pragma once
 #include "common.hpp"
 #include "occ_math.hpp"
+#include "wave_compact.hpp"
 
 // the largest r in [0, R) with table[r] <= i, for an ascending table [R + 1] with table[0] <= i: the RoI of cell i (of
 // tile i); RoIs without cells (equal neighbours) are stepped over.  Reads entries 1 .. R - 1 only.
@@ -29,25 +30,30 @@ __device__ __forceinline__ Cell cell_centre(uint32_t local, const float* __restr
           ococc_cell_centre((int)iz, size[2], voxel_size)};
 }
 
-// tile_start [R + 1]: exclusive prefix of ceil((start[r + 1] - start[r]) / 1024).  One wave, 64 RoIs per step.
-// (static: one copy per translation unit that launches it)
-static __global__ void __launch_bounds__(64)
-tile_table_kernel(const int64_t* __restrict__ start, int R, int64_t* __restrict__ tile_start) {
-  const int lane = threadIdx.x;
-  int64_t carry = 0;
-  if (lane == 0) tile_start[0] = 0;
-  for (int base = 0; base < R; base += 64) {
-    const int r = base + lane;
-    int64_t v = 0;
-    if (r < R) {
-      const int64_t k = start[r + 1] - start[r];
-      v = k > 0 ? (k + kOccCompactTile - 1) / kOccCompactTile : 0;
-    }
-    for (int d = 1; d < 64; d <<= 1) {
-      const int64_t u = __shfl_up(v, d, 64);
-      if (lane >= d) v += u;
-    }
-    if (r < R) tile_start[r + 1] = carry + v;
-    carry += __shfl(v, 63, 64);
-  }
-}
+// What the fill launch of the select kernel writes: a row per selected cell, in cell order.
+struct OccFillArgs {
+  const int64_t* scan;      // [max_tiles] exclusive prefix of tile_counts
+  const float* sizes;       // [R, 3] enlarged sizes
+  const int32_t* dims;      // [R, 3]
+  float voxel_size;
+  const float* rois;        // the pose, or null (box frame): rows of roi_stride floats, columns 1-3 the bottom centre,
+  int64_t roi_stride;       //   column 6 the height
+  const float* cos_yaw;     // [R]
+  const float* sin_yaw;     // [R]
+  const float* transforms;  // [R, 12] row-major 3x4 applied after the pose, or null
+  const float* roi_value;   // [R] for column 3, or null: sigmoid(logit)
+  int cols;                 // 3 or 4
+  float* out;               // [n_out, cols]
+  uint8_t* flags;           // [n_out] bit 0 predicted, bit 1 observed; or null
+  int64_t n_out;
+};
+
+// The two launches of the select kernel, behind ococc_occ_select_* and ococc_occ_frame_*; `fn`, the export, heads the
+// messages.  Selected: (ococc_occupied(logit) or observed[cell]) and row_keep[RoI] != 0; observed and row_keep may be null.
+// count checks its arguments, zeroes roi_counts and derives tile_start in front; fill launches only.
+int occ_select_count(const char* fn, const float* logits, const uint8_t* observed, const uint8_t* row_keep, int64_t n,
+                     const int64_t* start, int32_t R, float pos_thresh, int64_t* tile_start, int32_t* tile_counts,
+                     int64_t max_tiles, int64_t* roi_counts, hipStream_t stream);
+int occ_select_fill(const char* fn, const float* logits, const uint8_t* observed, const uint8_t* row_keep, int64_t n,
+                    const int64_t* start, const int64_t* tile_start, int32_t R, float pos_thresh, int64_t max_tiles,
+                    const OccFillArgs& a, hipStream_t stream);

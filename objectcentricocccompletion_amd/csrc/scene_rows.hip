@@ -5,19 +5,16 @@
 // PointDecoration and PointsRangeFilter, each a pass of its own over the points.  Here: one count launch, one read-back of
 // counts [n], one fill launch that writes the ROWS (xyz, features, row index), not indices.
 //
-// The plan is that of tracklet_crop.hip: a workgroup of 4 waves takes 4096 consecutive points (and, by blockIdx.y, a span
-// of the boxes: the points of one frame alone would leave most CUs idle -- box_span), each wave 1024 consecutive ones ("wave tile": 16 rounds of 64, lane = point, kept in registers, every point read once per pass however many boxes
-// there are); the boxes are staged 64 at a time in LDS (centre, half sizes, cos / sin, the conservative BEV radius, and the
-// box's 3x4 matrix) and read as broadcasts.  Per box and round one ballot: its popcount is the count, the popcount below the
-// lane the rank -- (wave tile, round, lane) is ascending point order, so no sort.  The count pass leaves the per-(wave tile,
-// box) counts in the workspace [wave tiles, n] i32 (box-minor); the fill pass sums the earlier wave tiles in front of its
-// own ranks.
+// The plan is that of tracklet_crop.hip, and the split, the staged boxes, the wave tile of points and the box test are
+// the same code (box_crop.hpp): a workgroup of 4 waves takes 4096 consecutive points (and, by blockIdx.y, a span of the
+// boxes: the points of one frame alone would leave most CUs idle -- box_span), each wave 1024 consecutive ones, read once
+// per pass however many boxes there are; the boxes are staged 64 at a time in LDS, here with the box's 3x4 matrix.  Per box
+// and round one ballot: its popcount is the count, the popcount below the lane the rank -- (wave tile, round, lane) is
+// ascending point order, so no sort.  The count pass leaves the per-(wave tile, box) counts in the workspace
+// [wave tiles, n] i32 (box-minor); the fill pass sums the earlier wave tiles in front of its own ranks.
 //
 // Membership of point p in box b, the same in both passes:
-//   1. the box test of tracklet_crop_kernel on the UNTRANSFORMED point, restated below expression for expression (the two
-//      files are held to bit equality by tests/test_gpu_scene_rows.py): |z - (z_bottom + h/2)| <= h/2, the radius reject,
-//      (dx, dy) turned by rot = (float)((double)yaw + pi/2), strict inequalities in BEV.  A NaN x or y is in no box; a NaN z
-//      passes the height test as it does there (!(|dz| > h/2)) and is dropped by the range, when one is given.
+//   1. StagedBox::holds on the UNTRANSFORMED point; a NaN z passes it and is dropped by the range, when one is given.
 //   2. with a range: the WRITTEN xyz strictly inside (x0, y0, z0, x1, y1, z1) (PointsRangeFilter).
 // The written xyz: with transforms, row b's row-major 3x4 matrix m applied as x' = fmaf(z, m02, fmaf(y, m01, fmaf(x, m00,
 // m03))) (y', z' with rows 1, 2); the identity returns the input bits (a -0.0 comes out as +0.0); without, the input bits.
@@ -32,20 +29,19 @@
 // ones); fill: + about T/2 * n * 4 B workspace in per wave tile (L2), M * A * 4 B of attributes in (the lines of the xyz) and
 // M * (12 + (A + K) * 4 + 8) B of rows out.  T = ceil(N / 1024) wave tiles, M = scan_out[n].  Vector stores only.
 #include "common.hpp"
+#include "box_crop.hpp"
 
 namespace {
 
-constexpr int kRounds = 16;                 // points per lane
-constexpr int kWaveTile = 64 * kRounds;     // 1024 points per wave
-constexpr int kWaves = 4;
-constexpr int kBlockTile = kWaveTile * kWaves;
-constexpr int kChunk = 64;                  // boxes staged at a time: one per lane
+constexpr int kWaves = kCropWaves;
+constexpr int kBlockTile = kCropBlockTile;
+constexpr int kChunk = kCropChunk;
 
 struct Range6 {
   float v[6];
 };
 
-// XR: a transform or a range is given (without either, the test is tracklet_crop_kernel's alone and needs fewer registers)
+// XR: a transform or a range is given (without either, the test is the box's alone and needs fewer registers)
 template <bool FILL, bool XR>
 __global__ void __launch_bounds__(64 * kWaves)
 scene_rows_kernel(const float* __restrict__ points, int64_t n, int32_t C, const float* __restrict__ boxes, int32_t nb,
@@ -53,26 +49,17 @@ scene_rows_kernel(const float* __restrict__ points, int64_t n, int32_t C, const 
                   unsigned long long* __restrict__ counts, int32_t A, const float* __restrict__ row_feats, int32_t K,
                   int64_t cap, const int64_t* __restrict__ scan_all, const int64_t* __restrict__ scan_out,
                   float* __restrict__ out_xyz, float* __restrict__ out_feats, int64_t* __restrict__ out_row) {
-  __shared__ float sb[9][kChunk];    // cx, cy, cz, hl, hw, hh, cos, sin, r^2
+  __shared__ BoxChunk sb;
   __shared__ float sm[12][kChunk];   // the box's 3x4 matrix, row-major
   const int64_t tile0 = (int64_t)blockIdx.x * kBlockTile;
   if (tile0 >= n) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t w0 = tile0 + (int64_t)wave * kWaveTile;   // index of this wave's first point
+  const int64_t w0 = tile0 + (int64_t)wave * kCropWaveTile;   // index of this wave's first point
   const int64_t wt = (int64_t)blockIdx.x * kWaves + wave;  // wave tile
   const bool xform = XR && transforms != nullptr;
 
-  float px[kRounds], py[kRounds], pz[kRounds];
-#pragma unroll
-  for (int r = 0; r < kRounds; ++r) {
-    const int64_t i = w0 + r * 64 + lane;
-    if (i < n) {
-      const float* q = points + i * C;
-      px[r] = q[0], py[r] = q[1], pz[r] = q[2];
-    } else {
-      px[r] = 0.f, py[r] = 0.f, pz[r] = INFINITY;   // fails the height test of every box
-    }
-  }
+  WavePoints p;
+  p.load(points, C, n, w0, lane);
 
   // this workgroup's boxes: [blockIdx.y * span, b_end)
   const int b_end = (int)min((int64_t)nb, ((int64_t)blockIdx.y + 1) * span);
@@ -80,14 +67,7 @@ scene_rows_kernel(const float* __restrict__ points, int64_t n, int32_t C, const 
     const int cn = min(kChunk, b_end - c0);
     __syncthreads();
     if (tid < cn) {
-      // (tracklet_crop_kernel's staging, expression for expression)
-      const float* b = boxes + (int64_t)(c0 + tid) * 7;
-      const float hh = b[5] * 0.5f, hl = b[4] * 0.5f, hw = b[3] * 0.5f;
-      const float rot = (float)((double)b[6] + 1.5707963267948966);
-      sb[0][tid] = b[0], sb[1][tid] = b[1], sb[2][tid] = b[2] + hh;
-      sb[3][tid] = hl, sb[4][tid] = hw, sb[5][tid] = hh;
-      sb[6][tid] = cosf(rot), sb[7][tid] = sinf(rot);
-      sb[8][tid] = (hl * hl + hw * hw) * 1.001f + 1e-6f;   // |local|^2 < hl^2 + hw^2 inside; the slack covers rounding
+      sb.stage(tid, boxes + (int64_t)(c0 + tid) * 7);
       if (xform) {
         const float* m = transforms + (int64_t)(c0 + tid) * 12;
 #pragma unroll
@@ -109,27 +89,20 @@ scene_rows_kernel(const float* __restrict__ points, int64_t n, int32_t C, const 
     }
     int mine = 0;                // lane j: count of box c0 + j in this wave tile
     for (int j = 0; j < cn; ++j) {
-      const float cx = sb[0][j], cy = sb[1][j], cz = sb[2][j], hl = sb[3][j], hw = sb[4][j], hh = sb[5][j];
-      const float ca = sb[6][j], sa = sb[7][j], r2 = sb[8][j];
+      const StagedBox box = sb.get(j);
       const int64_t base_j = FILL ? __shfl(base, j, 64) : 0, total_j = FILL ? __shfl(total, j, 64) : 0;
       const int64_t start_j = FILL ? __shfl(start, j, 64) : 0, end_j = FILL ? __shfl(end, j, 64) : 0;
       const bool pick = FILL && cap > 0 && total_j > cap;   // wave-uniform
       int cnt = 0;               // wave-uniform
 #pragma unroll
-      for (int r = 0; r < kRounds; ++r) {
-        // (tracklet_crop_kernel's test, expression for expression)
-        const float dx = px[r] - cx, dy = py[r] - cy;
-        bool in = !(fabsf(pz[r] - cz) > hh) && !(dx * dx + dy * dy > r2);
-        if (in) {
-          const float lx = dx * ca + dy * (-sa), ly = dx * sa + dy * ca;
-          in = (lx > -hl) & (lx < hl) & (ly > -hw) & (ly < hw);
-        }
-        float ox = px[r], oy = py[r], oz = pz[r];
+      for (int r = 0; r < kCropRounds; ++r) {
+        bool in = box.holds(p.x[r], p.y[r], p.z[r]);
+        float ox = p.x[r], oy = p.y[r], oz = p.z[r];
         if (XR && __ballot(in)) {   // wave-uniform: most (box, round) pairs have no point in the box
           if (in && xform) {
-            ox = fmaf(pz[r], sm[2][j], fmaf(py[r], sm[1][j], fmaf(px[r], sm[0][j], sm[3][j])));
-            oy = fmaf(pz[r], sm[6][j], fmaf(py[r], sm[5][j], fmaf(px[r], sm[4][j], sm[7][j])));
-            oz = fmaf(pz[r], sm[10][j], fmaf(py[r], sm[9][j], fmaf(px[r], sm[8][j], sm[11][j])));
+            ox = fmaf(p.z[r], sm[2][j], fmaf(p.y[r], sm[1][j], fmaf(p.x[r], sm[0][j], sm[3][j])));
+            oy = fmaf(p.z[r], sm[6][j], fmaf(p.y[r], sm[5][j], fmaf(p.x[r], sm[4][j], sm[7][j])));
+            oz = fmaf(p.z[r], sm[10][j], fmaf(p.y[r], sm[9][j], fmaf(p.x[r], sm[8][j], sm[11][j])));
           }
           if (in && has_range)
             in = (ox > range.v[0]) & (oy > range.v[1]) & (oz > range.v[2]) & (ox < range.v[3]) & (oy < range.v[4]) &
@@ -137,7 +110,7 @@ scene_rows_kernel(const float* __restrict__ points, int64_t n, int32_t C, const 
         }
         const unsigned long long bal = __ballot(in);
         if (FILL && in) {
-          const int64_t jm = base_j + cnt + __popcll(bal & ((1ull << lane) - 1ull));   // member index in the box
+          const int64_t jm = base_j + cnt + wave_rank(bal, lane);   // member index in the box
           int64_t pos = jm;
           bool keep = jm < total_j;            // (counts and scans of the same input: always)
           if (pick) {

@@ -3,18 +3,16 @@
 // upload of the box, one points_in_boxes launch over the whole cloud, one boolean-mask compaction and one
 // device-to-host copy.  Here: one count launch, one read-back of counts [B], one fill launch per batch of frames.
 //
-// Membership is check_pt_in_box3d (mmdet3d/ops/roiaware_pool3d/src/points_in_boxes_cuda.cu:24-49), each box on its
-// own, so a point may fall into several (overlapping, enlarged) boxes:
-//   |z - (z_bottom + h/2)| <= h/2;  (dx, dy) turned by yaw + pi/2;  -l/2 < local_x < l/2,  -w/2 < local_y < w/2.
+// Membership is check_pt_in_box3d, each box on its own, so a point may fall into several (overlapping, enlarged) boxes.
+// The test, the staged boxes and the wave tile of points are box_crop.hpp's, shared with scene_rows.hip.
 //
 // Work split: blockIdx.y = frame, a workgroup of 4 waves takes 4096 consecutive points of the frame, each wave 1024
 // consecutive ones ("wave tile": 16 rounds of 64, lane = point, kept in registers, every point read ONCE per pass
-// however many boxes the frame has).  The frame's boxes are staged 64 at a time in LDS once per workgroup (centre,
-// half sizes, cos / sin, a conservative BEV radius for a cheap reject) and read as broadcasts.  Per box and round one
-// ballot: its popcount is the count, the popcount below the lane the rank -- (wave tile, round, lane) IS ascending
-// point order, so no sort.  Two levels: the count pass leaves the per-(wave tile, box) counts in the workspace
-// [wave tiles per frame, B] i32 (box-minor: the fill pass reads 64 boxes of one wave tile as one 256 B line); the fill
-// pass sums the earlier wave tiles of its frame in front of its own ranks.
+// however many boxes the frame has).  The frame's boxes are staged 64 at a time in LDS once per workgroup and read as
+// broadcasts.  Per box and round one ballot: its popcount is the count, the popcount below the lane the rank -- (wave
+// tile, round, lane) IS ascending point order, so no sort.  Two levels: the count pass leaves the per-(wave tile, box)
+// counts in the workspace [wave tiles per frame, B] i32 (box-minor: the fill pass reads 64 boxes of one wave tile as one
+// 256 B line); the fill pass sums the earlier wave tiles of its frame in front of its own ranks.
 //
 // Algorithmic bytes per pass: N * 12 B of xyz (the rows are C * 4 B apart, so N * C * 4 B of cache lines move: 24 B
 // at C = 6), B * 28 B of boxes per workgroup (L2);  count: + T * B * 4 B workspace out, B * 8 B counts;
@@ -27,14 +25,13 @@
 // (zero-filled by the caller side of the export; a plain store of the same value from every wave tile that hits).
 // No workspace, no second pass.  Algorithmic bytes: N * 12 B of xyz in, B * 4 B out.
 #include "common.hpp"
+#include "box_crop.hpp"
 
 namespace {
 
-constexpr int kRounds = 16;                 // points per lane
-constexpr int kWaveTile = 64 * kRounds;     // 1024 points per wave
-constexpr int kWaves = 4;
-constexpr int kBlockTile = kWaveTile * kWaves;
-constexpr int kChunk = 64;                  // boxes staged at a time: one per lane
+constexpr int kWaves = kCropWaves;
+constexpr int kBlockTile = kCropBlockTile;
+constexpr int kChunk = kCropChunk;
 
 enum CropMode { kCount = 0, kFill = 1, kFlag = 2 };
 
@@ -45,7 +42,7 @@ tracklet_crop_kernel(const float* __restrict__ points, int32_t C, const int64_t*
                      const float* __restrict__ boxes, const int64_t* __restrict__ box_offsets, int64_t B,
                      int32_t* __restrict__ tile_counts, unsigned long long* __restrict__ counts,
                      const int64_t* __restrict__ scan, int64_t* __restrict__ out_index) {
-  __shared__ float sb[9][kChunk];   // cx, cy, cz, hl, hw, hh, cos, sin, r^2
+  __shared__ BoxChunk sb;
   const int f = blockIdx.y;
   const int64_t p0 = point_offsets[f], n = point_offsets[f + 1] - p0;
   const int64_t tile0 = (int64_t)blockIdx.x * kBlockTile;
@@ -54,33 +51,16 @@ tracklet_crop_kernel(const float* __restrict__ points, int32_t C, const int64_t*
   const int nb = (int)(box_offsets[f + 1] - b0);
   if (nb <= 0) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t w0 = tile0 + (int64_t)wave * kWaveTile;   // frame-local index of this wave's first point
-  const int64_t wt = (int64_t)blockIdx.x * kWaves + wave;  // wave tile of the frame
+  const int64_t w0 = tile0 + (int64_t)wave * kCropWaveTile;   // frame-local index of this wave's first point
+  const int64_t wt = (int64_t)blockIdx.x * kWaves + wave;      // wave tile of the frame
 
-  float px[kRounds], py[kRounds], pz[kRounds];
-#pragma unroll
-  for (int r = 0; r < kRounds; ++r) {
-    const int64_t i = w0 + r * 64 + lane;
-    if (i < n) {
-      const float* q = points + (p0 + i) * C;
-      px[r] = q[0], py[r] = q[1], pz[r] = q[2];
-    } else {
-      px[r] = 0.f, py[r] = 0.f, pz[r] = INFINITY;   // fails the height test of every box
-    }
-  }
+  WavePoints p;
+  p.load(points + p0 * C, C, n, w0, lane);
 
   for (int c0 = 0; c0 < nb; c0 += kChunk) {
     const int cn = min(kChunk, nb - c0);
     __syncthreads();
-    if (tid < cn) {
-      const float* b = boxes + (b0 + c0 + tid) * 7;
-      const float hh = b[5] * 0.5f, hl = b[4] * 0.5f, hw = b[3] * 0.5f;
-      const float rot = (float)((double)b[6] + 1.5707963267948966);
-      sb[0][tid] = b[0], sb[1][tid] = b[1], sb[2][tid] = b[2] + hh;
-      sb[3][tid] = hl, sb[4][tid] = hw, sb[5][tid] = hh;
-      sb[6][tid] = cosf(rot), sb[7][tid] = sinf(rot);
-      sb[8][tid] = (hl * hl + hw * hw) * 1.001f + 1e-6f;   // |local|^2 < hl^2 + hw^2 inside; the slack covers rounding
-    }
+    if (tid < cn) sb.stage(tid, boxes + (b0 + c0 + tid) * 7);
     __syncthreads();
 
     constexpr bool FILL = MODE == kFill;
@@ -94,18 +74,12 @@ tracklet_crop_kernel(const float* __restrict__ points, int32_t C, const int64_t*
     }
     int mine = 0;                // lane j: count of box c0 + j in this wave tile
     for (int j = 0; j < cn; ++j) {
-      const float cx = sb[0][j], cy = sb[1][j], cz = sb[2][j], hl = sb[3][j], hw = sb[4][j], hh = sb[5][j];
-      const float ca = sb[6][j], sa = sb[7][j], r2 = sb[8][j];
+      const StagedBox box = sb.get(j);
       const int64_t base_j = FILL ? __shfl(base, j, 64) : 0, end_j = FILL ? __shfl(end, j, 64) : 0;
       int cnt = 0;               // wave-uniform
 #pragma unroll
-      for (int r = 0; r < kRounds; ++r) {
-        const float dx = px[r] - cx, dy = py[r] - cy;
-        bool in = !(fabsf(pz[r] - cz) > hh) && !(dx * dx + dy * dy > r2);
-        if (in) {
-          const float lx = dx * ca + dy * (-sa), ly = dx * sa + dy * ca;
-          in = (lx > -hl) & (lx < hl) & (ly > -hw) & (ly < hw);
-        }
+      for (int r = 0; r < kCropRounds; ++r) {
+        const bool in = box.holds(p.x[r], p.y[r], p.z[r]);
         const unsigned long long bal = __ballot(in);
         if (MODE == kFlag) {
           if (bal) {
@@ -115,7 +89,7 @@ tracklet_crop_kernel(const float* __restrict__ points, int32_t C, const int64_t*
           continue;
         }
         if (FILL && in) {
-          const int64_t pos = base_j + cnt + __popcll(bal & ((1ull << lane) - 1ull));
+          const int64_t pos = base_j + cnt + wave_rank(bal, lane);
           if (pos < end_j) out_index[pos] = w0 + r * 64 + lane;   // (pos < end_j: counts and scan of the same input)
         }
         cnt += __popcll(bal);

@@ -235,26 +235,22 @@ def occ_select(logits, sizes, dims, start, total, voxel_size, pos_thresh, rois=N
     logits, sizes, dims, start = logits.contiguous(), sizes.contiguous(), dims.contiguous(), start.contiguous()
     tiles = int(L.lib.ococc_occ_select_max_tiles(n, R))
     tile_start = L.empty((R + 1,), torch.int64, dev)
-    tile_counts = L.empty((tiles,), torch.int32, dev)
-    roi_counts = L.empty((R,), torch.int64, dev)
-    L.check(L.lib.ococc_occ_select_count(L.ptr(logits), n, L.ptr(start), R, float(pos_thresh), L.ptr(tile_start),
-                                         L.ptr(tile_counts), tiles, L.ptr(roi_counts), L.stream()), 'occ_select_count')
-    scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts  # exclusive: where a tile's cells start
-    counts = [int(v) for v in roi_counts.tolist()]                      # the one read-back
-    n_occ = sum(counts)
-    out = L.empty((n_occ, cols), torch.float32, dev)
-    cos = sin = None
-    if rois is not None:
-        rois = rois.contiguous()
-        cos, sin = torch.cos(rois[:, 7]).contiguous(), torch.sin(rois[:, 7]).contiguous()
-    if roi_values is not None:
-        roi_values = roi_values.contiguous().view(-1)
-    L.check(L.lib.ococc_occ_select_fill(L.ptr(logits), n, L.ptr(start), L.ptr(tile_start), R, float(pos_thresh),
-                                        L.ptr(scan), tiles, L.ptr(sizes), L.ptr(dims), float(voxel_size),
-                                        int(rois is not None), L.ptr(rois), rois.size(1) if rois is not None else 0,
-                                        L.ptr(cos), L.ptr(sin), L.ptr(roi_values), cols, L.ptr(out), n_occ, L.stream()),
-            'occ_select_fill')
-    return out, counts
+    pose = rois.contiguous() if rois is not None else None
+    value = roi_values.contiguous().view(-1) if roi_values is not None else None
+
+    def count(tile_counts, roi_counts):
+        L.check(L.lib.ococc_occ_select_count(L.ptr(logits), n, L.ptr(start), R, float(pos_thresh), L.ptr(tile_start),
+                                             L.ptr(tile_counts), tiles, L.ptr(roi_counts), L.stream()), 'occ_select_count')
+
+    def fill(scan, out, n_occ):
+        cos, sin = (f(pose[:, 7]).contiguous() if pose is not None else None for f in (torch.cos, torch.sin))
+        L.check(L.lib.ococc_occ_select_fill(L.ptr(logits), n, L.ptr(start), L.ptr(tile_start), R, float(pos_thresh),
+                                            L.ptr(scan), tiles, L.ptr(sizes), L.ptr(dims), float(voxel_size),
+                                            int(pose is not None), L.ptr(pose), pose.size(1) if pose is not None else 0,
+                                            L.ptr(cos), L.ptr(sin), L.ptr(value), cols, L.ptr(out), n_occ, L.stream()),
+                'occ_select_fill')
+
+    return L.count_scan_fill(tiles, R, cols, dev, count, fill)[:2]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -315,23 +311,23 @@ def occ_frame_select(logits, sizes, dims, start, total, voxel_size, pos_thresh, 
         row_keep = row_keep.contiguous().view(torch.uint8) if row_keep.dtype == torch.bool else row_keep.contiguous()
     tiles = int(L.lib.ococc_occ_select_max_tiles(n, R))
     tile_start = L.empty((R + 1,), torch.int64, dev)
-    tile_counts = L.empty((tiles,), torch.int32, dev)
-    roi_counts = L.empty((R,), torch.int64, dev)
-    L.check(L.lib.ococc_occ_frame_count(L.ptr(logits), L.ptr(seen), L.ptr(row_keep), n, L.ptr(start), R, float(pos_thresh),
-                                        L.ptr(tile_start), L.ptr(tile_counts), tiles, L.ptr(roi_counts), L.stream()),
-            'occ_frame_count')
-    scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts  # exclusive: where a tile's cells start
     cos, sin = torch.cos(rois[:, 7]).contiguous(), torch.sin(rois[:, 7]).contiguous()
-    if transforms is not None:
-        transforms = transforms.contiguous()
-    counts = [int(v) for v in roi_counts.tolist()]                      # the one read-back
-    n_out = sum(counts)
-    out = L.empty((n_out, 4), torch.float32, dev)
-    flags = L.empty((n_out,), torch.uint8, dev)
-    L.check(L.lib.ococc_occ_frame_fill(L.ptr(logits), L.ptr(seen), L.ptr(row_keep), n, L.ptr(start), L.ptr(tile_start), R,
-                                       float(pos_thresh), L.ptr(scan), tiles, L.ptr(sizes), L.ptr(dims), float(voxel_size),
-                                       L.ptr(rois), rois.size(1), L.ptr(cos), L.ptr(sin), L.ptr(transforms), L.ptr(out),
-                                       L.ptr(flags), n_out, L.stream()), 'occ_frame_fill')
+    transforms = transforms.contiguous() if transforms is not None else None
+
+    def count(tile_counts, roi_counts):
+        L.check(L.lib.ococc_occ_frame_count(L.ptr(logits), L.ptr(seen), L.ptr(row_keep), n, L.ptr(start), R,
+                                            float(pos_thresh), L.ptr(tile_start), L.ptr(tile_counts), tiles,
+                                            L.ptr(roi_counts), L.stream()), 'occ_frame_count')
+
+    def fill(scan, out, n_out):
+        flags = L.empty((n_out,), torch.uint8, dev)
+        L.check(L.lib.ococc_occ_frame_fill(L.ptr(logits), L.ptr(seen), L.ptr(row_keep), n, L.ptr(start), L.ptr(tile_start),
+                                           R, float(pos_thresh), L.ptr(scan), tiles, L.ptr(sizes), L.ptr(dims),
+                                           float(voxel_size), L.ptr(rois), rois.size(1), L.ptr(cos), L.ptr(sin),
+                                           L.ptr(transforms), L.ptr(out), L.ptr(flags), n_out, L.stream()), 'occ_frame_fill')
+        return flags
+
+    out, counts, flags = L.count_scan_fill(tiles, R, 4, dev, count, fill)
     return out, flags, counts
 
 

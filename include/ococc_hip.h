@@ -836,6 +836,37 @@ int ococc_occ_frame_fill(const float* logits, const uint8_t* observed, const uin
                          ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * observation sample of one online step (csrc/tune_sample.hip): the rows the shape latent of a step is tuned against,
+ * behind occ_ops.tune_sample and the ``tune=`` argument of OccBBoxHead.forward_step / forward_steps.  Replaces, for the
+ * step, OccAutoEncoder.sample_observation with balance_sample and its cap
+ *   (mmdet3d/models/roi_heads/bbox_heads/occ_ae_head.py:65-201: the label volume per RoI, torch.multinomial per RoI for
+ *   the free cells and again for downsample_size).
+ * The flat cell list (start [K + 1] i64, sizes, dims) is that of the exports above and observed [n] u8 is what
+ * ococc_occ_frame_mark wrote.  Random numbers are integers: mix64 the splitmix64 finaliser,
+ *   key(s, c) = high 32 bits of mix64(s + (c + 1) * 0x9E3779B97F4A7C15); cell c of a RoI with seed s = row_seeds[r]
+ *   carries key(s, c), position p of the RoI's list carries key(s ^ 0xD1B54A32D192ED03, p); every order is on
+ *   (key, index), equal keys towards the smaller index.
+ * Rows of RoI r with k cells, npos of them observed, nneg = k - npos (row_keep [K] u8, NULL: every RoI kept):
+ *   row_keep[r] == 0: none.  balance == 0: every cell, label = observed (cap must be <= 0).  npos == 0: cell 0 with
+ *   label 0.  nneg == 0: none.  npos <= nneg: the observed cells and the npos free cells of smallest (key, c).
+ *   npos > nneg > 0: the observed cells, every free cell npos / nneg times, the npos % nneg free cells of smallest
+ *   (key, c) once more.  Rows in grid order, copies adjacent; cap > 0 and more than cap rows: the cap rows of smallest
+ *   (cap key, position), still in list order.
+ * ococc_tune_sample_count writes counts [K] i32 (-1: start is no ascending table inside [0, n], or a RoI has more than
+ *   2^30 cells) and plan [K, 4] i64 (the case and the two thresholds, for fill).  ococc_tune_sample_fill, given both,
+ *   writes S = sum of the counts rows: xyz [S, 3] f32 the cell centre (bit for bit ococc_dense_grid_cells_f32),
+ *   labels [S] i32, index [S] i32 non-decreasing, weights [S] f32 = 1.0f / (float)counts[r], one rounded division.
+ * Integer atomics in LDS only; the same input gives the same bytes.  K == 0 is an empty result, not an error.
+ * ------------------------------------------------------------------------ */
+int ococc_tune_sample_count(const uint8_t* observed, int64_t n, const int64_t* start, int32_t K,
+                            const int64_t* row_seeds, const uint8_t* row_keep, int32_t balance, int32_t cap,
+                            int32_t* counts, int64_t* plan, ococc_stream_t stream);
+int ococc_tune_sample_fill(const uint8_t* observed, int64_t n, const int64_t* start, int32_t K, const float* sizes,
+                           const int32_t* dims, float voxel_size, const int64_t* row_seeds, const int32_t* counts,
+                           const int64_t* plan, float* xyz, int32_t* labels, int32_t* index, float* weights, int64_t S,
+                           ococc_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * ground-truth occupancy export (csrc/gt_occ_crop.hip): the occupied label cells of one object, moved into the LiDAR
  * frame of every frame that has a GT box and cropped to that frame's proposal box, behind bbox.crop_gt_occ_packed and
  * TrackletRoIHeadOCC.save_gt_occ_from_tracklet.  Replaces the save_gt_occ=True branch of save_occ_from_tracklet

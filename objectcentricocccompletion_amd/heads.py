@@ -561,12 +561,27 @@ class OccAutoEncoder(nn.Module, SparseHeadMixin):
         """The completed occupancy of one online step (OccDecoder.get_frame_occ): the occupied cells of get_occ_packed
         joined with the cells sample_observation labels 1 for ``local_xyz`` -- the rotated coordinates ``encode``
         returns --, as (out [n, 4], flags [n] uint8, counts per RoI)."""
-        if not self.compensate_encoder_coors:   # (sample_observation's turn: encode left the coordinates as pooled)
+        return self.occ_decoder.get_frame_occ(local_roi_feats, rois, self.voxel_size, self.scale_wlh, self.offset_wlh,
+                                              self.observation_xyz(local_xyz), pts_roi_inds, row_keep=row_keep,
+                                              transforms=transforms, observed=observed, chunk=chunk)
+
+    def observation_xyz(self, local_xyz):
+        """The coordinates ``encode`` returns in the frame the observation grids are rasterised in: sample_observation's
+        pi / 2 turn, unless compensate_encoder_coors made ``encode`` apply it already."""
+        if not self.compensate_encoder_coors:
             r = const_tensor((np.pi / 2,), local_xyz.device, local_xyz.dtype)
             local_xyz = rotation_3d_in_axis(local_xyz[None, :, :], r, axis=2).squeeze(0)
-        return self.occ_decoder.get_frame_occ(local_roi_feats, rois, self.voxel_size, self.scale_wlh, self.offset_wlh,
-                                              local_xyz, pts_roi_inds, row_keep=row_keep, transforms=transforms,
-                                              observed=observed, chunk=chunk)
+        return local_xyz
+
+    def step_sample(self, local_xyz, rois, pts_roi_inds, row_seeds, row_keep, downsample_size=-1, balance_sample=True):
+        """The observation sample of one online step (occ_ops.tune_sample, csrc/tune_sample.hip): ``local_xyz`` the
+        coordinates ``encode`` returns, ``row_seeds`` [R] int64 one seed per RoI (occ_ops.tune_row_seed), ``row_keep`` [R]
+        the RoIs that hold a pooled point.  Returns (xyz [S, 3], labels [S] int32, RoI index [S] int32, weights [S] = 1 /
+        rows of the RoI, rows per RoI as a list)."""
+        sizes, dims, start, total = occ_ops.dense_grid_layout(rois[:, 4:7], self.voxel_size, self.scale_wlh, self.offset_wlh)
+        return occ_ops.tune_sample(sizes, dims, start, total, self.voxel_size, self.observation_xyz(local_xyz), pts_roi_inds,
+                                   row_seeds, row_keep, self.scale_wlh, self.offset_wlh, balance=balance_sample,
+                                   cap=downsample_size)
 
     def get_roi_occ(self, local_roi_feats, rois, transform=True, return_score=False):
         """occ_ae_head.py:440-449."""
@@ -730,9 +745,66 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
                  % ('' if latent_tune.KERNELS else ' and OCOCC_LATENT_TUNE_KERNELS=0 turns them off'))
         return ae.online_tuning_forward(shape_latent, smp_xyz, labels, None, smp_inds, num_iter).detach()
 
+    TUNE_KEYS = ('num_iter', 'downsample_size', 'balance_sample', 'seed')
+
+    @classmethod
+    def _check_tune(cls, tune):
+        """``tune = dict(num_iter, downsample_size=-1, balance_sample=True, seed=0)`` of the steps as (num_iter, cap, balance,
+        seed), or None; what it cannot be is reported before anything is launched."""
+        if tune is None:
+            return None
+        if not isinstance(tune, dict) or set(tune) - set(cls.TUNE_KEYS) or 'num_iter' not in tune:
+            raise ValueError(f'tune= takes dict(num_iter, downsample_size=-1, balance_sample=True, seed=0); got {tune!r}')
+        num_iter, cap = int(tune['num_iter']), int(tune.get('downsample_size', -1))
+        balance, seed = bool(tune.get('balance_sample', True)), int(tune.get('seed', 0))
+        if num_iter < 0:
+            raise ValueError(f'tune=: num_iter = {num_iter}')
+        if not balance and cap > 0:
+            raise NotImplementedError('tune= with balance_sample=False and downsample_size > 0 (the weighted draw of '
+                                      'sample_observation) is not built for the steps: balance_sample=True with any '
+                                      'downsample_size, or balance_sample=False with downsample_size=-1')
+        return num_iter, cap, balance, seed
+
+    def _step_tuner(self, tune, local_xyz, rois, roi_inds, nonempty_roi_mask, slots, frames):
+        """The ``tune`` callable of _fuse_and_predict for a step call, ``tune`` as _check_tune returns it: the fused shape
+        latent of every row tuned against the row's own observation.  The sample comes from occ_ops.tune_sample (HIP kernels over the step's pooled points): row j draws
+        with the seed tune_row_seed(seed, slot_j, frame_j), so what (slot, frame) draws does not depend on the row's place
+        in the call nor on single or chunked stepping; a row that holds no point has no observation and keeps its latent.
+        The loss of every RoI is loss_weight x the MEAN BCE over the RoI's own rows (weights 1 / m_r, the call's loss_weight
+        x S: scale x weight = loss_weight / m_r).  With one RoI in the call that is the reference's loss; with several the
+        reference -- and the offline test_cfg.online_tuning -- takes the mean over all rows of the call, which makes a
+        tracklet's result depend on its company: per RoI is this package's definition for the steps.  On the kernels of
+        occ/latent_tune.py for the bf16 decoder on the device, through OccAutoEncoder.online_tuning_forward (autograd) on
+        the same sample with the same weights otherwise and with OCOCC_LATENT_TUNE_KERNELS=0."""
+        from .occ import latent_tune
+        from .tracklet import host_index
+        num_iter, cap, balance, seed = tune
+        ae = self.occ_ae_head
+        seeds = [occ_ops.tune_row_seed(seed, s, f) for s, f in zip(slots, frames)]
+
+        def run(shape_latent):
+            if num_iter == 0 or local_xyz.size(0) == 0 or shape_latent.size(0) == 0:
+                return shape_latent
+            xyz, labels, index, weights, _ = ae.step_sample(local_xyz, rois, roi_inds, host_index(seeds, rois.device),
+                                                            nonempty_roi_mask, downsample_size=cap, balance_sample=balance)
+            S = xyz.size(0)
+            if S == 0:
+                return shape_latent
+            lw = ae.loss_occ_ae.loss_weight
+            if latent_tune.supported(ae.occ_decoder, shape_latent, xyz, labels, index):
+                return latent_tune.tune_latents(ae.occ_decoder, shape_latent, xyz, labels, index, num_iter, weights=weights,
+                                                loss_weight=lw * S).to(shape_latent.dtype)
+            log_once(('latent-tune-step', latent_tune.KERNELS, shape_latent.is_cuda, ae.occ_decoder.compute_dtype),
+                     'OccBBoxHead step tuning: the tuning kernels take the bf16 occupancy decoder (60 -> 512 -> 1024 -> 1024 '
+                     '-> 1) on a ROCm device%s; tuning through autograd (OccAutoEncoder.online_tuning_forward)'
+                     % ('' if latent_tune.KERNELS else ' and OCOCC_LATENT_TUNE_KERNELS=0 turns them off'))
+            return ae.online_tuning_forward(shape_latent, xyz, labels.long(), weights * S, index.long(), num_iter).detach()
+
+        return run
+
     def _fuse_and_predict(self, local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask, tune=None):
         """The per-RoI stages behind the temporal transformer: shape latent by ``fused_mode`` (tuned by ``tune`` when given:
-        test_cfg.online_tuning), then score and box deltas."""
+        test_cfg.online_tuning, or the ``tune=`` argument of the steps), then score and box deltas."""
         if self.fused_mode == 'residual':
             shape_latent = local_roi_feats + self.conv_latent(roi_feats_fused)
         elif self.fused_mode == 'concat':
@@ -768,7 +840,8 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
         return self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask, tune)
 
     @torch.no_grad()
-    def forward_step(self, pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds, slot, cache, return_points=False):
+    def forward_step(self, pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds, slot, cache, return_points=False,
+                     tune=None):
         """``forward`` for ONE new frame of each of n tracklets that arrive frame by frame: rois [n, 8] (column 0 the row's
         own index), roi_frame_inds [n] the frame number of each (= the frames its slot has been stepped through), ``slot``
         the list of the rows' cache slots, ``cache`` the TemporalCache of ``trans_enc`` (occ/layers.py).  Every stage but
@@ -776,34 +849,43 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
         the cached ones (TransformerEncoder.step), which under the causal mask of ``get_future_mask`` -- windowed by
         test_cfg.attn_window_size as there -- is row t of the full pass over frames 0..t.  Returns the dict of ``forward``
         for the n new RoIs.  test_cfg.allow_attn_future makes the model non-causal: ValueError; test_cfg.online_tuning
-        (test-time tuning of the latent) is not built for single steps: NotImplementedError.  ``return_points`` adds two
-        keys, ``local_xyz`` [M, 3] and ``roi_inds`` [M]: the pooled points in their boxes' frames as the occupancy
-        auto-encoder saw them, the input of get_frame_occ."""
+        (the offline test-time tuning of the latent) keeps its offline meaning: NotImplementedError.  ``return_points``
+        adds two keys, ``local_xyz`` [M, 3] and ``roi_inds`` [M]: the pooled points in their boxes' frames as the occupancy
+        auto-encoder saw them, the input of get_frame_occ.  ``tune = dict(num_iter, downsample_size=-1,
+        balance_sample=True, seed=0)`` tunes the fused shape latent of every row against the row's own observation
+        (_step_tuner: the sample drawn on HIP kernels, the loss a per-RoI mean); ``fused_roi_feats``, ``cls_score`` and
+        ``bbox_pred`` are then those of the tuned latent, while ``ori_roi_feats`` and the temporal cache -- K and V come from
+        the SIR features, before the fuse -- are bit for bit those of an untuned step.  None: nothing is launched for it."""
         if self.training:
             raise RuntimeError('OccBBoxHead.forward_step is inference only: call .eval() first')
         if self.test_cfg.get('allow_attn_future', False):
             raise ValueError('test_cfg.allow_attn_future lets a frame attend to later frames: such a model cannot run '
                              'frame by frame')
         if self.test_cfg.get('online_tuning', False):
-            raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference')
+            raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference: pass `tune=` to the step')
+        tune = self._check_tune(tune)
+        frames = [cache.pos_host[int(s)] for s in slot] if tune is not None else None   # (before the step bumps them)
         final_cluster_feats, nonempty_roi_mask, local_roi_feats, local_xyz = self._encode_rois(
             pts_xyz, pts_features, pts_info, roi_inds, rois)
         pos_embed = self._pos_embed(roi_frame_inds, rois[:, 1:])
         roi_feats_fused = self.trans_enc.step(final_cluster_feats, pos_embed, slot, cache,
                                               self.test_cfg.get('attn_window_size', -1))
-        ret = self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
+        if tune is not None:
+            tune = self._step_tuner(tune, local_xyz, rois, roi_inds, nonempty_roi_mask, [int(s) for s in slot], frames)
+        ret = self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask, tune)
         if return_points:   # (what get_frame_occ rasterises: the auto-encoder's box-frame points and their rows)
             ret.update(local_xyz=local_xyz, roi_inds=roi_inds)
         return ret
 
     @torch.no_grad()
-    def forward_steps(self, pts_xyz, pts_features, pts_info, roi_inds, rois, slot_rows, cache, return_points=False):
+    def forward_steps(self, pts_xyz, pts_features, pts_info, roi_inds, rois, slot_rows, cache, return_points=False, tune=None):
         """``forward_step`` for one OR MORE new frames per tracklet in one call: ``slot_rows`` is the slot of every row
         and may repeat -- the rows of a slot are its new frames, consecutive and in frame order (TemporalCache.check_steps)
         -- and the frame index of row j of the run of slot s is cache.pos_host[s] + j.  The temporal transformer runs
         TransformerEncoder.steps (one attention launch per layer for all rows); everything else works per RoI.  The
-        refusals are those of ``forward_step``, and so is ``return_points``.  Returns the dict of ``forward`` for the n rows,
-        in input order."""
+        refusals are those of ``forward_step``, and so are ``return_points`` and ``tune`` (a row draws the sample of its
+        (slot, frame), as the single step of that frame does).  Returns the dict of ``forward`` for the n rows, in input
+        order."""
         from .tracklet import host_index
         if self.training:
             raise RuntimeError('OccBBoxHead.forward_steps is inference only: call .eval() first')
@@ -811,15 +893,19 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
             raise ValueError('test_cfg.allow_attn_future lets a frame attend to later frames: such a model cannot run '
                              'frame by frame')
         if self.test_cfg.get('online_tuning', False):
-            raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference')
+            raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference: pass `tune=` to the step')
+        tune = self._check_tune(tune)
         slots, offsets, _ = cache.check_steps(slot_rows)
-        roi_frame_inds = host_index([cache.pos_host[s] + j for s, j in zip(slots, offsets)], rois.device)
+        frames = [cache.pos_host[s] + j for s, j in zip(slots, offsets)]
+        roi_frame_inds = host_index(frames, rois.device)
         final_cluster_feats, nonempty_roi_mask, local_roi_feats, local_xyz = self._encode_rois(
             pts_xyz, pts_features, pts_info, roi_inds, rois)
         pos_embed = self._pos_embed(roi_frame_inds, rois[:, 1:])
         roi_feats_fused = self.trans_enc.steps(final_cluster_feats, pos_embed, slots, cache,
                                                self.test_cfg.get('attn_window_size', -1))
-        ret = self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask)
+        if tune is not None:
+            tune = self._step_tuner(tune, local_xyz, rois, roi_inds, nonempty_roi_mask, slots, frames)
+        ret = self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask, tune)
         if return_points:
             ret.update(local_xyz=local_xyz, roi_inds=roi_inds)
         return ret

@@ -1,6 +1,8 @@
 """Host mirror of mmdet3d/ops/occ/occ_ops.py: voxel-centre helpers of the implicit
 occupancy grid (generate_dense_voxel_centers :5-50, quantize_points :53-93,
 jitter_voxel_center :96-100).  Elementwise index math on small tensors."""
+import os
+
 import torch
 
 from .._lib import const_tensor
@@ -331,6 +333,23 @@ def occ_frame_select(logits, sizes, dims, start, total, voxel_size, pos_thresh, 
     return out, flags, counts
 
 
+def _observed_aten(size, dims, start, total, voxel_size, local_xyz, pts_roi):
+    """observed [total] bool of the flat cell list, the mark kernel of csrc/occ_frame.hip as an operator chain: ``size``
+    [R, 3] the enlarged sizes, ``local_xyz`` [M, 3] the pooled points in the box frame, ``pts_roi`` [M] their RoI."""
+    dev = local_xyz.device
+    seen = torch.zeros(int(total), dtype=torch.bool, device=dev)
+    idx = pts_roi.long()
+    # quantize_points' expression with the voxel as a TENSOR divisor: on a device ATen divides by a host scalar through
+    # its reciprocal, which moves a point that sits on a cell face (2.0 / 0.2f is 10, 2.0 * (1 / 0.2f) is 9.9999998);
+    # tensor / tensor is a true division everywhere, as on the host and in the mark kernel
+    coors = torch.floor((local_xyz - (-size / 2)[idx]) / const_tensor((voxel_size,), dev)).to(torch.long)
+    d = dims.long()[idx]
+    valid = ((coors < d) & (coors >= 0)).all(dim=1)
+    flat = start[idx] + (coors[:, 0] * d[:, 1] + coors[:, 1]) * d[:, 2] + coors[:, 2]
+    seen[flat[valid]] = True
+    return seen
+
+
 def occ_frame_select_aten(logits, sizes, dims, start, total, voxel_size, pos_thresh, rois, local_xyz, pts_roi,
                           scale_wlh=[1.0, 1.0, 1.0], offset_wlh=[0.0, 0.0, 0.0], row_keep=None, transforms=None,
                           observed=True):
@@ -354,16 +373,8 @@ def occ_frame_select_aten(logits, sizes, dims, start, total, voxel_size, pos_thr
         pred = prob > pos_thresh
     seen = torch.zeros(int(total), dtype=torch.bool, device=dev)
     if observed and M:
-        idx = pts_roi.long()
-        # quantize_points' expression with the voxel as a TENSOR divisor: on a device ATen divides by a host scalar through
-        # its reciprocal, which moves a point that sits on a cell face (2.0 / 0.2f is 10, 2.0 * (1 / 0.2f) is 9.9999998);
-        # tensor / tensor is a true division everywhere, as on the host and in the mark kernel
         size = rois[:, 4:7] * const_tensor(scale_wlh, dev).view(1, 3) + const_tensor(offset_wlh, dev).view(1, 3)
-        coors = torch.floor((local_xyz - (-size / 2)[idx]) / const_tensor((voxel_size,), dev)).to(torch.long)
-        d = dims.long()[idx]
-        valid = ((coors < d) & (coors >= 0)).all(dim=1)
-        flat = start[idx] + (coors[:, 0] * d[:, 1] + coors[:, 1]) * d[:, 2] + coors[:, 2]
-        seen[flat[valid]] = True
+        seen = _observed_aten(size, dims, start, total, voxel_size, local_xyz, pts_roi)
     sel = pred | seen
     if row_keep is not None:
         sel = sel & (row_keep != 0)[box]
@@ -375,3 +386,197 @@ def occ_frame_select_aten(logits, sizes, dims, start, total, voxel_size, pos_thr
     out = torch.cat([pts, prob[sel].view(-1, 1)], 1)
     flags = pred[sel].to(torch.uint8) | (seen[sel].to(torch.uint8) << 1)
     return out, flags, torch.bincount(pbox, minlength=R).tolist()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# observation sample of a tuned online step (csrc/tune_sample.hip)
+# 0: tune_sample runs the operator chain tune_sample_aten instead of the kernels
+TUNE_SAMPLE_KERNEL = os.environ.get('OCOCC_TUNE_SAMPLE_KERNEL', '1') != '0'
+
+_M64 = (1 << 64) - 1
+TUNE_GOLDEN, TUNE_CAP_SALT = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03   # csrc/tune_rng.hpp
+
+
+def _i64(v):
+    """the 64-bit pattern ``v`` as the Python int an int64 tensor holds"""
+    v &= _M64
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def mix64_int(x):
+    """The splitmix64 finaliser of one Python int (csrc/tune_rng.hpp), as an unsigned 64-bit value."""
+    x &= _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def tune_row_seed(seed, slot, frame):
+    """The seed of the sample of frame ``frame`` of cache slot ``slot``: mix64(seed ^ (slot << 32 | frame)) as the signed
+    value an int64 tensor holds.  A function of (seed, slot, frame) alone: the draw does not depend on the row's place in
+    the call."""
+    return _i64(mix64_int((int(seed) & _M64) ^ (((int(slot) << 32) | int(frame)) & _M64)))
+
+
+def _lsr(x, n):
+    """logical right shift of an int64 tensor"""
+    return (x >> n) & ((1 << (64 - n)) - 1)
+
+
+def _tune_key(seed, c):
+    """key(seed, c) of csrc/tune_rng.hpp on int64 tensors (two's-complement products wrap as the u64 ones do): values
+    in [0, 2^32)."""
+    x = seed + (c + 1) * _i64(TUNE_GOLDEN)
+    x = (x ^ _lsr(x, 30)) * _i64(0xBF58476D1CE4E5B9)
+    x = (x ^ _lsr(x, 27)) * _i64(0x94D049BB133111EB)
+    return _lsr(x ^ _lsr(x, 31), 32)
+
+
+def _rank_in_group(group, key, group_start):
+    """rank of every element among the elements of its group by (key, position); ``group`` ascending, key < 2^32"""
+    order = torch.argsort((group << 32) | key, stable=True)
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(order.numel(), device=order.device)
+    return rank - group_start[group]
+
+
+def _tune_sample_shapes(L, what, sizes, dims, start, total, local_xyz, pts_roi, row_seeds, row_keep, balance, cap):
+    """(K, M) of the inputs of tune_sample / tune_sample_aten, or OcoccError."""
+    K = _check_layout(L, what, sizes, dims, start)
+    if local_xyz is None or pts_roi is None or local_xyz.dtype != torch.float32 or local_xyz.dim() != 2 \
+            or local_xyz.size(1) != 3 or pts_roi.dtype not in (torch.int32, torch.int64) \
+            or tuple(pts_roi.shape) != (local_xyz.size(0),):
+        raise L.OcoccError(f'{what}: local_xyz is f32 [M, 3] and pts_roi int32 (or int64) [M]')
+    if row_seeds is None or row_seeds.dtype != torch.int64 or tuple(row_seeds.shape) != (K,):
+        raise L.OcoccError(f'{what}: row_seeds is int64 [{K}]')
+    if row_keep is not None and (row_keep.dtype not in (torch.uint8, torch.bool) or tuple(row_keep.shape) != (K,)):
+        raise L.OcoccError(f'{what}: row_keep is uint8 (or bool) [{K}]')
+    if int(total) < 0:
+        raise L.OcoccError(f'{what}: a layout of {int(total)} cells')
+    if not balance and int(cap) > 0:
+        raise L.OcoccError(f'{what}: cap > 0 with balance == 0: the weighted draw is not built (balance=True with a cap, '
+                           'or balance=False without one)')
+    return K, local_xyz.size(0)
+
+
+def tune_sample(sizes, dims, start, total, voxel_size, local_xyz, pts_roi, row_seeds, row_keep=None,
+                scale_wlh=[1.0, 1.0, 1.0], offset_wlh=[0.0, 0.0, 0.0], balance=True, cap=-1):
+    """The observation sample one online step tunes its shape latents against, from the flat cell list of
+    dense_grid_layout (``sizes`` are its enlarged sizes: scale_wlh and offset_wlh are already in them and are taken for
+    the symmetry with occ_frame_select only) and the step's pooled points ``local_xyz`` [M, 3] (box frame, after the
+    turn of sample_observation), ``pts_roi`` [M].  Per RoI r with k cells, npos of them hit by a point, nneg = k - npos:
+
+        row_keep[r] == 0             no rows (no pooled point: no observation, no tuning)
+        balance False                every cell in grid order, label = observed (cap must be <= 0)
+        npos == 0                    cell 0 with label 0            nneg == 0      no rows
+        npos <= nneg                 the observed cells and the npos free cells of smallest (key, cell)
+        npos > nneg > 0              the observed cells, every free cell npos // nneg times and the npos % nneg free
+                                     cells of smallest (key, cell) once more (stratified: the reference draws npos times
+                                     with replacement)
+
+    in grid order, copies adjacent; more than ``cap`` > 0 rows: the cap rows of smallest (cap key, list position).  The
+    keys are the integers of csrc/tune_rng.hpp from ``row_seeds`` [K] int64 (tune_row_seed).  Returns (xyz [S, 3] f32 the
+    cell centres, bit for bit dense_grid_cells'; labels [S] int32; index [S] int32, non-decreasing; weights [S] f32 =
+    1 / rows of the RoI; counts per RoI as a list of int).  One memset and one mark launch (ococc_occ_frame_mark), one
+    count launch, one read-back of the counts, one fill launch (csrc/tune_sample.hip).  ``tune_sample_aten`` is the same
+    result, bit for bit, as a torch operator chain: what OCOCC_TUNE_SAMPLE_KERNEL=0 runs."""
+    from .. import _lib as L
+    K, M = _tune_sample_shapes(L, 'tune_sample', sizes, dims, start, total, local_xyz, pts_roi, row_seeds, row_keep,
+                               balance, cap)
+    if not TUNE_SAMPLE_KERNEL:
+        return tune_sample_aten(sizes, dims, start, total, voxel_size, local_xyz, pts_roi, row_seeds, row_keep,
+                                scale_wlh, offset_wlh, balance, cap)
+    L.require_device(sizes, dims, start, local_xyz, pts_roi, row_seeds, row_keep)
+    dev = sizes.device
+    n = int(total)
+    if K == 0:
+        return (L.empty((0, 3), torch.float32, dev), L.empty((0,), torch.int32, dev), L.empty((0,), torch.int32, dev),
+                L.empty((0,), torch.float32, dev), [])
+    sizes, dims, start, row_seeds = sizes.contiguous(), dims.contiguous(), start.contiguous(), row_seeds.contiguous()
+    seen = L.empty((n,), torch.uint8, dev)
+    L.check(L.lib.ococc_occ_frame_mark(L.ptr(local_xyz.contiguous()), L.ptr(pts_roi.to(torch.int32).contiguous()), M,
+                                       L.ptr(sizes), L.ptr(dims), L.ptr(start), K, float(voxel_size), L.ptr(seen), n,
+                                       L.stream()), 'occ_frame_mark')
+    if row_keep is not None:
+        row_keep = row_keep.contiguous().view(torch.uint8) if row_keep.dtype == torch.bool else row_keep.contiguous()
+    counts = L.empty((K,), torch.int32, dev)
+    plan = L.empty((K, 4), torch.int64, dev)
+    L.check(L.lib.ococc_tune_sample_count(L.ptr(seen), n, L.ptr(start), K, L.ptr(row_seeds), L.ptr(row_keep), int(bool(balance)),
+                                          int(cap), L.ptr(counts), L.ptr(plan), L.stream()), 'tune_sample_count')
+    host = counts.tolist()   # the one read-back
+    if min(host) < 0:
+        raise L.OcoccError(f'tune_sample: start is not the ascending prefix table of a layout of {n} cells (or a RoI '
+                           f'holds more than 2^30 cells): RoI {host.index(min(host))}')
+    S = sum(host)
+    xyz, labels = L.empty((S, 3), torch.float32, dev), L.empty((S,), torch.int32, dev)
+    index, weights = L.empty((S,), torch.int32, dev), L.empty((S,), torch.float32, dev)
+    L.check(L.lib.ococc_tune_sample_fill(L.ptr(seen), n, L.ptr(start), K, L.ptr(sizes), L.ptr(dims), float(voxel_size),
+                                         L.ptr(row_seeds), L.ptr(counts), L.ptr(plan), L.ptr(xyz), L.ptr(labels),
+                                         L.ptr(index), L.ptr(weights), S, L.stream()), 'tune_sample_fill')
+    return xyz, labels, index, weights, host
+
+
+def tune_sample_aten(sizes, dims, start, total, voxel_size, local_xyz, pts_roi, row_seeds, row_keep=None,
+                     scale_wlh=[1.0, 1.0, 1.0], offset_wlh=[0.0, 0.0, 0.0], balance=True, cap=-1):
+    """``tune_sample`` as an operator chain on any device, bit for bit: the keys through int64 arithmetic, the orders
+    through stable argsorts of (RoI << 32 | key), the copies through repeat_interleave.  What the CPU tests run, what
+    OCOCC_TUNE_SAMPLE_KERNEL=0 selects and what the kernels are timed against."""
+    from .. import _lib as L
+    K, M = _tune_sample_shapes(L, 'tune_sample_aten', sizes, dims, start, total, local_xyz, pts_roi, row_seeds, row_keep,
+                               balance, cap)
+    dev = sizes.device
+    n, cap = int(total), int(cap)
+    i32, i64 = torch.int32, torch.long
+    if K == 0:
+        return (sizes.new_zeros((0, 3)), torch.zeros((0,), dtype=i32, device=dev), torch.zeros((0,), dtype=i32, device=dev),
+                sizes.new_zeros((0,)), [])
+    k = start[1:] - start[:-1]
+    if int(start[0]) != 0 or int(start[-1]) != n or bool((k < 0).any()):
+        raise L.OcoccError(f'tune_sample_aten: start is not the ascending prefix table of a layout of {n} cells')
+    roi = torch.arange(K, device=dev)
+    box = torch.repeat_interleave(roi, k, output_size=n)
+    local = torch.arange(n, device=dev) - start[box]
+    if M:
+        seen = _observed_aten(sizes, dims, start, n, voxel_size, local_xyz, pts_roi)
+    else:
+        seen = torch.zeros(n, dtype=torch.bool, device=dev)
+    keep = torch.ones(K, dtype=torch.bool, device=dev) if row_keep is None else row_keep != 0
+    zeros = lambda: torch.zeros(K, dtype=i64, device=dev)
+    if not balance:
+        mult = keep[box].to(i64)
+    else:
+        npos = zeros().index_add_(0, box, seen.to(i64))
+        nneg = k - npos
+        drawn = keep & (npos > 0) & (nneg > 0)
+        small = npos <= nneg
+        div = nneg.clamp_min(1)
+        q = torch.where(small, npos, npos % div)
+        rep = torch.where(small, torch.zeros_like(npos), npos // div)
+        mult = (seen & drawn[box]).to(i64)
+        fi = torch.nonzero(~seen & drawn[box]).squeeze(1)     # the free cells of the RoIs that draw, in cell order
+        fb = box[fi]
+        nfree = torch.where(drawn, nneg, torch.zeros_like(nneg))
+        rank = _rank_in_group(fb, _tune_key(row_seeds[fb], local[fi]), torch.cumsum(nfree, 0) - nfree)
+        mult[fi] = rep[fb] + (rank < q[fb]).to(i64)
+        first = keep & (npos == 0) & (k > 0)
+        mult[start[:-1][first]] = 1
+    rows = torch.repeat_interleave(torch.arange(n, device=dev), mult)
+    rbox = box[rows]
+    cnt = zeros().index_add_(0, rbox, torch.ones_like(rbox))
+    if cap > 0:
+        over = cnt > cap
+        pos = torch.arange(rows.numel(), device=dev) - (torch.cumsum(cnt, 0) - cnt)[rbox]
+        ci = torch.nonzero(over[rbox]).squeeze(1)
+        cb = rbox[ci]
+        ncap = torch.where(over, cnt, torch.zeros_like(cnt))
+        rank = _rank_in_group(cb, _tune_key(row_seeds[cb] ^ _i64(TUNE_CAP_SALT), pos[ci]), torch.cumsum(ncap, 0) - ncap)
+        kept = torch.ones(rows.numel(), dtype=torch.bool, device=dev)
+        kept[ci] = rank < cap
+        rows, rbox = rows[kept], rbox[kept]
+        cnt = cnt.clamp_max(cap)
+    d = dims.long()[rbox]
+    loc = local[rows]
+    coors = torch.stack([loc // (d[:, 1] * d[:, 2]), (loc // d[:, 2]) % d[:, 1], loc % d[:, 2]], 1)
+    xyz = coors.to(torch.float) * voxel_size + (-sizes / 2)[rbox] + voxel_size / 2   # dense_voxel_centers_batched's
+    weights = (torch.ones(K, dtype=torch.float32, device=dev) / cnt.to(torch.float32))[rbox]
+    return xyz, seen[rows].to(i32), rbox.to(i32), weights, cnt.tolist()

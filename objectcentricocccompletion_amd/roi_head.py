@@ -418,7 +418,7 @@ class TrackletRoIHeadOCC(nn.Module):
 
     @torch.no_grad()
     def simple_test_step(self, pts_xyz, pts_feats, pts_batch_idx, boxes, scores, labels, slot, state, gt_rois=None,
-                         occ=False, occ_transforms=None):
+                         occ=False, occ_transforms=None, tune=None):
         """One new frame of n tracklets: the frame's points (pts_batch_idx: the ROW 0..n-1 a point belongs to), the
         proposal boxes [n, 7], scores [n] and labels [n] of this frame, ``slot`` the list of the rows' slots in ``state``
         (online_begin).  Pools the frame's points into the frame's boxes, appends the RoI score / corner offsets as
@@ -435,6 +435,11 @@ class TrackletRoIHeadOCC(nn.Module):
         INPUT box, which the latent is relative to (as save_occ_from_tracklet takes the proposal RoIs).
         test_cfg.filter_empty_roi empties the rows whose box held no point; test_cfg.online_occ = dict(observed=True,
         chunk=1 << 20) turns the observed cells off or sets the decode's chunk.  Without ``occ`` nothing of this is launched.
+
+        ``tune = dict(num_iter, downsample_size=-1, balance_sample=True, seed=0)`` (default: test_cfg.online_step_tuning, a
+        key of this package, absent by default) tunes the fused shape latent of every row against the row's own points
+        before score, box and occupancy are taken from it (OccBBoxHead.forward_step): ``fused_roi_feats`` is the
+        tuned latent and ``occ`` is decoded from it; the temporal cache and ``ori_roi_feats`` are those of an untuned step.
 
         ALL frames of a tracklet must be given in ONE fixed coordinate frame: the encoders see absolute coordinates, so the
         cached keys and values belong to the frame they were computed in.  (The offline pipeline moves a tracklet into the
@@ -460,7 +465,7 @@ class TrackletRoIHeadOCC(nn.Module):
         pooled = self._pool_points(pts_xyz, pts_feats, pts_batch_idx.long(), torch.zeros_like(pts_batch_idx, dtype=torch.long),
                                    rois, scores, same)
         occ_cfg = self.online_occ_cfg() if occ else None               # (a wrong test_cfg.online_occ: before any launch)
-        res = self.bbox_head.forward_step(*pooled, rois, frames, slots, state.cache, **({'return_points': True} if occ else {}))
+        res = self.bbox_head.forward_step(*pooled, rois, frames, slots, state.cache, **self._step_kwargs(occ, tune))
         one = torch.cat([torch.zeros_like(rois[:, :1]), rois[:, 1:]], 1)   # (one group: get_bboxes splits by column 0)
         out_boxes, out_scores, out_labels, valid = self.bbox_head.get_bboxes_from_tracklet(
             one, res['cls_score'], res['bbox_pred'], res['nonempty_roi_mask'], labels, scores, None, gt_rois=gt_rois,
@@ -473,7 +478,7 @@ class TrackletRoIHeadOCC(nn.Module):
 
     @torch.no_grad()
     def simple_test_steps(self, pts_xyz, pts_feats, pts_row_idx, boxes, scores, labels, slot_rows, state, gt_rois=None,
-                          occ=False):
+                          occ=False, tune=None):
         """``simple_test_step`` for one OR MORE new frames per tracklet in one call -- a tracklet that arrives with
         history (a track confirmed after several hits, a dropped batch), or a recorded one fed T frames at a time.  A row
         is one (tracklet, frame): ``pts_row_idx`` the ROW 0..n-1 a point belongs to, boxes [n, 7], scores [n], labels [n]
@@ -482,7 +487,8 @@ class TrackletRoIHeadOCC(nn.Module):
         continue where its earlier steps stopped.  Pooling, decode and the returned dict are those of simple_test_step,
         n rows in input order; the temporal transformer takes all rows in one launch per layer
         (OccBBoxHead.forward_steps).  The coordinate-frame rule of simple_test_step holds, and ``occ=True`` adds its three
-        keys ``occ``, ``occ_flags`` and ``occ_counts`` for the n rows.
+        keys ``occ``, ``occ_flags`` and ``occ_counts`` for the n rows; ``tune`` is that of simple_test_step, and a row draws
+        the sample the single step of its (slot, frame) draws.
 
         Reported on the host before anything is launched: slots out of range, rows of a slot that are not consecutive, a
         run past the cache's cap (OcoccError), CPU tensors (OcoccError), training mode (RuntimeError)."""
@@ -502,7 +508,7 @@ class TrackletRoIHeadOCC(nn.Module):
         pooled = self._pool_points(pts_xyz, pts_feats, pts_row_idx.long(), torch.zeros_like(pts_row_idx, dtype=torch.long),
                                    rois, scores, same)
         occ_cfg = self.online_occ_cfg() if occ else None
-        res = self.bbox_head.forward_steps(*pooled, rois, slots, state.cache, **({'return_points': True} if occ else {}))
+        res = self.bbox_head.forward_steps(*pooled, rois, slots, state.cache, **self._step_kwargs(occ, tune))
         one = torch.cat([torch.zeros_like(rois[:, :1]), rois[:, 1:]], 1)   # (one group: get_bboxes splits by column 0)
         out_boxes, out_scores, out_labels, valid = self.bbox_head.get_bboxes_from_tracklet(
             one, res['cls_score'], res['bbox_pred'], res['nonempty_roi_mask'], labels, scores, None, gt_rois=gt_rois,
@@ -512,6 +518,16 @@ class TrackletRoIHeadOCC(nn.Module):
         if occ:
             out.update(self._step_occ(res, rois, occ_cfg))
         return out
+
+    def _step_kwargs(self, occ, tune):
+        """What a step adds to the head's call: the pooled points back for ``occ``, and the tuning of the latent -- the
+        ``tune`` argument, or test_cfg.online_step_tuning when that is None.  Neither: nothing, the call of a plain step."""
+        if tune is None:
+            tune = self.test_cfg.get('online_step_tuning', None)
+        kw = {'return_points': True} if occ else {}
+        if tune is not None:
+            kw['tune'] = tune
+        return kw
 
     def online_occ_cfg(self):
         """test_cfg.online_occ: an optional dict, ``observed`` (default True: the cells the frame's points fell into join
@@ -551,7 +567,7 @@ class TrackletRoIHeadOCC(nn.Module):
         return torch.cat([centre, b[:, 3:6], torch.atan2(t[:, 0], t[:, 1])[:, None]], 1).to(boxes.dtype)
 
     @torch.no_grad()
-    def simple_test_scene_step(self, points, pose, boxes, scores, labels, slot, state, gt_rois=None, occ=False):
+    def simple_test_scene_step(self, points, pose, boxes, scores, labels, slot, state, gt_rois=None, occ=False, tune=None):
         """simple_test_step from what a sensor frame brings: ``points`` [N, >= 3 + attr] f32, the scene cloud of the frame in
         its own ego frame; ``pose``, the 4x4 ego -> world of the frame (numpy or torch); ``boxes`` [n, 7], ``scores`` [n],
         ``labels`` [n], the tracker's output for the frame in the same ego frame; ``slot`` and ``state`` as in
@@ -570,7 +586,8 @@ class TrackletRoIHeadOCC(nn.Module):
         refined boxes back in the frame's ego frame through inverse(M_i), rows with valid == False their input box bit for
         bit; ``num_points`` [n] i64 on the host, the points in each enlarged box before the cap.  ``occ=True`` adds
         ``occ_ego`` [N, 4], the rows of simple_test_step's ``occ`` in the frame's ego frame -- through float32(inverse(M_i)),
-        the matrix ``boxes_ego`` uses, applied in the fill kernel --, ``occ_flags`` and ``occ_counts``.
+        the matrix ``boxes_ego`` uses, applied in the fill kernel --, ``occ_flags`` and ``occ_counts``.  ``tune`` is that of
+        simple_test_step.
 
         Reported on the host before anything is launched: what simple_test_step reports, a pose that is not 4x4 or not
         finite (OcoccError), a slot in mid-tracklet without an origin -- it was stepped through simple_test_step
@@ -617,10 +634,10 @@ class TrackletRoIHeadOCC(nn.Module):
             point_cloud_range=cfg['point_cloud_range'], max_points=cfg['max_points'], deco_boxes=fixed_boxes)
         if occ:
             out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois,
-                                        occ=True, occ_transforms=mats[1].float())
+                                        occ=True, occ_transforms=mats[1].float(), tune=tune)
             out['occ_ego'] = out.pop('occ')
         else:
-            out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois)
+            out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois, tune=tune)
         out['boxes_ego'] = torch.where(out['valid'].to(dev).bool()[:, None], self._boxes_through(out['boxes'], mats[1]),
                                        boxes[:, :7])
         out['num_points'] = counts

@@ -4,7 +4,7 @@
 clouds) stepped through frame by frame, the way the method is deployed -- no track-input database, no per-tracklet files:
 
     python tools/online_raw.py <config> <checkpoint> <raw.yaml> [--slots 64] [--out FILE.bin] [--poses poses.pkl]
-                               [--save-occ DIR] [--cfg-options k=v ...]
+                               [--save-occ DIR] [--step-tuning N [--step-tuning-samples S]] [--cfg-options k=v ...]
 
 Per segment and frame, in time order: the frame's scene cloud is loaded once, every track that starts at the frame gets a
 free slot of the temporal K/V cache, TrackletRoIHeadOCC.simple_test_scene_step refines all live tracks in one call (crop,
@@ -160,10 +160,20 @@ def parse_args(argv=None):
     ap.add_argument('--save-occ', metavar='DIR', default=None,
                     help='write the completed occupancy of every frame and object below DIR: <segment>/<timestamp>/<type>_<id>.bin, '
                     'float32 [n, 4] in the frame\'s ego frame, the refined score in column 3 (occ_export.load_frame_occ reads it)')
+    ap.add_argument('--step-tuning', type=int, metavar='N', default=None,
+                    help='tune the fused shape latent of every live track against the frame\'s own points with N Adam steps '
+                    'inside the step (sets test_cfg.online_step_tuning = dict(num_iter=N, downsample_size=S, '
+                    'balance_sample=True, seed=0); boxes, scores and --save-occ files then come from the tuned latent)')
+    ap.add_argument('--step-tuning-samples', type=int, metavar='S', default=None,
+                    help='at most S sampled cells per RoI under --step-tuning (default -1: no limit)')
     ap.add_argument('--cfg-options', nargs='+', default=[], help='k=v overrides merged into the config')
     args = ap.parse_args(argv)
     if args.slots < 1:
         ap.error('--slots takes a number of tracks >= 1')
+    if args.step_tuning is not None and args.step_tuning < 0:
+        ap.error('--step-tuning takes a number of iterations >= 0')
+    if args.step_tuning_samples is not None and args.step_tuning is None:
+        ap.error('--step-tuning-samples goes with --step-tuning')
     return args
 
 
@@ -179,6 +189,10 @@ def main(argv=None):
     spec.loader.exec_module(tool)
     cfg = config.fromfile(args.config)
     config.merge_from_dict(cfg, tool.parse_kv(args.cfg_options))
+    if args.step_tuning is not None:
+        config.merge_from_dict(cfg, {'model.test_cfg.online_step_tuning': dict(
+            num_iter=args.step_tuning, downsample_size=-1 if args.step_tuning_samples is None else args.step_tuning_samples,
+            balance_sample=True, seed=0)})
     dev = torch.device('cuda', torch.cuda.current_device())
     model = DETECTORS.build(cfg['model']).to(dev)
     ck = torch.load(args.checkpoint, map_location=dev)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Test / evaluation entry point with the CLI of the reference's tools/test.py (:23-87):
     python tools/test.py <config> <checkpoint> [--out FILE.pkl] [--save-occ DIR] [--save-gt-occ DIR] [--online [--online-chunk T]] [--eval iou waymo waymo_native] [--matcher {score_first,hungarian}] [--format-only]
-                         [--online-tuning N [--tuning-samples S]] [--decoder-dtype {f32,bf16}]
+                         [--online-tuning N [--tuning-samples S]] [--step-tuning N [--step-tuning-samples S]]
+                         [--decoder-dtype {f32,bf16}]
                          [--eval-options k=v ...] [--cfg-options k=v ...] [--launcher {none,pytorch}]
                          [--tmpdir DIR] [--gpu-collect] [--local_rank N]
 The test dataset is the config's data.test (the reference's data/waymo layout); with --data-root DIR it reads the tree
@@ -80,6 +81,12 @@ def parse_args(argv=None):
                     'heads read it (sets test_cfg.online_tuning = dict(num_iter=N, downsample_size=S, balance_sample=True))')
     ap.add_argument('--tuning-samples', type=int, metavar='S', default=None,
                     help='at most S sampled cells per RoI under --online-tuning (default -1: no limit)')
+    ap.add_argument('--step-tuning', type=int, metavar='N', default=None,
+                    help='with --online: tune the fused shape latent of every frame against the frame\'s own points with N '
+                    'Adam steps inside the step, the sample drawn on HIP kernels and the loss a mean per RoI (sets '
+                    'test_cfg.online_step_tuning = dict(num_iter=N, downsample_size=S, balance_sample=True, seed=0))')
+    ap.add_argument('--step-tuning-samples', type=int, metavar='S', default=None,
+                    help='at most S sampled cells per RoI under --step-tuning (default -1: no limit)')
     ap.add_argument('--decoder-dtype', choices=('f32', 'bf16'), default='f32',
                     help='compute dtype of the occupancy decoder (bf16: the fused decoder and tuning kernels)')
     args = ap.parse_args(argv)
@@ -95,6 +102,12 @@ def parse_args(argv=None):
         ap.error('--tuning-samples goes with --online-tuning')
     if args.online_tuning is not None and args.online_tuning < 0:
         ap.error('--online-tuning takes a number of iterations >= 0')
+    if args.step_tuning is not None and not args.online:
+        ap.error('--step-tuning goes with --online (offline: --online-tuning)')
+    if args.step_tuning is not None and args.step_tuning < 0:
+        ap.error('--step-tuning takes a number of iterations >= 0')
+    if args.step_tuning_samples is not None and args.step_tuning is None:
+        ap.error('--step-tuning-samples goes with --step-tuning')
     if 'LOCAL_RANK' not in os.environ:
         os.environ['LOCAL_RANK'] = str(args.local_rank)
     if args.matcher and 'waymo_native' not in (args.eval or []):
@@ -206,6 +219,10 @@ def main(argv=None):
         config.merge_from_dict(cfg, {'model.test_cfg.online_tuning': dict(
             num_iter=args.online_tuning, downsample_size=-1 if args.tuning_samples is None else args.tuning_samples,
             balance_sample=True)})
+    if args.step_tuning is not None:
+        config.merge_from_dict(cfg, {'model.test_cfg.online_step_tuning': dict(
+            num_iter=args.step_tuning, downsample_size=-1 if args.step_tuning_samples is None else args.step_tuning_samples,
+            balance_sample=True, seed=0)})
     rank, world, local_rank = init_dist(args.dist_backend) if args.launcher == 'pytorch' else (0, 1, 0)
     dev = torch.device('cuda', local_rank % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)

@@ -248,21 +248,10 @@ __global__ void __launch_bounds__(kST) append_chunk_kernel(ChunkArgs a) {
   }
 }
 
-// the launch behind both exports (their checks come first: nothing is dereferenced or launched before they pass)
+// the launches behind the exports (their checks come first: nothing is dereferenced or launched before they pass)
 template <int kMaxS>
-int launch_step(const float* q, int64_t ldq, const float* k_new, int64_t ldk, const float* v_new, int64_t ldv,
-                const int32_t* slot, const int32_t* pos, float* k_cache, float* v_cache, int32_t n, int32_t slots, int32_t cap,
-                int32_t H, int32_t D, float scale, int32_t window, int32_t ring, float* out, int64_t ldo,
-                ococc_stream_t stream_) {
-  StepArgs a{};
-  a.q = q; a.k_new = k_new; a.v_new = v_new;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
-  a.slot = slot; a.pos = pos;
-  a.k_cache = k_cache; a.v_cache = v_cache;
-  a.n = n; a.slots = slots; a.cap = cap; a.H = H; a.D = D;
-  a.scale = scale; a.window = window; a.ring = ring;
-  a.out = out; a.ldo = ldo;
-  hipLaunchKernelGGL(attn_step_kernel<kMaxS>, dim3(n, H), dim3(kST), 0, (hipStream_t)stream_, a);
+int launch_step(const StepArgs& a, ococc_stream_t stream_) {
+  hipLaunchKernelGGL(attn_step_kernel<kMaxS>, dim3(a.n, a.H), dim3(kST), 0, (hipStream_t)stream_, a);
   OCOCC_CHECK_LAUNCH();
   return OCOCC_OK;
 }
@@ -278,7 +267,12 @@ int launch_chunk(const ChunkArgs& a, ococc_stream_t stream_) {
 
 }  // namespace
 
-#define OCOCC_STEP_COMMON_CHECKS()                                                                                     \
+// The three exports name their common arguments alike, so what they share is written once over those names.
+// OCOCC_STEP_CHECKS(the export's own checks): the checks of all three around the export's own, in the order the messages
+// have always come in; an empty call returns OCOCC_OK once the checks on the sizes have passed.
+#define OCOCC_STEP_CHECKS(...)                                                                                         \
+  OCOCC_REQUIRE(n >= 0 && slots >= 1 && cap >= 1 && H >= 1 && D >= 1, "empty cache or negative row count");            \
+  __VA_ARGS__                                                                                                          \
   OCOCC_REQUIRE(H <= 65535, "too many heads");                                                                         \
   if (n == 0) return OCOCC_OK;                                                                                         \
   OCOCC_REQUIRE(q && k_new && v_new && slot && pos && k_cache && v_cache && out, "null pointer");                      \
@@ -288,19 +282,24 @@ int launch_chunk(const ChunkArgs& a, ococc_stream_t stream_) {
                     (((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_cache | (uintptr_t)v_cache |   \
                       (uintptr_t)out) & 15) == 0,                                                                      \
                 "rows must be 16-byte aligned")
+#define OCOCC_REQUIRE_LONG_CACHE()                                                                                  \
+  OCOCC_REQUIRE(cap <= kLongMaxS, "caches of up to 4096 frames per slot");                                             \
+  OCOCC_REQUIRE(ring == 0 || (window >= 1 && window <= cap),                                                           \
+                "a ring cache needs a window of 1 .. cap frames (the row of frame t overwrites frame t - cap)")
+// the StepArgs of an export's arguments, in the order of the struct's fields
+#define OCOCC_STEP_ARGS(ring_)                                                                                         \
+  StepArgs { q, k_new, v_new, ldq, ldk, ldv, slot, pos, k_cache, v_cache, n, slots, cap, H, D, scale, window, (ring_), out, ldo }
 
 extern "C" int ococc_temporal_attention_step_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk,
                                                  const float* v_new, int64_t ldv, const int32_t* slot, const int32_t* pos,
                                                  float* k_cache, float* v_cache, int32_t n, int32_t slots, int32_t cap,
                                                  int32_t H, int32_t D, float scale, int32_t window, float* out, int64_t ldo,
                                                  ococc_stream_t stream_) {
-  OCOCC_REQUIRE(n >= 0 && slots >= 1 && cap >= 1 && H >= 1 && D >= 1, "empty cache or negative row count");
-  OCOCC_REQUIRE(n <= slots, "more rows than cache slots (the slots of one step are distinct)");
-  OCOCC_REQUIRE(cap <= kSMaxS && D <= kSMaxD && D % 4 == 0,
-                "caches of up to 256 frames per slot, head width a multiple of 4 up to 384");
-  OCOCC_STEP_COMMON_CHECKS();
-  return launch_step<kSMaxS>(q, ldq, k_new, ldk, v_new, ldv, slot, pos, k_cache, v_cache, n, slots, cap, H, D, scale, window,
-                             0, out, ldo, stream_);
+  OCOCC_STEP_CHECKS(
+      OCOCC_REQUIRE(n <= slots, "more rows than cache slots (the slots of one step are distinct)");
+      OCOCC_REQUIRE(cap <= kSMaxS && D <= kSMaxD && D % 4 == 0,
+                    "caches of up to 256 frames per slot, head width a multiple of 4 up to 384"););
+  return launch_step<kSMaxS>(OCOCC_STEP_ARGS(0), stream_);
 }
 
 extern "C" int ococc_temporal_attention_step_long_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk,
@@ -309,15 +308,11 @@ extern "C" int ococc_temporal_attention_step_long_f32(const float* q, int64_t ld
                                                       int32_t slots, int32_t cap, int32_t H, int32_t D, float scale,
                                                       int32_t window, int32_t ring, float* out, int64_t ldo,
                                                       ococc_stream_t stream_) {
-  OCOCC_REQUIRE(n >= 0 && slots >= 1 && cap >= 1 && H >= 1 && D >= 1, "empty cache or negative row count");
-  OCOCC_REQUIRE(cap <= kLongMaxS, "caches of up to 4096 frames per slot");
-  OCOCC_REQUIRE(ring == 0 || (window >= 1 && window <= cap),
-                "a ring cache needs a window of 1 .. cap frames (the row of frame t overwrites frame t - cap)");
-  OCOCC_REQUIRE(n <= slots, "more rows than cache slots (the slots of one step are distinct)");
-  OCOCC_REQUIRE(D <= kSMaxD && D % 4 == 0, "head width a multiple of 4 up to 384");
-  OCOCC_STEP_COMMON_CHECKS();
-  return launch_step<kLongMaxS>(q, ldq, k_new, ldk, v_new, ldv, slot, pos, k_cache, v_cache, n, slots, cap, H, D, scale,
-                                window, ring != 0, out, ldo, stream_);
+  OCOCC_STEP_CHECKS(
+      OCOCC_REQUIRE_LONG_CACHE();
+      OCOCC_REQUIRE(n <= slots, "more rows than cache slots (the slots of one step are distinct)");
+      OCOCC_REQUIRE(D <= kSMaxD && D % 4 == 0, "head width a multiple of 4 up to 384"););
+  return launch_step<kLongMaxS>(OCOCC_STEP_ARGS(ring != 0), stream_);
 }
 
 extern "C" int ococc_temporal_attention_chunk_f32(const float* q, int64_t ldq, const float* k_new, int64_t ldk,
@@ -326,22 +321,11 @@ extern "C" int ococc_temporal_attention_chunk_f32(const float* q, int64_t ldq, c
                                                   int32_t slots, int32_t cap, int32_t H, int32_t D, float scale,
                                                   int32_t window, int32_t ring, float* out, int64_t ldo,
                                                   ococc_stream_t stream_) {
-  OCOCC_REQUIRE(n >= 0 && slots >= 1 && cap >= 1 && H >= 1 && D >= 1, "empty cache or negative row count");
-  OCOCC_REQUIRE(cap <= kLongMaxS, "caches of up to 4096 frames per slot");
-  OCOCC_REQUIRE(ring == 0 || (window >= 1 && window <= cap),
-                "a ring cache needs a window of 1 .. cap frames (the row of frame t overwrites frame t - cap)");
-  OCOCC_REQUIRE(D <= kSMaxD && D % 4 == 0, "head width a multiple of 4 up to 384");
-  OCOCC_STEP_COMMON_CHECKS();
+  OCOCC_STEP_CHECKS(
+      OCOCC_REQUIRE_LONG_CACHE();
+      OCOCC_REQUIRE(D <= kSMaxD && D % 4 == 0, "head width a multiple of 4 up to 384"););
   OCOCC_REQUIRE(off, "null pointer");
   const bool small = cap <= kSMaxS && ring == 0;   // one score per thread, as ococc_temporal_attention_step_f32
-  ChunkArgs a{};
-  a.q = q; a.k_new = k_new; a.v_new = v_new;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
-  a.slot = slot; a.pos = pos; a.off = off;
-  a.k_cache = k_cache; a.v_cache = v_cache;
-  a.n = n; a.slots = slots; a.cap = cap; a.H = H; a.D = D;
-  a.scale = scale; a.window = window; a.ring = ring != 0;
-  a.out = out; a.ldo = ldo;
-  a.max_keys = small ? kSMaxS : kLongMaxS;
+  const ChunkArgs a{OCOCC_STEP_ARGS(ring != 0), off, small ? kSMaxS : kLongMaxS};
   return small ? launch_chunk<kSMaxS>(a, stream_) : launch_chunk<kLongMaxS>(a, stream_);
 }

@@ -856,26 +856,10 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
         (_step_tuner: the sample drawn on HIP kernels, the loss a per-RoI mean); ``fused_roi_feats``, ``cls_score`` and
         ``bbox_pred`` are then those of the tuned latent, while ``ori_roi_feats`` and the temporal cache -- K and V come from
         the SIR features, before the fuse -- are bit for bit those of an untuned step.  None: nothing is launched for it."""
-        if self.training:
-            raise RuntimeError('OccBBoxHead.forward_step is inference only: call .eval() first')
-        if self.test_cfg.get('allow_attn_future', False):
-            raise ValueError('test_cfg.allow_attn_future lets a frame attend to later frames: such a model cannot run '
-                             'frame by frame')
-        if self.test_cfg.get('online_tuning', False):
-            raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference: pass `tune=` to the step')
-        tune = self._check_tune(tune)
+        tune = self._check_online('forward_step', tune)
         frames = [cache.pos_host[int(s)] for s in slot] if tune is not None else None   # (before the step bumps them)
-        final_cluster_feats, nonempty_roi_mask, local_roi_feats, local_xyz = self._encode_rois(
-            pts_xyz, pts_features, pts_info, roi_inds, rois)
-        pos_embed = self._pos_embed(roi_frame_inds, rois[:, 1:])
-        roi_feats_fused = self.trans_enc.step(final_cluster_feats, pos_embed, slot, cache,
-                                              self.test_cfg.get('attn_window_size', -1))
-        if tune is not None:
-            tune = self._step_tuner(tune, local_xyz, rois, roi_inds, nonempty_roi_mask, [int(s) for s in slot], frames)
-        ret = self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask, tune)
-        if return_points:   # (what get_frame_occ rasterises: the auto-encoder's box-frame points and their rows)
-            ret.update(local_xyz=local_xyz, roi_inds=roi_inds)
-        return ret
+        return self._forward_online(pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds, slot, frames,
+                                    self.trans_enc.step, cache, return_points, tune)
 
     @torch.no_grad()
     def forward_steps(self, pts_xyz, pts_features, pts_info, roi_inds, rois, slot_rows, cache, return_points=False, tune=None):
@@ -887,26 +871,36 @@ class OccBBoxHead(nn.Module, SparseHeadMixin):
         (slot, frame), as the single step of that frame does).  Returns the dict of ``forward`` for the n rows, in input
         order."""
         from .tracklet import host_index
+        tune = self._check_online('forward_steps', tune)
+        slots, offsets, _ = cache.check_steps(slot_rows)
+        frames = [cache.pos_host[s] + j for s, j in zip(slots, offsets)]
+        return self._forward_online(pts_xyz, pts_features, pts_info, roi_inds, rois, host_index(frames, rois.device), slots,
+                                    frames, self.trans_enc.steps, cache, return_points, tune)
+
+    def _check_online(self, what, tune):
+        """what the steps refuse, in this order and before ``cache`` is touched; ``tune`` as _check_tune returns it"""
         if self.training:
-            raise RuntimeError('OccBBoxHead.forward_steps is inference only: call .eval() first')
+            raise RuntimeError(f'OccBBoxHead.{what} is inference only: call .eval() first')
         if self.test_cfg.get('allow_attn_future', False):
             raise ValueError('test_cfg.allow_attn_future lets a frame attend to later frames: such a model cannot run '
                              'frame by frame')
         if self.test_cfg.get('online_tuning', False):
             raise NotImplementedError('test_cfg.online_tuning with frame-by-frame inference: pass `tune=` to the step')
-        tune = self._check_tune(tune)
-        slots, offsets, _ = cache.check_steps(slot_rows)
-        frames = [cache.pos_host[s] + j for s, j in zip(slots, offsets)]
-        roi_frame_inds = host_index(frames, rois.device)
+        return self._check_tune(tune)
+
+    def _forward_online(self, pts_xyz, pts_features, pts_info, roi_inds, rois, roi_frame_inds, slots, frames, encoder_step,
+                        cache, return_points, tune):
+        """the body of forward_step and forward_steps once the rows' frame indices are known: ``roi_frame_inds`` on the
+        device for the positional embedding, ``frames`` on the host for the tuning seeds (needed with ``tune`` only);
+        ``encoder_step`` is trans_enc.step or trans_enc.steps"""
         final_cluster_feats, nonempty_roi_mask, local_roi_feats, local_xyz = self._encode_rois(
             pts_xyz, pts_features, pts_info, roi_inds, rois)
         pos_embed = self._pos_embed(roi_frame_inds, rois[:, 1:])
-        roi_feats_fused = self.trans_enc.steps(final_cluster_feats, pos_embed, slots, cache,
-                                               self.test_cfg.get('attn_window_size', -1))
+        roi_feats_fused = encoder_step(final_cluster_feats, pos_embed, slots, cache, self.test_cfg.get('attn_window_size', -1))
         if tune is not None:
-            tune = self._step_tuner(tune, local_xyz, rois, roi_inds, nonempty_roi_mask, slots, frames)
+            tune = self._step_tuner(tune, local_xyz, rois, roi_inds, nonempty_roi_mask, [int(s) for s in slots], frames)
         ret = self._fuse_and_predict(local_roi_feats, roi_feats_fused, final_cluster_feats, nonempty_roi_mask, tune)
-        if return_points:
+        if return_points:   # (what get_frame_occ rasterises: the auto-encoder's box-frame points and their rows)
             ret.update(local_xyz=local_xyz, roi_inds=roi_inds)
         return ret
 

@@ -119,27 +119,18 @@ class TemporalCache(object):
         return 2 * self.num_layers * self.slots * self.cap * self.embed_dim * 4
 
     def check_step(self, slots):
-        """the host-side checks of one step over the slot list ``slots``: in range, distinct, room for one more frame (a
-        ring cache always has room: only its frame counter can run out)"""
+        """the host-side checks of one step over the slot list ``slots``: distinct, and what ``check_steps`` asks of runs
+        of one frame -- in range, room for one more frame (a ring cache always has room: only its frame counter can run
+        out).  Returns the slots as ints."""
         from .. import _lib as L
         slots = [int(s) for s in slots]
         if len(set(slots)) != len(slots):
             raise L.OcoccError(f'TemporalCache: duplicate slots in one step: {sorted(slots)}')
-        for s in slots:
-            if not 0 <= s < self.slots:
-                raise L.OcoccError(f'TemporalCache: slot {s} outside 0..{self.slots - 1}')
-            if self.ring:
-                if self.pos_host[s] >= self.MAX_FRAMES:
-                    raise L.OcoccError(f'TemporalCache: slot {s} has been stepped through 2**31 - 1 frames, the last its '
-                                       'int32 counter holds (reset the slot)')
-            elif self.pos_host[s] >= self.cap:
-                raise L.OcoccError(f'TemporalCache: slot {s} already holds cap = {self.cap} frames; a tracklet longer than '
-                                   'the cache is not supported (reset the slot or build the cache with a larger cap <= '
-                                   f'{self.MAX_LONG_CAP if self.long else 256})')
-        return slots
+        return self.check_steps(slots)[0]
 
     def advance(self, slots, slot_dev):
-        """one more frame in every slot of ``slots`` (``slot_dev``: the same list as an int32 / int64 device tensor)"""
+        """one more frame per ROW of ``slots`` (``slot_dev``: the same list as an int32 / int64 device tensor): a slot
+        gains one frame in a step, its run's T_s frames in a chunked step (index_add_ counts a slot once per row it has)"""
         self.pos.index_add_(0, slot_dev.long(), torch.ones_like(slot_dev, dtype=torch.int32))
         for s in slots:
             self.pos_host[s] += 1
@@ -170,10 +161,6 @@ class TemporalCache(object):
                                    f'{self.cap}; a tracklet longer than the cache is not supported (reset the slot or '
                                    f'build the cache with a larger cap <= {self.MAX_LONG_CAP if self.long else 256})')
         return slots, offsets, runs
-
-    def advance_steps(self, slots, slot_dev):
-        """``advance`` after a chunked step: one more frame per ROW of ``slots`` (a slot gains its run's T_s frames)"""
-        self.advance(slots, slot_dev)   # (index_add_ counts a slot once per row it has)
 
     def reset(self, slots=None):
         """forget the frames of ``slots`` (all when None): the slot can follow a new tracklet.  The cached rows are left
@@ -279,6 +266,36 @@ class MultiheadAttention(nn.Module):
         ctx = gemm.bmm(prob, self._heads(v, S)).transpose(0, 1).reshape(L * B, E)
         return gemm.linear(ctx, self.out_proj.weight, self.out_proj.bias).view(L, B, E), None
 
+    def _step(self, what, x_qk, x_v, slot, off, cache_k, cache_v, pos, window, ring, long):
+        """the body of ``step`` (``off`` None) and ``steps``: the checks, the two in-projections, the attention export
+        that (off, long or ring) pick, out_proj"""
+        from .. import _lib as L
+        _eval_only(self, f'MultiheadAttention.{what}')
+        rows = (slot,) if off is None else (slot, off)
+        L.require_device(x_qk, x_v, *rows, cache_k, cache_v, pos)
+        n, E = x_qk.shape
+        assert E == self.embed_dim and x_v.shape == (n, E) and all(r.shape == (n,) and r.dtype == torch.int32 for r in rows)
+        assert pos.dtype == torch.int32 and cache_k.shape == cache_v.shape and cache_k.shape[2] == E
+        assert cache_k.dtype == cache_v.dtype == torch.float32 and cache_k.is_contiguous() and cache_v.is_contiguous()
+        assert pos.shape == (cache_k.shape[0],)
+        w, b = self.in_proj_weight, self.in_proj_bias
+        qk = gemm.linear(x_qk.float(), w[:2 * E], b[:2 * E])
+        v = gemm.linear(x_v.float(), w[2 * E:], b[2 * E:])
+        q, k = qk[:, :E], qk[:, E:]
+        ctx = torch.empty((n, E), dtype=torch.float32, device=qk.device)
+        new = (q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), *(r.data_ptr() for r in rows))
+        cached = (pos.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(), n, cache_k.shape[0], cache_k.shape[1], self.num_heads,
+                  self.head_dim, float(self.head_dim) ** -0.5, int(window))
+        out = (ctx.data_ptr(), ctx.stride(0), L.stream())
+        if off is not None:
+            L.check(L.lib.ococc_temporal_attention_chunk_f32(*new, *cached, int(bool(ring)), *out), 'temporal_attention_chunk')
+        elif long or ring:
+            L.check(L.lib.ococc_temporal_attention_step_long_f32(*new, *cached, int(bool(ring)), *out),
+                    'temporal_attention_step_long')
+        else:
+            L.check(L.lib.ococc_temporal_attention_step_f32(*new, *cached, *out), 'temporal_attention_step')
+        return gemm.linear(ctx, self.out_proj.weight, self.out_proj.bias)
+
     @torch.no_grad()
     def step(self, x_qk, x_v, slot, cache_k, cache_v, pos, window=-1, ring=False, long=False):
         """One new frame per tracklet against the cached ones: x_qk, x_v [n, E] (this frame's src + pos and src),
@@ -289,33 +306,7 @@ class MultiheadAttention(nn.Module):
         left as it is.  ``long`` / ``ring`` (TemporalCache): ococc_temporal_attention_step_long_f32 instead -- caches of up
         to 4096 rows, and with ``ring`` frame f in row f % cap (1 <= window <= cap).  No fall-back: arguments the kernel
         does not take raise."""
-        from .. import _lib as L
-        _eval_only(self, 'MultiheadAttention.step')
-        L.require_device(x_qk, x_v, slot, cache_k, cache_v, pos)
-        n, E = x_qk.shape
-        assert E == self.embed_dim and x_v.shape == (n, E) and slot.shape == (n,) and slot.dtype == torch.int32
-        assert pos.dtype == torch.int32 and cache_k.shape == cache_v.shape and cache_k.shape[2] == E
-        assert cache_k.dtype == cache_v.dtype == torch.float32 and cache_k.is_contiguous() and cache_v.is_contiguous()
-        assert pos.shape == (cache_k.shape[0],)
-        w, b = self.in_proj_weight, self.in_proj_bias
-        qk = gemm.linear(x_qk.float(), w[:2 * E], b[:2 * E])
-        v = gemm.linear(x_v.float(), w[2 * E:], b[2 * E:])
-        q, k = qk[:, :E], qk[:, E:]
-        ctx = torch.empty((n, E), dtype=torch.float32, device=qk.device)
-        if long or ring:
-            L.check(L.lib.ococc_temporal_attention_step_long_f32(
-                q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), slot.data_ptr(),
-                pos.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(), n, cache_k.shape[0], cache_k.shape[1], self.num_heads,
-                self.head_dim, float(self.head_dim) ** -0.5, int(window), int(bool(ring)), ctx.data_ptr(), ctx.stride(0),
-                L.stream()), 'temporal_attention_step_long')
-        else:
-            L.check(L.lib.ococc_temporal_attention_step_f32(
-                q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), slot.data_ptr(),
-                pos.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(), n, cache_k.shape[0], cache_k.shape[1], self.num_heads,
-                self.head_dim, float(self.head_dim) ** -0.5, int(window), ctx.data_ptr(), ctx.stride(0), L.stream()),
-                'temporal_attention_step')
-        return gemm.linear(ctx, self.out_proj.weight, self.out_proj.bias)
-
+        return self._step('step', x_qk, x_v, slot, None, cache_k, cache_v, pos, window, ring, long)
 
     @torch.no_grad()
     def steps(self, x_qk, x_v, slot, off, cache_k, cache_v, pos, window=-1, ring=False):
@@ -324,25 +315,7 @@ class MultiheadAttention(nn.Module):
         run (TemporalCache.check_steps).  Row i is frame pos[slot] + off[i]: it attends to the cached frames and to the
         earlier rows of its own run; the keys and values of all rows are appended afterwards, inside the same call.  The
         export picks the instance by cap and ``ring`` itself.  ``pos`` is left as it is."""
-        from .. import _lib as L
-        _eval_only(self, 'MultiheadAttention.steps')
-        L.require_device(x_qk, x_v, slot, off, cache_k, cache_v, pos)
-        n, E = x_qk.shape
-        assert E == self.embed_dim and x_v.shape == (n, E) and slot.shape == off.shape == (n,)
-        assert slot.dtype == off.dtype == pos.dtype == torch.int32 and cache_k.shape == cache_v.shape and cache_k.shape[2] == E
-        assert cache_k.dtype == cache_v.dtype == torch.float32 and cache_k.is_contiguous() and cache_v.is_contiguous()
-        assert pos.shape == (cache_k.shape[0],)
-        w, b = self.in_proj_weight, self.in_proj_bias
-        qk = gemm.linear(x_qk.float(), w[:2 * E], b[:2 * E])
-        v = gemm.linear(x_v.float(), w[2 * E:], b[2 * E:])
-        q, k = qk[:, :E], qk[:, E:]
-        ctx = torch.empty((n, E), dtype=torch.float32, device=qk.device)
-        L.check(L.lib.ococc_temporal_attention_chunk_f32(
-            q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), slot.data_ptr(), off.data_ptr(),
-            pos.data_ptr(), cache_k.data_ptr(), cache_v.data_ptr(), n, cache_k.shape[0], cache_k.shape[1], self.num_heads,
-            self.head_dim, float(self.head_dim) ** -0.5, int(window), int(bool(ring)), ctx.data_ptr(), ctx.stride(0),
-            L.stream()), 'temporal_attention_chunk')
-        return gemm.linear(ctx, self.out_proj.weight, self.out_proj.bias)
+        return self._step('steps', x_qk, x_v, slot, off, cache_k, cache_v, pos, window, ring, False)
 
 
 class SimpleEncoderLayer(nn.Module):
@@ -372,11 +345,14 @@ class SimpleEncoderLayer(nn.Module):
         hidden = self.dropout(self.activation(gemm.linear(x, self.linear1.weight, self.linear1.bias)))
         return gemm.linear(hidden, self.linear2.weight, self.linear2.bias)
 
+    def _after_attention(self, src, attended):
+        x = self._residual_norm(self.norm1, src, attended, self.dropout1)
+        return self._residual_norm(self.norm2, x, self._feed_forward(x), self.dropout2)
+
     def forward(self, src, key_padding_mask=None, pos_enc=None, attn_mask=None):
         qk_in = self.with_pos_embed(src, pos_enc)
         attended, _ = self.self_attn(qk_in, qk_in, value=src, attn_mask=attn_mask, key_padding_mask=key_padding_mask)
-        x = self._residual_norm(self.norm1, src, attended, self.dropout1)
-        return self._residual_norm(self.norm2, x, self._feed_forward(x), self.dropout2)
+        return self._after_attention(src, attended)
 
     @torch.no_grad()
     def step(self, src, pos_enc, slot, cache_k, cache_v, pos, window=-1, ring=False, long=False):
@@ -384,21 +360,16 @@ class SimpleEncoderLayer(nn.Module):
         (MultiheadAttention.step, which ``ring`` / ``long`` go to): the same post-LN structure, the dropouts are the
         identity (inference only)."""
         _eval_only(self, 'SimpleEncoderLayer.step')
-        attended = self.self_attn.step(self.with_pos_embed(src, pos_enc), src, slot, cache_k, cache_v, pos, window, ring,
-                                       long)
-        x = self._residual_norm(self.norm1, src, attended, self.dropout1)
-        return self._residual_norm(self.norm2, x, self._feed_forward(x), self.dropout2)
-
+        return self._after_attention(src, self.self_attn.step(self.with_pos_embed(src, pos_enc), src, slot, cache_k, cache_v,
+                                                              pos, window, ring, long))
 
     @torch.no_grad()
     def steps(self, src, pos_enc, slot, off, cache_k, cache_v, pos, window=-1, ring=False):
         """``step`` for one or more new frames per tracklet (MultiheadAttention.steps): everything but the attention
         works per row"""
         _eval_only(self, 'SimpleEncoderLayer.steps')
-        attended = self.self_attn.steps(self.with_pos_embed(src, pos_enc), src, slot, off, cache_k, cache_v, pos, window,
-                                        ring)
-        x = self._residual_norm(self.norm1, src, attended, self.dropout1)
-        return self._residual_norm(self.norm2, x, self._feed_forward(x), self.dropout2)
+        return self._after_attention(src, self.self_attn.steps(self.with_pos_embed(src, pos_enc), src, slot, off, cache_k,
+                                                               cache_v, pos, window, ring))
 
 
 def _get_clones(module, N):
@@ -419,6 +390,31 @@ class TransformerEncoder(nn.Module):
             x = layer(x, key_padding_mask=key_padding_mask, pos_enc=pos_enc, attn_mask=attn_mask)
         return x
 
+    def _step(self, src, pos_enc, slots, offsets, cache, window):
+        """the body of ``step`` (``offsets`` None) and ``steps`` over rows that the cache has checked: the checks of the
+        cache against this encoder and the rows, ONE upload of the row indices, the layers in turn, one bump"""
+        from .. import _lib as L
+        from ..tracklet import host_index
+        if cache.num_layers != self.num_layers:
+            raise L.OcoccError(f'TemporalCache of {cache.num_layers} layers for an encoder of {self.num_layers}')
+        ring, long = cache.ring, cache.long
+        if ring and not 1 <= int(window) <= cache.cap:
+            raise L.OcoccError(f'a ring TemporalCache of cap = {cache.cap} rows serves windows of 1..{cache.cap} frames, not '
+                               f'window = {window}: the row of frame t overwrites frame t - cap')
+        if len(slots) != src.shape[0]:
+            raise L.OcoccError(f'{len(slots)} slots for {src.shape[0]} rows')
+        L.require_device(src, pos_enc, cache.pos)
+        rows = host_index(slots + (offsets or []), src.device, dtype=torch.int32)   # (slots | offsets: one upload)
+        slot_dev, off_dev = rows[:len(slots)], rows[len(slots):]
+        x = src
+        for i, layer in enumerate(self.layers):
+            if offsets is None:
+                x = layer.step(x, pos_enc, slot_dev, cache.k[i], cache.v[i], cache.pos, window, ring, long)
+            else:
+                x = layer.steps(x, pos_enc, slot_dev, off_dev, cache.k[i], cache.v[i], cache.pos, window, ring)
+        cache.advance(slots, slot_dev)
+        return x
+
     @torch.no_grad()
     def step(self, src, pos_enc, slot, cache, window=-1):
         """One new frame for each of n tracklets: src, pos_enc [n, E]; ``slot``: the cache slot of each row, a list of
@@ -428,25 +424,9 @@ class TransformerEncoder(nn.Module):
         A ring cache (``cache.ring``) needs 1 <= window <= cache.cap.
         The host-side checks (duplicate slots, a step past ``cache.cap``, a window a ring cache cannot serve, CPU tensors)
         raise before anything is launched."""
-        from .. import _lib as L
-        from ..tracklet import host_index
         _eval_only(self, 'TransformerEncoder.step')
-        if cache.num_layers != self.num_layers:
-            raise L.OcoccError(f'TemporalCache of {cache.num_layers} layers for an encoder of {self.num_layers}')
-        ring, long = cache.ring, cache.long
-        if ring and not 1 <= int(window) <= cache.cap:
-            raise L.OcoccError(f'a ring TemporalCache of cap = {cache.cap} rows serves windows of 1..{cache.cap} frames, not '
-                               f'window = {window}: the row of frame t overwrites frame t - cap')
         slots = cache.check_step(slot.tolist() if torch.is_tensor(slot) else slot)
-        if len(slots) != src.shape[0]:
-            raise L.OcoccError(f'{len(slots)} slots for {src.shape[0]} rows')
-        L.require_device(src, pos_enc, cache.pos)
-        slot_dev = host_index(slots, src.device, dtype=torch.int32)
-        x = src
-        for i, layer in enumerate(self.layers):
-            x = layer.step(x, pos_enc, slot_dev, cache.k[i], cache.v[i], cache.pos, window, ring, long)
-        cache.advance(slots, slot_dev)
-        return x
+        return self._step(src, pos_enc, slots, None, cache, window)
 
     @torch.no_grad()
     def steps(self, src, pos_enc, slot_rows, cache, window=-1):
@@ -458,23 +438,6 @@ class TransformerEncoder(nn.Module):
         is; a ring cache takes runs longer than its cap.  Bumps ``cache.pos`` and its host mirror by the runs once, after
         the last layer.  The host-side checks (a window a ring cache cannot serve, slots out of range, rows of a slot that
         are not consecutive, a run past ``cache.cap``, CPU tensors) raise before anything is launched."""
-        from .. import _lib as L
-        from ..tracklet import host_index
         _eval_only(self, 'TransformerEncoder.steps')
-        if cache.num_layers != self.num_layers:
-            raise L.OcoccError(f'TemporalCache of {cache.num_layers} layers for an encoder of {self.num_layers}')
-        ring = cache.ring
-        if ring and not 1 <= int(window) <= cache.cap:
-            raise L.OcoccError(f'a ring TemporalCache of cap = {cache.cap} rows serves windows of 1..{cache.cap} frames, not '
-                               f'window = {window}: the row of frame t overwrites frame t - cap')
         slots, offsets, _ = cache.check_steps(slot_rows.tolist() if torch.is_tensor(slot_rows) else slot_rows)
-        if len(slots) != src.shape[0]:
-            raise L.OcoccError(f'{len(slots)} slots for {src.shape[0]} rows')
-        L.require_device(src, pos_enc, cache.pos)
-        both = host_index(slots + offsets, src.device, dtype=torch.int32)   # (one upload)
-        slot_dev, off_dev = both[:len(slots)], both[len(slots):]
-        x = src
-        for i, layer in enumerate(self.layers):
-            x = layer.steps(x, pos_enc, slot_dev, off_dev, cache.k[i], cache.v[i], cache.pos, window, ring)
-        cache.advance_steps(slots, slot_dev)
-        return x
+        return self._step(src, pos_enc, slots, offsets, cache, window)

@@ -447,34 +447,10 @@ class TrackletRoIHeadOCC(nn.Module):
 
         Reported on the host before anything is launched: a step past the cache's cap and duplicate or out-of-range
         slots (OcoccError), CPU tensors (OcoccError), training mode (RuntimeError)."""
-        from . import _lib as L
-        from .tracklet import host_index
         if self.training:
             raise RuntimeError('simple_test_step is inference only: call .eval() first')
-        slots = state.cache.check_step(slot)
-        L.require_device(pts_xyz, pts_feats, pts_batch_idx, boxes, scores, labels, state.cache.pos)
-        n, dev = boxes.size(0), boxes.device
-        if len(slots) != n or scores.size(0) != n or labels.size(0) != n:
-            raise L.OcoccError(f'{len(slots)} slots, {scores.size(0)} scores, {labels.size(0)} labels for {n} boxes')
-        if pts_xyz.size(0) == 0:   # (a frame without points: one zero row, as the detector gives an empty sample)
-            pts_xyz, pts_feats, pts_batch_idx = TrackletDetectorOCC.fake_points_for_empty_input(
-                [pts_xyz, pts_feats, pts_batch_idx])
-        rois = bbox3d2roi([boxes[i:i + 1, :7] for i in range(n)])     # column 0: the row's own index
-        frames = host_index([state.cache.pos_host[s] for s in slots], dev)
-        same = torch.zeros_like(frames)                                  # (the points are this frame's: one frame key)
-        pooled = self._pool_points(pts_xyz, pts_feats, pts_batch_idx.long(), torch.zeros_like(pts_batch_idx, dtype=torch.long),
-                                   rois, scores, same)
-        occ_cfg = self.online_occ_cfg() if occ else None               # (a wrong test_cfg.online_occ: before any launch)
-        res = self.bbox_head.forward_step(*pooled, rois, frames, slots, state.cache, **self._step_kwargs(occ, tune))
-        one = torch.cat([torch.zeros_like(rois[:, :1]), rois[:, 1:]], 1)   # (one group: get_bboxes splits by column 0)
-        out_boxes, out_scores, out_labels, valid = self.bbox_head.get_bboxes_from_tracklet(
-            one, res['cls_score'], res['bbox_pred'], res['nonempty_roi_mask'], labels, scores, None, gt_rois=gt_rois,
-            cfg=self.test_cfg)[0]
-        out = dict(boxes=out_boxes, scores=out_scores, labels=out_labels, valid=valid,
-                   fused_roi_feats=res['fused_roi_feats'], ori_roi_feats=res['ori_roi_feats'])
-        if occ:
-            out.update(self._step_occ(res, rois, occ_cfg, occ_transforms))
-        return out
+        return self._simple_test_rows(self.bbox_head.forward_step, state.cache.check_step(slot), None, pts_xyz, pts_feats,
+                                      pts_batch_idx, boxes, scores, labels, state, gt_rois, occ, occ_transforms, tune)
 
     @torch.no_grad()
     def simple_test_steps(self, pts_xyz, pts_feats, pts_row_idx, boxes, scores, labels, slot_rows, state, gt_rois=None,
@@ -492,23 +468,33 @@ class TrackletRoIHeadOCC(nn.Module):
 
         Reported on the host before anything is launched: slots out of range, rows of a slot that are not consecutive, a
         run past the cache's cap (OcoccError), CPU tensors (OcoccError), training mode (RuntimeError)."""
-        from . import _lib as L
         if self.training:
             raise RuntimeError('simple_test_steps is inference only: call .eval() first')
-        slots, _, _ = state.cache.check_steps(slot_rows)
+        slots, offsets, _ = state.cache.check_steps(slot_rows)
+        return self._simple_test_rows(self.bbox_head.forward_steps, slots, offsets, pts_xyz, pts_feats, pts_row_idx, boxes,
+                                      scores, labels, state, gt_rois, occ, None, tune)
+
+    def _simple_test_rows(self, head_step, slots, offsets, pts_xyz, pts_feats, pts_row_idx, boxes, scores, labels, state,
+                          gt_rois, occ, occ_transforms, tune):
+        """the body of simple_test_step (``offsets`` None: ``head_step`` is forward_step, which takes the rows' frame
+        indices from here) and simple_test_steps (forward_steps, which derives them) over checked ``slots``: pool the
+        rows' points into the rows' boxes, the head, the decode as one group, the result dict"""
+        from . import _lib as L
+        from .tracklet import host_index
         L.require_device(pts_xyz, pts_feats, pts_row_idx, boxes, scores, labels, state.cache.pos)
-        n = boxes.size(0)
+        n, dev = boxes.size(0), boxes.device
         if len(slots) != n or scores.size(0) != n or labels.size(0) != n:
             raise L.OcoccError(f'{len(slots)} slots, {scores.size(0)} scores, {labels.size(0)} labels for {n} boxes')
         if pts_xyz.size(0) == 0:   # (rows without points: one zero row, as the detector gives an empty sample)
             pts_xyz, pts_feats, pts_row_idx = TrackletDetectorOCC.fake_points_for_empty_input(
                 [pts_xyz, pts_feats, pts_row_idx])
         rois = bbox3d2roi([boxes[i:i + 1, :7] for i in range(n)])     # column 0: the row's own index
-        same = torch.zeros((n,), dtype=torch.long, device=boxes.device)   # (a row's points are its frame's: one frame key)
+        frames = (host_index([state.cache.pos_host[s] for s in slots], dev),) if offsets is None else ()
+        same = torch.zeros((n,), dtype=torch.long, device=dev)          # (a row's points are its frame's: one frame key)
         pooled = self._pool_points(pts_xyz, pts_feats, pts_row_idx.long(), torch.zeros_like(pts_row_idx, dtype=torch.long),
                                    rois, scores, same)
-        occ_cfg = self.online_occ_cfg() if occ else None
-        res = self.bbox_head.forward_steps(*pooled, rois, slots, state.cache, **self._step_kwargs(occ, tune))
+        occ_cfg = self.online_occ_cfg() if occ else None               # (a wrong test_cfg.online_occ: before any launch)
+        res = head_step(*pooled, rois, *frames, slots, state.cache, **self._step_kwargs(occ, tune))
         one = torch.cat([torch.zeros_like(rois[:, :1]), rois[:, 1:]], 1)   # (one group: get_bboxes splits by column 0)
         out_boxes, out_scores, out_labels, valid = self.bbox_head.get_bboxes_from_tracklet(
             one, res['cls_score'], res['bbox_pred'], res['nonempty_roi_mask'], labels, scores, None, gt_rois=gt_rois,
@@ -516,7 +502,7 @@ class TrackletRoIHeadOCC(nn.Module):
         out = dict(boxes=out_boxes, scores=out_scores, labels=out_labels, valid=valid,
                    fused_roi_feats=res['fused_roi_feats'], ori_roi_feats=res['ori_roi_feats'])
         if occ:
-            out.update(self._step_occ(res, rois, occ_cfg))
+            out.update(self._step_occ(res, rois, occ_cfg, occ_transforms))
         return out
 
     def _step_kwargs(self, occ, tune):
@@ -632,12 +618,10 @@ class TrackletRoIHeadOCC(nn.Module):
         xyz, feats, row, counts = scene_step_rows(
             points, boxes, scores, transforms=mats[0].float(), extra_width=cfg['extra_width'], attr_dims=cfg['attr_dims'],
             point_cloud_range=cfg['point_cloud_range'], max_points=cfg['max_points'], deco_boxes=fixed_boxes)
+        kw = dict(occ=True, occ_transforms=mats[1].float()) if occ else {}
+        out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois, tune=tune, **kw)
         if occ:
-            out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois,
-                                        occ=True, occ_transforms=mats[1].float(), tune=tune)
             out['occ_ego'] = out.pop('occ')
-        else:
-            out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois, tune=tune)
         out['boxes_ego'] = torch.where(out['valid'].to(dev).bool()[:, None], self._boxes_through(out['boxes'], mats[1]),
                                        boxes[:, :7])
         out['num_points'] = counts
@@ -662,7 +646,6 @@ class TrackletRoIHeadOCC(nn.Module):
         Up to 256 frames: a cache of that many rows.  Above: with test_cfg.attn_window_size = W > 0 a ring cache of W rows
         (any length), without a window a long cache of up to 4096 rows; past that an OcoccError."""
         from . import _lib as L
-        from .tracklet import host_index
         assert len(tracklet_list) == 1, 'only support batch size 1'
         if self.test_cfg.get('tta', None) is not None:
             raise NotImplementedError('test_cfg.online with test_cfg.tta')
@@ -687,21 +670,19 @@ class TrackletRoIHeadOCC(nn.Module):
         order = torch.sort(pts_frame_inds, stable=True).indices
         counts = torch.bincount(pts_frame_inds, minlength=num).tolist()
         assert len(counts) == num, 'a point lies in a frame past the tracklet'
-        steps = []
-        if chunk == 1:
-            for t, sel in enumerate(order.split(counts)):
-                steps.append(self.simple_test_step(
-                    pts_xyz[sel], pts_feats[sel], torch.zeros_like(pts_batch_idx[sel]), rois[t:t + 1, 1:8],
-                    cls_preds[t:t + 1], labels_3d[t:t + 1], [0], state, gt_rois=None if gt_rois is None else gt_rois[t:t + 1]))
-        else:   # T frames per call: a point's row is its frame's place in the chunk
-            first = 0
-            for t in range(0, num, chunk):
-                T = min(chunk, num - t)
-                sel = order[first:first + sum(counts[t:t + T])]
-                first += sel.numel()
-                steps.append(self.simple_test_steps(
-                    pts_xyz[sel], pts_feats[sel], pts_frame_inds[sel] - t, rois[t:t + T, 1:8], cls_preds[t:t + T],
-                    labels_3d[t:t + T], [0] * T, state, gt_rois=None if gt_rois is None else gt_rois[t:t + T]))
+        steps, first = [], 0
+        for t in range(0, num, chunk):   # T frames per call, the last call takes the rest
+            T = min(chunk, num - t)
+            sel = order[first:first + sum(counts[t:t + T])]
+            first += sel.numel()
+            rows = (rois[t:t + T, 1:8], cls_preds[t:t + T], labels_3d[t:t + T])
+            gt = None if gt_rois is None else gt_rois[t:t + T]
+            if chunk == 1:
+                steps.append(self.simple_test_step(pts_xyz[sel], pts_feats[sel], torch.zeros_like(pts_batch_idx[sel]), *rows,
+                                                   [0], state, gt_rois=gt))
+            else:   # (a point's row is its frame's place in the chunk)
+                steps.append(self.simple_test_steps(pts_xyz[sel], pts_feats[sel], pts_frame_inds[sel] - t, *rows, [0] * T,
+                                                    state, gt_rois=gt))
         cat = lambda k: torch.cat([s[k] for s in steps], 0)
         res = dict(fused_roi_feats=cat('fused_roi_feats'), ori_roi_feats=cat('ori_roi_feats'), nonempty_roi_mask=cat('valid'))
         decoded = [(cat('boxes'), cat('scores'), cat('labels'), cat('valid'))]

@@ -1,6 +1,6 @@
 """Several frames per tracklet in one online step, host side (no device): the chunk export of the attention step
 (csrc/causal_attn_step.hip, ococc_temporal_attention_chunk_f32) is declared, bound and documented and reports argument
-errors before it dereferences or launches anything; the bookkeeping of TemporalCache.check_steps / advance_steps; ``steps``
+errors before it dereferences or launches anything; the bookkeeping of TemporalCache.check_steps / advance; ``steps``
 on CPU tensors; test_cfg.online_chunk and tools/test.py --online-chunk."""
 import ctypes
 import importlib.util
@@ -88,7 +88,7 @@ def test_check_steps_bookkeeping():
             c.check_steps(rows)
         assert c.pos_host == state[0] and torch.equal(c.pos, state[1])       # nothing is modified when it raises
     slot_dev = torch.tensor(slots, dtype=torch.int32)
-    c.advance_steps(slots, slot_dev)
+    c.advance(slots, slot_dev)
     assert c.pos_host == [8, 0, 0, 8, 0, 8] and c.pos.tolist() == c.pos_host
     with pytest.raises(L.OcoccError, match='cap = 8'):
         c.check_steps([2, 0])

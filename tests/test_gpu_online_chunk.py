@@ -318,3 +318,67 @@ def test_steps_of_two_tracklets_at_different_frame_counts(runs, dev):
             d = float((res[key].double() - other[key][fr].double()).abs().max()) / scale
             print(f'{key}: rows of two tracklets against the {name} {d:.3e} (d0 = {d0:.3e})')
             assert d <= 2 * d0 + 1e-7, (key, name, d, d0)
+
+
+@pytest.mark.parametrize('ring', [False, True])
+def test_encoder_steps_of_one_frame_are_the_step(dev, ring):
+    """``steps`` with a run of one frame per slot against ``step`` on twin caches: the two share everything but the
+    attention export, whose chunk mode computes the step's sums in the step's order, so the output, every layer's keys and
+    values, ``pos`` and ``pos_host`` are equal bit for bit.  2 layers, E = 32, 2 heads, ffn 64; rows for the slots [2, 0]
+    of a three-slot cache that holds 1, 0 and 3 frames (cap 4), and of a ring of cap = window = 3 at frames 7, 0 and 4,
+    where both new rows overwrite an old frame."""
+    from objectcentricocccompletion_amd.occ.layers import SimpleEncoderLayer, TemporalCache, TransformerEncoder
+    torch.manual_seed(11)
+    E, slots = 32, [2, 0]
+    enc = TransformerEncoder(SimpleEncoderLayer(E, 2, dim_feedforward=64, dropout=0.1), 2)
+    with torch.no_grad():
+        for prm in enc.parameters():
+            prm.copy_(torch.randn_like(prm) * prm.shape[1] ** -0.5 if prm.dim() == 2 else prm + 0.1 * torch.randn_like(prm))
+    enc = enc.to(dev).eval()
+    kw, window, pos = (dict(cap=3, ring=True), 3, [7, 0, 4]) if ring else (dict(cap=4), -1, [1, 0, 3])
+    twins = [TemporalCache(2, 3, E, dev, **kw) for _ in range(2)]
+    rows = [torch.randn_like(k) for k in twins[0].k + twins[0].v]
+    for cache in twins:
+        for t, r in zip(cache.k + cache.v, rows):
+            t.copy_(r)
+        cache.pos.copy_(torch.tensor(pos, dtype=torch.int32))
+        cache.pos_host = list(pos)
+    src, pe = torch.randn(2, E, device=dev), torch.randn(2, E, device=dev)
+    one = enc.step(src, pe, slots, twins[0], window)
+    many = enc.steps(src, pe, slots, twins[1], window)
+    assert torch.equal(one, many) and bool(torch.isfinite(one).all())
+    for a, b, r in zip(twins[0].k + twins[0].v, twins[1].k + twins[1].v, rows):
+        assert torch.equal(a, b) and not torch.equal(a, r)
+    after = [p + (s in slots) for s, p in enumerate(pos)]
+    for cache in twins:
+        assert cache.pos_host == after and cache.pos.tolist() == after
+
+
+def test_three_steps_and_one_chunk_of_three_leave_the_same_state(runs, dev):
+    """frames 0-2 of the tracklet above with ``occ=True``, as three simple_test_step calls and as one simple_test_steps
+    call with a run of three: the frame counters on the host and on the device are equal, both forms return the same nine
+    keys, the valid flags are equal and boxes, scores and fused latents agree by the rule of the tests above."""
+    model = runs['model']
+    rh = model.roi_head
+    kw = _tracklet_inputs(dev)
+    xyz, feats, _, frames = model._cat_points(kw['points'], kw['pts_frame_inds'])
+    rois, _, scores, labels = rh.tracklets2rois(kw['tracklet'])
+    sel = [torch.nonzero(frames == f)[:, 0] for f in range(3)]
+    single, chunked = rh.online_begin(1, dev, cap=L_FRAMES), rh.online_begin(1, dev, cap=L_FRAMES)
+    with torch.no_grad():
+        steps = [rh.simple_test_step(xyz[s], feats[s], torch.zeros_like(s), rois[f:f + 1, 1:8], scores[f:f + 1],
+                                     labels[f:f + 1], [0], single, occ=True) for f, s in enumerate(sel)]
+        chunk = rh.simple_test_steps(xyz[torch.cat(sel)], feats[torch.cat(sel)],
+                                     torch.cat([torch.full_like(s, f) for f, s in enumerate(sel)]), rois[:3, 1:8], scores[:3],
+                                     labels[:3], [0] * 3, chunked, occ=True)
+    assert single.cache.pos_host == chunked.cache.pos_host == [3] and single.frames == chunked.frames
+    assert single.cache.pos.tolist() == chunked.cache.pos.tolist() == [3]
+    keys = {'boxes', 'scores', 'labels', 'valid', 'fused_roi_feats', 'ori_roi_feats', 'occ', 'occ_flags', 'occ_counts'}
+    assert set(chunk) == keys and all(set(s) == keys for s in steps)
+    assert len(chunk['occ_counts']) == 3 and all(len(s['occ_counts']) == 1 for s in steps)
+    assert torch.equal(chunk['valid'], torch.cat([s['valid'] for s in steps])) and bool(chunk['valid'].all())
+    for key in ('boxes', 'scores', 'fused_roi_feats'):
+        d0, scale = _d0(runs, key)
+        d = float((chunk[key].double() - torch.cat([s[key] for s in steps]).double()).abs().max()) / scale
+        print(f'{key}: one chunk of three against three single steps {d:.3e} (d0 = {d0:.3e})')
+        assert d <= 2 * d0 + 1e-7, (key, d, d0)

@@ -64,6 +64,50 @@ def test_cache_bookkeeping():
         TemporalCache(3, 1, 64, 'cpu', cap=257)
 
 
+@pytest.mark.parametrize('kind', ['plain', 'ring', 'long'])
+def test_check_step_is_check_steps_over_distinct_slots(kind):
+    """check_step(s) is check_steps(s) for runs of one frame plus the refusal of duplicates: on every list of distinct
+    slots of a 4-slot cache (slots at 0 frames, in mid-tracklet, one below the limit, at the limit) both return the same
+    rows, with offsets 0 and runs of 1, or both raise OcoccError; [1, 1] is a run of two to check_steps and a duplicate
+    to check_step; neither touches pos_host"""
+    import itertools
+    from objectcentricocccompletion_amd import _lib as L
+    from objectcentricocccompletion_amd.occ.layers import TemporalCache
+    c = TemporalCache(1, 4, 8, 'cpu', **dict(plain=dict(cap=2), ring=dict(cap=3, ring=True), long=dict(cap=300, long=True))[kind])
+    limit = c.MAX_FRAMES if c.ring else c.cap
+    c.pos_host = [0, 0, limit - 1, limit]                                           # slot 3 is full / its counter is spent
+    before = list(c.pos_host)
+
+    def outcome(check, slots):
+        try:
+            return check(slots)
+        except L.OcoccError as e:
+            return str(e)
+
+    lists = [list(p) for n in range(5) for p in itertools.permutations(range(4), n)] + [[4], [0, 4], [-1], [2, 5, 1]]
+    raised = 0
+    for slots in lists:
+        one, many = outcome(c.check_step, slots), outcome(c.check_steps, slots)
+        if isinstance(many, str):                                                    # the same refusal, word for word
+            assert one == many and (3 in slots or min(slots) < 0 or max(slots) > 3), slots
+            raised += 1
+        else:
+            assert one == many[0] == slots and many[1] == [0] * len(slots) and many[2] == {s: 1 for s in slots}, slots
+    assert raised == len([s for s in lists if 3 in s or min(s, default=0) < 0 or max(s, default=0) > 3]) > 0
+    for check in (c.check_step, c.check_steps):
+        with pytest.raises(L.OcoccError, match='outside 0..3'):
+            check([0, 4])
+        with pytest.raises(L.OcoccError, match=re.escape('2**31') if c.ring else f'cap = {c.cap}'):
+            check([3])
+    if not c.ring:
+        with pytest.raises(L.OcoccError, match='<= 4096' if kind == 'long' else '<= 256'):
+            c.check_step([3])
+    with pytest.raises(L.OcoccError, match='duplicate'):
+        c.check_step([1, 1])
+    assert c.check_steps([1, 1]) == ([1, 1], [0, 1], {1: 2})
+    assert c.pos_host == before and c.pos.tolist() == [0, 0, 0, 0]
+
+
 def test_encoder_step_reports_on_the_host():
     from objectcentricocccompletion_amd import _lib as L
     from objectcentricocccompletion_amd.occ.layers import SimpleEncoderLayer, TemporalCache, TransformerEncoder

@@ -836,6 +836,41 @@ int ococc_occ_frame_fill(const float* logits, const uint8_t* observed, const uin
                          ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * occupancy-enhanced scene cloud (csrc/occ_merge.hip): the frame's cloud followed by the completed-occupancy cells that
+ * pass the score test, behind occ_ops.occ_merge and the ``merged=`` result of TrackletRoIHeadOCC.simple_test_scene_step.
+ * Replaces, for a cloud and cells already on the device, the column slice, `occ_points[:, -1] > score_threshold`, the
+ * np.pad calls and the np.concatenate of LoadPointsAndOccPredFromFile.__call__ and LoadOccPredFromFile.__call__
+ *   (mmdet3d/datasets/pipelines/occ_pinelines.py:639-694 and :757-805).
+ * points [N, C] f32 row-major, the scene cloud.  use_dim: a HOST array of D column indices, 3 <= D <= 16, each in
+ *   [0, C), repeats allowed, the first three taken as x, y, z; checked here, passed to the kernel by value.
+ * occ [M, 4] f32 (x, y, z, value), the packed rows of ococc_occ_frame_fill; start [R + 1] i64 on the device, the
+ *   exclusive prefix of the cells per row: cell m belongs to row r with start[r] <= m < start[r + 1].
+ * The score of a cell is row_score[r] (row_score [R] f32), or with row_score NULL column 3 of the cell (what the
+ *   exported files carry there).  A cell survives iff score > score_threshold in f32 -- strict; a NaN score never
+ *   survives -- and, with flags [M] u8 given and drop_observed != 0, (flags[m] & 2) == 0 (no real point fell into it).
+ * Tiles: 1024 consecutive cells of one row, at most ococc_occ_select_max_tiles(M, R) of them, one wave per tile.
+ * ococc_occ_merge_count checks start on the device in a one-wave launch of its own: start[r] >= 0,
+ *   start[r] <= start[r + 1], start[R] <= M.  A table that fails is not read through: tile_start = 0, no tile runs and
+ *   row_counts [R] i64 = -1 (the caller reports it after its read-back, as with ococc_tune_sample_count).  Otherwise it
+ *   writes tile_start [R + 1] i64, tile_counts [max_tiles] i32 (0 for the unused tail) and row_counts, the survivors
+ *   per row (one integer atomic per tile).
+ * ococc_occ_merge_fill: given tile_scan [max_tiles] i64, the exclusive prefix of tile_counts, and K, their sum, writes
+ *   merged [N + K, D + 2] f32 in ONE launch with two block roles:
+ *     row i < N: points[i, use_dim[j]] for j < D, then 0.0f, 0.0f;
+ *     row N + k: the k-th survivor in input order: its x, y, z, 0.0f for the D - 3 other attributes, its score, 1.0f.
+ *   One thread per output element.  Every value is copied as a 32-bit word: a NaN or denormal passes bit for bit.
+ *   K == 0 (or M == 0, R == 0): the real rows only, nothing of occ / start / tile_scan is read.
+ * N == 0, M == 0 and R == 0 are empty parts, not errors.  Integer atomics only; the same input gives the same bytes.
+ * ------------------------------------------------------------------------ */
+int ococc_occ_merge_count(const float* occ, int64_t M, const int64_t* start, int32_t R, const float* row_score,
+                          const uint8_t* flags, int32_t drop_observed, float score_threshold, int64_t* tile_start,
+                          int32_t* tile_counts, int64_t max_tiles, int64_t* row_counts, ococc_stream_t stream);
+int ococc_occ_merge_fill(const float* points, int64_t N, int32_t C, const int32_t* use_dim, int32_t D, const float* occ,
+                         int64_t M, const int64_t* start, const int64_t* tile_start, int32_t R, const float* row_score,
+                         const uint8_t* flags, int32_t drop_observed, float score_threshold, const int64_t* tile_scan,
+                         int64_t max_tiles, float* merged, int64_t K, ococc_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * observation sample of one online step (csrc/tune_sample.hip): the rows the shape latent of a step is tuned against,
  * behind occ_ops.tune_sample and the ``tune=`` argument of OccBBoxHead.forward_step / forward_steps.  Replaces, for the
  * step, OccAutoEncoder.sample_observation with balance_sample and its cap

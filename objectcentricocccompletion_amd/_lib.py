@@ -138,6 +138,9 @@ SIGNATURES = {
     'ococc_occ_frame_count': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp, c_vp]),
     'ococc_occ_frame_fill': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_f32, c_vp, c_i64, c_vp, c_vp, c_f32,
                                      c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'ococc_occ_merge_count': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    'ococc_occ_merge_fill': (c_i32, [c_vp, c_i64, c_i32, ctypes.POINTER(c_i32), c_i32, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp,
+                                     c_vp, c_i32, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp]),
     'ococc_tune_sample_count': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'ococc_tune_sample_fill': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        c_vp, c_i64, c_vp]),

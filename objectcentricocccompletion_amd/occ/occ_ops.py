@@ -580,3 +580,117 @@ def tune_sample_aten(sizes, dims, start, total, voxel_size, local_xyz, pts_roi, 
     xyz = coors.to(torch.float) * voxel_size + (-sizes / 2)[rbox] + voxel_size / 2   # dense_voxel_centers_batched's
     weights = (torch.ones(K, dtype=torch.float32, device=dev) / cnt.to(torch.float32))[rbox]
     return xyz, seen[rows].to(i32), rbox.to(i32), weights, cnt.tolist()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# occupancy-enhanced scene cloud (csrc/occ_merge.hip)
+# 0: occ_merge runs the operator chain occ_merge_aten instead of the kernels
+OCC_MERGE_KERNEL = os.environ.get('OCOCC_OCC_MERGE_KERNEL', '1') != '0'
+
+
+def merge_use_dim(use_dim):
+    """``use_dim`` as a tuple of column indices: an int n means range(n), as the reference's points_use_dim"""
+    if isinstance(use_dim, bool):
+        raise ValueError(f'use_dim is an int or a list of column indices, not {use_dim!r}')
+    if isinstance(use_dim, int):
+        return tuple(range(use_dim))
+    return tuple(int(v) for v in use_dim)
+
+
+def _occ_merge_shapes(L, what, points, occ, counts, use_dim, row_score, flags):
+    """(N, C, M, R, use_dim as a tuple, counts as a list of int) of the inputs of occ_merge / occ_merge_aten, or OcoccError."""
+    if points.dtype != torch.float32 or points.dim() != 2:
+        raise L.OcoccError(f'{what}: points {tuple(points.shape)} {points.dtype} are not f32 [N, C]')
+    if occ.dtype != torch.float32 or occ.dim() != 2 or occ.size(1) != 4:
+        raise L.OcoccError(f'{what}: occ {tuple(occ.shape)} {occ.dtype} is not f32 [M, 4] (x, y, z, value)')
+    N, C, M = points.size(0), points.size(1), occ.size(0)
+    dim = merge_use_dim(use_dim)
+    if not 3 <= len(dim) <= 16 or min(dim) < 0 or max(dim) >= C:
+        raise L.OcoccError(f'{what}: use_dim {dim!r} is not 3 to 16 columns of a cloud with {C} (x, y, z first)')
+    counts = [int(c) for c in counts]
+    if any(c < 0 for c in counts) or sum(counts) != M:
+        raise L.OcoccError(f'{what}: counts {counts if len(counts) <= 8 else counts[:8] + ["..."]} do not sum to the {M} rows of occ')
+    R = len(counts)
+    if row_score is not None and (row_score.dtype != torch.float32 or tuple(row_score.shape) != (R,)):
+        raise L.OcoccError(f'{what}: row_score {tuple(row_score.shape)} {row_score.dtype} is not f32 [{R}]')
+    if flags is not None and (flags.dtype != torch.uint8 or tuple(flags.shape) != (M,)):
+        raise L.OcoccError(f'{what}: flags {tuple(flags.shape)} {flags.dtype} are not uint8 [{M}]')
+    return N, C, M, R, dim, counts
+
+
+def occ_merge(points, occ, counts, use_dim=(0, 1, 2, 3, 4), row_score=None, flags=None, drop_observed=False,
+              score_threshold=0.0):
+    """The occupancy-enhanced cloud of a frame, what LoadPointsAndOccPredFromFile builds from files
+    (mmdet3d/datasets/pipelines/occ_pinelines.py:585-715), from tensors on the device: ``points`` [N, C] f32 the scene
+    cloud, ``occ`` [M, 4] f32 (x, y, z, value) and ``counts`` (a host list, the rows of ``occ`` per object) as
+    occ_frame_select returns them.  Returns (merged [N + K, D + 2] f32, the survivors per object as a list of int):
+
+        row i < N    points[i, use_dim], then 0, 0
+        row N + k    the k-th surviving cell in input order: x, y, z, D - 3 zeros, its score, 1
+
+    The score of a cell is ``row_score[object]`` (f32 [R]) or, without it, column 3 of the cell -- the exported files
+    carry the object's score there.  A cell survives iff score > score_threshold in f32 (strict, as
+    ``occ_points[:, -1] > self.score_threshold``; a NaN score never survives) and, with ``flags`` (uint8 [M], bit 1: a real
+    point of the frame fell into the cell) and ``drop_observed``, its bit 1 is clear.  Values are copied bit for bit.
+    One table and one count launch, one cumsum, ONE read-back (the survivors per object; K is their sum), one fill launch
+    that also copies the real rows (csrc/occ_merge.hip); without cells the count launches and the read-back are skipped.
+    ``occ_merge_aten`` is the same result as a torch operator chain: what OCOCC_OCC_MERGE_KERNEL=0 runs."""
+    import ctypes
+    from .. import _lib as L
+    from ..tracklet import host_index
+    N, C, M, R, dim, counts = _occ_merge_shapes(L, 'occ_merge', points, occ, counts, use_dim, row_score, flags)
+    L.require_device(points, occ, row_score, flags)
+    if not OCC_MERGE_KERNEL:
+        return occ_merge_aten(points, occ, counts, dim, row_score, flags, drop_observed, score_threshold)
+    dev = points.device
+    D = len(dim)
+    points, occ = points.contiguous(), occ.contiguous()
+    row_score = row_score.contiguous() if row_score is not None else None
+    flags = flags.contiguous() if flags is not None and drop_observed else None
+    tiles = int(L.lib.ococc_occ_select_max_tiles(M, R))
+    start = tile_start = scan = None
+    kept = [0] * R
+    if M:
+        prefix = [0]
+        for c in counts:
+            prefix.append(prefix[-1] + c)
+        start = host_index(prefix, dev)
+        tile_start = L.empty((R + 1,), torch.int64, dev)
+        tile_counts = L.empty((tiles,), torch.int32, dev)
+        row_counts = L.empty((R,), torch.int64, dev)
+        L.check(L.lib.ococc_occ_merge_count(L.ptr(occ), M, L.ptr(start), R, L.ptr(row_score), L.ptr(flags),
+                                            int(flags is not None), float(score_threshold), L.ptr(tile_start),
+                                            L.ptr(tile_counts), tiles, L.ptr(row_counts), L.stream()), 'occ_merge_count')
+        scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts
+        kept = [int(v) for v in row_counts.tolist()]   # the one read-back
+        if min(kept) < 0:
+            raise L.OcoccError(f'occ_merge: start is not an ascending table inside [0, {M}]')
+    K = sum(kept)
+    merged = L.empty((N + K, D + 2), torch.float32, dev)
+    L.check(L.lib.ococc_occ_merge_fill(L.ptr(points), N, C, (ctypes.c_int32 * D)(*dim), D, L.ptr(occ), M, L.ptr(start),
+                                       L.ptr(tile_start), R, L.ptr(row_score), L.ptr(flags), int(flags is not None),
+                                       float(score_threshold), L.ptr(scan), tiles, L.ptr(merged), K, L.stream()),
+            'occ_merge_fill')
+    return merged, kept
+
+
+def occ_merge_aten(points, occ, counts, use_dim=(0, 1, 2, 3, 4), row_score=None, flags=None, drop_observed=False,
+                   score_threshold=0.0):
+    """``occ_merge`` as an operator chain on any device, bit for bit the same rows: a column index, a compare, a boolean
+    index, zero / one columns and two ``cat``.  What OCOCC_OCC_MERGE_KERNEL=0 selects and what the kernels are timed
+    against."""
+    from .. import _lib as L
+    N, C, M, R, dim, counts = _occ_merge_shapes(L, 'occ_merge_aten', points, occ, counts, use_dim, row_score, flags)
+    dev = points.device
+    D = len(dim)
+    head = torch.cat([points[:, list(dim)], points.new_zeros((N, 2))], 1)
+    if M == 0:
+        return head, [0] * R
+    row = torch.repeat_interleave(torch.arange(R, device=dev), torch.tensor(counts, device=dev), output_size=M)
+    score = row_score[row] if row_score is not None else occ[:, 3]
+    keep = score > torch.full((), float(score_threshold), dtype=torch.float32, device=dev)
+    if flags is not None and drop_observed:
+        keep = keep & ((flags & 2) == 0)
+    tail = torch.cat([occ[keep, :3], occ.new_zeros((int(keep.sum()), D - 3)), score[keep][:, None]], 1)
+    tail = torch.cat([tail, torch.ones_like(tail[:, :1])], 1)
+    return torch.cat([head, tail], 0), torch.bincount(row[keep], minlength=R).tolist()

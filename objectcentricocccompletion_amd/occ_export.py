@@ -49,3 +49,10 @@ def load_frame_occ(root, segment, ts, types=None):
         names = [n for n in names if n[:-4].split('_', 1)[0] in types]
     parts = [read_occ_bin(os.path.join(folder, n)) for n in names]
     return np.concatenate(parts, 0) if parts else np.zeros((0, 4), np.float32)
+
+
+def occ_pred_filename(root, segment, ts, per_object_occ):
+    """What WaymoDatasetWithPredOCC.get_data_info puts into results['occ_pred_filename']
+    (mmdet3d/datasets/waymo_dataset.py:1572-1575): the frame's directory of per-object files -- the layout above -- with
+    ``per_object_occ``, else one file ``<root>/<segment>/<timestamp>.bin`` per frame."""
+    return os.path.join(root, segment, f'{ts}' if per_object_occ else f'{ts}.bin')

@@ -77,6 +77,116 @@ class LoadTrackletPoints(object):
         return out_p, out_f
 
 
+def _use_dim(use_dim, load_dim, what):
+    use_dim = list(range(use_dim)) if isinstance(use_dim, int) else list(use_dim)
+    assert max(use_dim) < load_dim, f'Expect all used dimensions < {load_dim}, got {use_dim} ({what})'
+    return use_dim
+
+
+def _load_occ_pred(path, load_dim, use_dim):
+    """The cells of ``path``: one .bin file, or every *.bin of a directory in SORTED file-name order, as float32
+    [m, len(use_dim)]; FileNotFoundError for a missing path (occ_pinelines.py:641-654, 765-778)."""
+    import glob
+    import os
+    if path.endswith('.bin'):
+        occ = np.fromfile(path, dtype=np.float32)
+    else:
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        occ = np.concatenate([np.fromfile(f, dtype=np.float32) for f in sorted(glob.glob(os.path.join(path, '*.bin')))], axis=0)
+    return occ.reshape(-1, load_dim)[:, use_dim]
+
+
+def _pad_occ_points(occ, extra_dim):
+    """x, y, z, ``extra_dim`` zeros, the score, 1 (occ_pinelines.py:680-690, 792-802)"""
+    if extra_dim > 0:
+        occ = np.concatenate([np.pad(occ[:, :3], ((0, 0), (0, extra_dim)), mode='constant', constant_values=0), occ[:, 3:]],
+                             axis=-1)
+    return np.pad(occ, ((0, 0), (0, 1)), mode='constant', constant_values=1)
+
+
+@PIPELINES.register_module()
+class LoadPointsAndOccPredFromFile(object):
+    """The frame's cloud (results['pts_filename'], float32 rows of points_load_dim) followed by its completed-occupancy
+    cells (results['occ_pred_filename']: a .bin file or a directory of per-object *.bin files, rows of occs_load_dim) as
+    ONE array results['points'] [N + K, len(points_use_dim) + 2] float32: a real point keeps its used columns and gets
+    0, 0; a cell keeps x, y, z, gets zeros for the other attributes, its score and 1
+    (mmdet3d/datasets/pipelines/occ_pinelines.py:585-715; occ_ops.occ_merge builds the same array on the device).  A cell
+    is kept iff its last used column is > score_threshold, when the draw ``torch.rand(1) <= filter_prob`` says so -- the
+    draw is made once per call, after the cells are read and only if they were (a missing path draws nothing), as in the
+    reference.  ``tanh_dim``: columns (> 2) of the real points that go through tanh.  ``drop_occ_ratio`` is accepted and
+    unused, as upstream.  Numpy on the host; ``points`` is a plain array where the reference wraps a LiDARPoints.  A
+    directory is read in sorted file-name order: the reference takes glob's order, which is unspecified."""
+
+    def __init__(self, coord_type, points_load_dim=6, occs_load_dim=4, points_use_dim=[0, 1, 2], occs_use_dim=[0, 1, 2, 3],
+                 file_client_args=dict(backend='disk'), tanh_dim=None, score_threshold=0.0, filter_prob=1.0,
+                 drop_occ_ratio=0.0):
+        assert coord_type in ['CAMERA', 'LIDAR', 'DEPTH']
+        self.coord_type = coord_type
+        self.points_load_dim, self.points_use_dim = points_load_dim, _use_dim(points_use_dim, points_load_dim, 'points')
+        self.occs_load_dim, self.occs_use_dim = occs_load_dim, _use_dim(occs_use_dim, occs_load_dim, 'occs')
+        self.file_client_args = dict(file_client_args)
+        self.tanh_dim, self.score_threshold, self.filter_prob, self.drop_occ_ratio = tanh_dim, score_threshold, filter_prob, drop_occ_ratio
+
+    def __call__(self, results):
+        width = len(self.points_use_dim) + 2
+        try:
+            occ = _load_occ_pred(results['occ_pred_filename'], self.occs_load_dim, self.occs_use_dim)
+            if torch.rand(1) <= self.filter_prob:
+                occ = occ[occ[:, -1] > self.score_threshold]
+            if len(occ) == 0:
+                occ = np.zeros((0, width), dtype=np.float32)
+        except FileNotFoundError:
+            occ = np.zeros((0, width), dtype=np.float32)
+        points = np.fromfile(results['pts_filename'], dtype=np.float32).reshape(-1, self.points_load_dim)[:, self.points_use_dim]
+        if self.tanh_dim is not None:
+            assert isinstance(self.tanh_dim, list)
+            assert max(self.tanh_dim) < points.shape[1]
+            assert min(self.tanh_dim) > 2
+            points[:, self.tanh_dim] = np.tanh(points[:, self.tanh_dim])
+        if len(occ) > 0:
+            assert occ.shape[-1] == 4, f'Expect occ points to have 4 dimensions, got {occ.shape[-1]}'
+            occ = _pad_occ_points(occ, points.shape[-1] - 3)
+        points = np.pad(points, ((0, 0), (0, 2)), mode='constant', constant_values=0)
+        results['points'] = np.concatenate([points, occ], axis=0)
+        return results
+
+
+@PIPELINES.register_module()
+class LoadOccPredFromFile(object):
+    """LoadPointsAndOccPredFromFile for a cloud that an earlier step loaded: results['points'] [N, D] float32 gets two
+    zero columns and the kept cells of results['occ_pred_filename'] below it (occ_pinelines.py:719-806).  No draw: the
+    score test always applies.  Without a kept cell (or without the path) the result is the padded cloud, with a warning
+    as upstream."""
+
+    def __init__(self, coord_type, occs_load_dim=4, occs_use_dim=[0, 1, 2, 3], file_client_args=dict(backend='disk'),
+                 score_threshold=0.0):
+        assert coord_type in ['CAMERA', 'LIDAR', 'DEPTH']
+        self.coord_type = coord_type
+        self.occs_load_dim, self.occs_use_dim = occs_load_dim, _use_dim(occs_use_dim, occs_load_dim, 'occs')
+        self.file_client_args = dict(file_client_args)
+        self.score_threshold = score_threshold
+
+    def __call__(self, results):
+        points = np.asarray(results['points'], dtype=np.float32)
+        dim = points.shape[1]
+        points = np.concatenate([points, np.zeros((len(points), 2), dtype=np.float32)], axis=1)
+        path = results['occ_pred_filename']
+        try:
+            occ = _load_occ_pred(path, self.occs_load_dim, self.occs_use_dim)
+            occ = occ[occ[:, -1] > self.score_threshold]
+            if len(occ) == 0:
+                warnings.warn(f'No occ points with score > {self.score_threshold} in {path}')
+        except FileNotFoundError:
+            warnings.warn(f'No occ prediction file {path}')
+            occ = np.zeros((0, dim + 2), dtype=np.float32)
+        if len(occ) > 0:
+            assert occ.shape[-1] == 4, f'Expect occ points to have 4 dimensions, got {occ.shape[-1]}'
+            points = np.concatenate([points, _pad_occ_points(occ, dim - 3)], axis=0)
+        results['points'] = points
+        return results
+
+
 @PIPELINES.register_module()
 class LoadTrackletAnnotations(object):
     """tracklet_pipelines.py:94-101."""

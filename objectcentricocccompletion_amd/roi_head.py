@@ -526,6 +526,37 @@ class TrackletRoIHeadOCC(nn.Module):
             raise ValueError(f'test_cfg.online_occ.chunk is the number of cells per decoder call, an int >= 1, not {chunk!r}')
         return dict(observed=bool(cfg.get('observed', True)), chunk=chunk)
 
+    def online_merged_cfg(self, merged=True):
+        """What ``merged`` of simple_test_scene_step asks for: test_cfg.online_merged (a key of this package, absent by
+        default), overridden key by key by ``merged`` when that is a dict.  Keys: ``use_dim`` (the cloud's columns that are
+        kept, default 5; an int n means range(n) as the reference's points_use_dim; 3 to 16 columns, x, y, z first),
+        ``score_threshold`` (default 0.0: a cell survives iff its row's score is greater) and ``drop_observed`` (default
+        False; True: a cell a real point of the frame fell into is left out).  Returns dict(use_dim as a tuple,
+        score_threshold, drop_observed)."""
+        from .occ.occ_ops import merge_use_dim
+        keys = {'use_dim', 'score_threshold', 'drop_observed'}
+        cfg = self.test_cfg.get('online_merged', None) or {}
+        if not isinstance(cfg, dict) or set(cfg) - keys:
+            raise ValueError(f'test_cfg.online_merged is a dict with the keys use_dim, score_threshold and drop_observed, not {cfg!r}')
+        if isinstance(merged, dict):
+            if set(merged) - keys:
+                raise ValueError(f'merged is True or a dict with the keys use_dim, score_threshold and drop_observed, not {merged!r}')
+            cfg = dict(cfg, **merged)
+        elif merged is not True:
+            raise ValueError(f'merged is True or a dict with the keys use_dim, score_threshold and drop_observed, not {merged!r}')
+        use_dim, thr, drop = cfg.get('use_dim', 5), cfg.get('score_threshold', 0.0), cfg.get('drop_observed', False)
+        try:
+            dim = merge_use_dim(use_dim)
+        except (TypeError, ValueError):
+            dim = ()
+        if not 3 <= len(dim) <= 16 or min(dim) < 0:
+            raise ValueError(f'online_merged.use_dim is an int or a list of 3 to 16 column indices (x, y, z first), not {use_dim!r}')
+        if isinstance(thr, bool) or not isinstance(thr, (int, float)):
+            raise ValueError(f'online_merged.score_threshold is a number, not {thr!r}')
+        if not isinstance(drop, bool):
+            raise ValueError(f'online_merged.drop_observed is a bool, not {drop!r}')
+        return dict(use_dim=dim, score_threshold=float(thr), drop_observed=drop)
+
     def _step_occ(self, res, rois, cfg, transforms=None):
         """The three ``occ`` keys of a step from what the head returned with return_points: the grid of every row's INPUT
         box decoded from the fused latent, joined with the cells the row's pooled points fell into
@@ -553,7 +584,8 @@ class TrackletRoIHeadOCC(nn.Module):
         return torch.cat([centre, b[:, 3:6], torch.atan2(t[:, 0], t[:, 1])[:, None]], 1).to(boxes.dtype)
 
     @torch.no_grad()
-    def simple_test_scene_step(self, points, pose, boxes, scores, labels, slot, state, gt_rois=None, occ=False, tune=None):
+    def simple_test_scene_step(self, points, pose, boxes, scores, labels, slot, state, gt_rois=None, occ=False, tune=None,
+                               merged=None):
         """simple_test_step from what a sensor frame brings: ``points`` [N, >= 3 + attr] f32, the scene cloud of the frame in
         its own ego frame; ``pose``, the 4x4 ego -> world of the frame (numpy or torch); ``boxes`` [n, 7], ``scores`` [n],
         ``labels`` [n], the tracker's output for the frame in the same ego frame; ``slot`` and ``state`` as in
@@ -575,8 +607,18 @@ class TrackletRoIHeadOCC(nn.Module):
         the matrix ``boxes_ego`` uses, applied in the fill kernel --, ``occ_flags`` and ``occ_counts``.  ``tune`` is that of
         simple_test_step.
 
+        ``merged=True`` (test_cfg.online_merged, or a dict that overrides it: online_merged_cfg) implies ``occ=True`` and
+        adds the occupancy-enhanced cloud of the frame, the array LoadPointsAndOccPredFromFile builds from files
+        (occ_ops.occ_merge, csrc/occ_merge.hip): ``points_merged`` [N + K, D + 2] f32 -- ``points[:, use_dim]`` with two zero
+        columns, then the surviving rows of ``occ_ego`` as x, y, z, D - 3 zeros, the row's score, 1 -- and
+        ``merged_counts``, the survivors per input row as a list of int on the host.  The score of a row is what
+        tools/online_raw.py writes into column 3 of its files: where(valid, refined score, input score) as f32.  Without
+        ``merged`` nothing of this is launched and the keys are absent.  A frame without boxes (n == 0) with ``merged`` is
+        not stepped: every key of the step is empty and ``points_merged`` is the cloud with its two zero columns.
+
         Reported on the host before anything is launched: what simple_test_step reports, a pose that is not 4x4 or not
         finite (OcoccError), a slot in mid-tracklet without an origin -- it was stepped through simple_test_step
+        (OcoccError), a wrong ``merged`` or test_cfg.online_merged (ValueError), a ``use_dim`` beyond the cloud's columns
         (OcoccError)."""
         import numpy as np
         from . import _lib as L
@@ -584,6 +626,11 @@ class TrackletRoIHeadOCC(nn.Module):
         from .tracklet import host_index
         if self.training:
             raise RuntimeError('simple_test_scene_step is inference only: call .eval() first')
+        merged_cfg = None
+        if merged is not None and merged is not False:
+            merged_cfg, occ = self.online_merged_cfg(merged), True
+            if points.dim() != 2 or max(merged_cfg['use_dim']) >= points.size(1):
+                raise L.OcoccError(f'merged: use_dim {merged_cfg["use_dim"]} of a cloud {tuple(points.shape)}')
         pose64 = np.asarray(pose.detach().cpu().numpy() if torch.is_tensor(pose) else pose, dtype=np.float64)
         if pose64.shape != (4, 4) or not np.isfinite(pose64).all():
             raise L.OcoccError(f'pose must be a finite 4x4 ego -> world matrix, got shape {pose64.shape}')
@@ -607,6 +654,15 @@ class TrackletRoIHeadOCC(nn.Module):
         n, dev = boxes.size(0), boxes.device
         if len(slots) != n or scores.size(0) != n or labels.size(0) != n:
             raise L.OcoccError(f'{len(slots)} slots, {scores.size(0)} scores, {labels.size(0)} labels for {n} boxes')
+        if n == 0 and merged_cfg is not None:                          # a frame without tracks: its cloud, nothing to step
+            from .occ.occ_ops import occ_merge
+            feats = boxes.new_zeros((0, self.bbox_head.roi_feature_channels))
+            out = dict(boxes=boxes.new_zeros((0, 7)), scores=scores.new_zeros((0,)), labels=labels.new_zeros((0,)),
+                       valid=torch.zeros((0,), dtype=torch.bool, device=dev), fused_roi_feats=feats, ori_roi_feats=feats,
+                       occ_ego=boxes.new_zeros((0, 4)), occ_flags=torch.zeros((0,), dtype=torch.uint8, device=dev),
+                       occ_counts=[], boxes_ego=boxes.new_zeros((0, 7)), num_points=torch.zeros((0,), dtype=torch.long))
+            out['points_merged'], out['merged_counts'] = occ_merge(points, out['occ_ego'], [], merged_cfg['use_dim'])
+            return out
         cfg = dict(self.SCENE_ROWS_DEFAULTS, **(self.test_cfg.get('scene_rows', None) or {}))
         for s in slots:
             if state.frames[s] == 0:
@@ -625,6 +681,13 @@ class TrackletRoIHeadOCC(nn.Module):
         out['boxes_ego'] = torch.where(out['valid'].to(dev).bool()[:, None], self._boxes_through(out['boxes'], mats[1]),
                                        boxes[:, :7])
         out['num_points'] = counts
+        if merged_cfg is not None:
+            from .occ.occ_ops import occ_merge
+            row_score = torch.where(out['valid'].to(dev).bool(), out['scores'].float(), scores.float())
+            out['points_merged'], out['merged_counts'] = occ_merge(
+                points, out['occ_ego'], out['occ_counts'], merged_cfg['use_dim'], row_score=row_score,
+                flags=out['occ_flags'], drop_observed=merged_cfg['drop_observed'],
+                score_threshold=merged_cfg['score_threshold'])
         return out
 
     def online_chunk(self):

@@ -5,6 +5,7 @@ clouds) stepped through frame by frame, the way the method is deployed -- no tra
 
     python tools/online_raw.py <config> <checkpoint> <raw.yaml> [--slots 64] [--out FILE.bin] [--poses poses.pkl]
                                [--save-occ DIR] [--step-tuning N [--step-tuning-samples S]] [--cfg-options k=v ...]
+                               [--save-merged DIR [--merged-use-dim 5] [--merged-score-threshold 0] [--merged-drop-observed]]
 
 Per segment and frame, in time order: the frame's scene cloud is loaded once, every track that starts at the frame gets a
 free slot of the temporal K/V cache, TrackletRoIHeadOCC.simple_test_scene_step refines all live tracks in one call (crop,
@@ -18,6 +19,11 @@ With --save-occ DIR every step also returns the completed occupancy of its frame
 ``occ_ego``, csrc/occ_frame.hip) and the tool writes ``<DIR>/<segment>/<timestamp>/<type>_<id>.bin`` per frame and object,
 float32 [n, 4]: the cells in the frame's ego frame and the object's refined score of that frame in column 3 -- the layout
 tools/test.py --save-occ writes and occ_export.load_frame_occ reads.  Boxes, scores and cells of a frame come down in one copy.
+With --save-merged DIR every step also returns the occupancy-enhanced cloud of its frame (simple_test_scene_step(...,
+merged=...): ``points_merged``, csrc/occ_merge.hip) and the tool writes ``<DIR>/<segment>/<timestamp>.bin`` per replayed
+frame, float32 [N + K, D + 2]: the first D columns of the frame's cloud with two zero columns, then the cells of the
+frame's objects whose score passes --merged-score-threshold as x, y, z, D - 3 zeros, score, 1 -- the array
+pipelines.LoadPointsAndOccPredFromFile builds from the cloud file and the --save-occ files of the frame.
 Config and checkpoint are loaded as tools/test.py loads them."""
 import argparse
 import os
@@ -48,7 +54,7 @@ def choose_cache(roi_head, longest):
                        f'holds at most {TemporalCache.MAX_LONG_CAP} frames of history')
 
 
-def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_occ=None):
+def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_occ=None, save_merged=None, merged=True):
     """``model``: a TrackletDetectorOCC in eval mode on a ROCm device; ``raw_yaml``: the track-input yaml (path or mapping,
     ctrl_prep.load_config); ``poses``: {timestamp: 4x4 ego -> world} or the path of its pickle (default: the yaml's
     ``poses_path``, else <mm_data_root>/poses.pkl).  Returns (records, state): one record per object of the tracker's
@@ -56,7 +62,10 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_oc
     frame's ego frame, score, num_points: the points in the enlarged box before the cap, refined: whether the head's
     result was taken) -- and the OnlineState, every slot released.  With ``out`` the records are written there as a Waymo
     metrics file.  With ``save_occ`` (a directory) the completed occupancy of every refined frame is written below it, one
-    file per frame and object (occ_export.write_tracklet_occ), and every record gets ``occ_cells``, the rows of its file."""
+    file per frame and object (occ_export.write_tracklet_occ), and every record gets ``occ_cells``, the rows of its file.
+    With ``save_merged`` (a directory) the occupancy-enhanced cloud of every replayed frame is written to
+    <save_merged>/<segment>/<timestamp>.bin (``merged``: True or the dict simple_test_scene_step takes), and every record
+    gets ``merged_cells``, the cells of its object in that file."""
     import numpy as np
     import torch
     from objectcentricocccompletion_amd import _lib as L
@@ -79,6 +88,8 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_oc
     num_points = [[0] * len(t) for t in tracklets]
     refined = [[False] * len(t) for t in tracklets]
     occ_cells = [[0] * len(t) for t in tracklets]
+    merged_cells = [[0] * len(t) for t in tracklets]
+    step_kw = dict(**({'occ': True} if save_occ else {}), **({'merged': merged} if save_merged else {}))
     by_seg = defaultdict(list)
     for k in live:
         by_seg[tracklets[k].segment_name].append(k)
@@ -105,15 +116,21 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_oc
             scores = torch.stack([tracklets[k].scores[i].float() for k, i in rows]).to(dev)
             labels = torch.tensor([WAYMO_TYPE_TO_LABEL[tracklets[k].type] for k, _ in rows], dtype=torch.long).to(dev)
             res = rh.simple_test_scene_step(torch.from_numpy(cloud).to(dev), np.asarray(poses[ts], dtype=np.float64), boxes,
-                                            scores, labels, [slot_of[k] for k, _ in rows], state,
-                                            **({'occ': True} if save_occ else {}))
+                                            scores, labels, [slot_of[k] for k, _ in rows], state, **step_kw)
             valid = res['valid'].to(dev).bool()
             back = torch.cat([res['boxes_ego'], torch.where(valid, res['scores'].float(), scores)[:, None],
                               valid[:, None].float()], 1)
-            if save_occ:                                                  # boxes, scores and cells: still one read-back per frame
-                flat = torch.cat([back.reshape(-1), res['occ_ego'].reshape(-1)]).cpu()
-                back, cells = flat[:back.numel()].view(-1, 9), flat[back.numel():].view(-1, 4).numpy()
-                cuts = np.cumsum([0] + list(res['occ_counts']))
+            if save_occ or save_merged:                                   # boxes, scores, cells, cloud: still one read-back per frame
+                parts = [back] + ([res['occ_ego']] if save_occ else []) + ([res['points_merged']] if save_merged else [])
+                flat = torch.cat([p.reshape(-1) for p in parts]).cpu().split([p.numel() for p in parts])
+                back = flat[0].view(-1, 9)
+                if save_occ:
+                    cells = flat[1].view(-1, 4).numpy()
+                    cuts = np.cumsum([0] + list(res['occ_counts']))
+                if save_merged:
+                    path = os.path.join(save_merged, str(seg), f'{ts}.bin')
+                    os.makedirs(os.path.dirname(path), exist_ok=True)
+                    flat[-1].numpy().tofile(path)
             else:
                 back = back.cpu()                                         # one read-back per frame
             done = []
@@ -126,6 +143,8 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_oc
                     occ_export.write_tracklet_occ(save_occ, seg, [ts], tracklets[k].type, tracklets[k].id, mine,
                                                   [len(mine)])
                     occ_cells[k][i] = len(mine)
+                if save_merged:
+                    merged_cells[k][i] = int(res['merged_counts'][r])
                 if i == len(tracklets[k]) - 1:
                     done.append(slot_of.pop(k))
             if done:
@@ -139,6 +158,8 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_oc
                                 num_points=num_points[k][i], refined=refined[k][i]))
             if save_occ:
                 records[-1]['occ_cells'] = occ_cells[k][i]
+            if save_merged:
+                records[-1]['merged_cells'] = merged_cells[k][i]
             if out:
                 chunks.append(waymo_io._f_bytes(1, waymo_io.lidar2waymo_box(b[i], s[i], t.type, t.segment_name, ts, t.id)))
     if out:
@@ -160,6 +181,15 @@ def parse_args(argv=None):
     ap.add_argument('--save-occ', metavar='DIR', default=None,
                     help='write the completed occupancy of every frame and object below DIR: <segment>/<timestamp>/<type>_<id>.bin, '
                     'float32 [n, 4] in the frame\'s ego frame, the refined score in column 3 (occ_export.load_frame_occ reads it)')
+    ap.add_argument('--save-merged', metavar='DIR', default=None,
+                    help='write the occupancy-enhanced cloud of every replayed frame to DIR/<segment>/<timestamp>.bin, float32 '
+                    '[N + K, D + 2]: the cloud\'s first D columns, 0, 0, then the surviving cells as x, y, z, zeros, score, 1')
+    ap.add_argument('--merged-use-dim', type=int, metavar='D', default=None,
+                    help='columns of the cloud kept under --save-merged (default 5, or test_cfg.online_merged)')
+    ap.add_argument('--merged-score-threshold', type=float, metavar='T', default=None,
+                    help='a cell is kept iff its object\'s score of the frame is > T (default 0, or test_cfg.online_merged)')
+    ap.add_argument('--merged-drop-observed', action='store_true',
+                    help='leave out the cells a real point of the frame fell into')
     ap.add_argument('--step-tuning', type=int, metavar='N', default=None,
                     help='tune the fused shape latent of every live track against the frame\'s own points with N Adam steps '
                     'inside the step (sets test_cfg.online_step_tuning = dict(num_iter=N, downsample_size=S, '
@@ -174,7 +204,25 @@ def parse_args(argv=None):
         ap.error('--step-tuning takes a number of iterations >= 0')
     if args.step_tuning_samples is not None and args.step_tuning is None:
         ap.error('--step-tuning-samples goes with --step-tuning')
+    if args.save_merged is None and (args.merged_use_dim is not None or args.merged_score_threshold is not None
+                                     or args.merged_drop_observed):
+        ap.error('--merged-use-dim, --merged-score-threshold and --merged-drop-observed go with --save-merged')
+    if args.merged_use_dim is not None and not 3 <= args.merged_use_dim <= 6:
+        ap.error('--merged-use-dim takes 3 to 6 columns of the six a cloud file holds')
     return args
+
+
+def merged_arg(args):
+    """the ``merged`` argument of simple_test_scene_step from the --merged-* options: only what was given overrides
+    test_cfg.online_merged"""
+    cfg = {}
+    if args.merged_use_dim is not None:
+        cfg['use_dim'] = args.merged_use_dim
+    if args.merged_score_threshold is not None:
+        cfg['score_threshold'] = args.merged_score_threshold
+    if args.merged_drop_observed:
+        cfg['drop_observed'] = True
+    return cfg or True
 
 
 def main(argv=None):
@@ -200,10 +248,13 @@ def main(argv=None):
     model.eval()
     raw, _ = ctrl_prep.load_config(args.raw_yaml)
     out = args.out or os.path.splitext(ctrl_prep.bin_path_for_split(raw))[0] + '_online.bin'
-    records, _ = replay(model, args.raw_yaml, slots=args.slots, out=out, poses=args.poses, device=dev, save_occ=args.save_occ)
+    records, _ = replay(model, args.raw_yaml, slots=args.slots, out=out, poses=args.poses, device=dev, save_occ=args.save_occ,
+                        save_merged=args.save_merged, merged=merged_arg(args))
     print(f'{len(records)} objects, {sum(r["refined"] for r in records)} refined; wrote {out}')
     if args.save_occ:
         print(f'{sum(r.get("occ_cells", 0) for r in records)} occupancy cells in {args.save_occ}')
+    if args.save_merged:
+        print(f'{sum(r.get("merged_cells", 0) for r in records)} occupancy cells merged into the clouds in {args.save_merged}')
     return out
 
 

@@ -10,7 +10,9 @@
  * maintainer would add in the mmdet3d/ops python files to call it.
  *
  * Conventions (all entry points):
- *   - every pointer is a DEVICE pointer unless the parameter is called host_*;
+ *   - every pointer is a DEVICE pointer unless the parameter is called host_*; arrays `T x[k]`, host_* pointers and
+ *     the descriptor structs (`const ococc_<struct>* x`) are HOST memory, read or written before the call returns.
+ *     The Python binding derives its ctypes signatures from this header by that rule ("C ABI binding");
  *   - the caller owns every buffer, including `workspace` whose size comes from
  *     the matching *_workspace_bytes() query (pure host arithmetic);
  *   - nothing allocates, frees, synchronises or throws; work is queued on
@@ -103,8 +105,8 @@ int64_t ococc_grid_unique_workspace_bytes(int32_t ndim, const int32_t host_dims[
 /* Byte offsets of the cell bitmap (1 bit per cell, row-major over dims) and of its exclusive popcount
  * prefix (one u32 per 32 cells) inside the grid_unique workspace: after ococc_grid_unique_i32 they
  * describe the sorted voxel set and can be handed to ococc_subm_rulebook_build_sorted. */
-int ococc_grid_unique_workspace_layout(int32_t ndim, const int32_t host_dims[4], int64_t* bitmap_offset,
-                                       int64_t* prefix_offset);
+int ococc_grid_unique_workspace_layout(int32_t ndim, const int32_t host_dims[4], int64_t* host_bitmap_offset,
+                                       int64_t* host_prefix_offset);
 int ococc_grid_unique_i32(const int32_t* coors, int64_t n, int32_t ndim, const int32_t host_dims[4],
                           int32_t* out_coors, int64_t out_capacity, int32_t* inv, int32_t* counts,
                           int32_t* num_unique, int32_t* status, void* workspace,
@@ -422,9 +424,9 @@ int64_t ococc_sparse_conv_sorted_lnbwd_partial_rows(int64_t n_out);
  * always bf16 out. */
 /* Same conversion for up to 16 f32 weight tensors in ONE launch (host arrays of device pointers and
  * sizes; argument meaning per entry as ococc_weight_prepare_bf16). */
-int ococc_weight_prepare_multi_bf16(int32_t count, const void* const* w, const int32_t* kvol, const int32_t* cin,
-                                    const int32_t* cout, const int32_t* mode, void* const* wn,
-                                    ococc_stream_t stream);
+int ococc_weight_prepare_multi_bf16(int32_t count, const void* const* host_w, const int32_t* host_kvol,
+                                    const int32_t* host_cin, const int32_t* host_cout, const int32_t* host_mode,
+                                    void* const* host_wn, ococc_stream_t stream);
 
 int ococc_weight_prepare_bf16(const void* w, int32_t w_dtype, int32_t kvol, int32_t cin,
                               int32_t cout, int32_t mode, uint16_t* wn, ococc_stream_t stream);
@@ -455,26 +457,30 @@ int ococc_indice_maxpool_backward(const void* features, const void* out_features
 /* The slab pass of ococc_sparse_conv_wgrad_bf16 (dw == NULL form) for TWO or THREE layers in one launch: arrays of
  * ``count``, shapes 16 x 32, 32 x 64 and 64 x 128 (OCOCC_EUNSUPPORTED otherwise; put the longest first).  Each is a few
  * hundred latency-bound work items that fill a fifth of the chip: side by side they take little more than the longest.
+ * Every host_* argument is a HOST array of ``count`` entries (device pointers or sizes), read before the call returns.
  * Same slabs as separate calls, bit for bit; finish them with ococc_sparse_conv_wgrad_reduce_multi /
  * ococc_backward_param_reduce_multi. */
-int ococc_sparse_conv_wgrad_multi_bf16(int32_t count, const uint16_t* const* x, const uint16_t* const* dy, const int32_t* cin,
-                                       const int32_t* cout, const int32_t* const* indice_pairs,
-                                       const int32_t* const* indice_num, const int32_t* kvol, const int64_t* pair_capacity,
-                                       void* const* workspaces, const int64_t* workspace_bytes, ococc_stream_t stream);
+int ococc_sparse_conv_wgrad_multi_bf16(int32_t count, const uint16_t* const* host_x, const uint16_t* const* host_dy,
+                                       const int32_t* host_cin, const int32_t* host_cout,
+                                       const int32_t* const* host_indice_pairs, const int32_t* const* host_indice_num,
+                                       const int32_t* host_kvol, const int64_t* host_pair_capacity,
+                                       void* const* host_workspaces, const int64_t* host_workspace_bytes,
+                                       ococc_stream_t stream);
 /* Both kinds of end-of-backward parameter-gradient sums in ONE launch: the weight-gradient slab sums of
  * ococc_sparse_conv_wgrad_reduce_multi (first five tables) and the LayerNorm d gamma / d beta column sums of
  * ococc_layernorm_param_reduce_multi (last five); same results as the two calls, bit for bit.  (No reference
  * counterpart: indiceConvBackward and torch's native_layer_norm_backward reduce inside their own kernels.) */
-int ococc_backward_param_reduce_multi(int32_t wcount, const void* const* workspaces, const int32_t* const* indice_nums,
-                                      const int32_t* kvols, const int64_t* elems, float* const* dws, int32_t lcount,
-                                      const void* const* partials, const int32_t* rows, const int32_t* c,
-                                      void* const* dgamma, void* const* dbeta, ococc_stream_t stream);
+int ococc_backward_param_reduce_multi(int32_t wcount, const void* const* host_workspaces,
+                                      const int32_t* const* host_indice_nums, const int32_t* host_kvols,
+                                      const int64_t* host_elems, float* const* host_dws, int32_t lcount,
+                                      const void* const* host_partials, const int32_t* host_rows, const int32_t* host_c,
+                                      void* const* host_dgamma, void* const* host_dbeta, ococc_stream_t stream);
 /* dw == NULL above stops after the per-work-item slabs (left in `workspace`); this call finishes up to 8 such
- * weight gradients in one launch: dw[i][k][e] = sum of the slabs of offset k, fixed order (deterministic).
- * elems[i] = cin * cout of layer i.  Used to move the reductions of a backward pass behind its last kernel. */
-int ococc_sparse_conv_wgrad_reduce_multi(int32_t count, const void* const* workspaces,
-                                         const int32_t* const* indice_nums, const int32_t* kvols,
-                                         const int64_t* elems, float* const* dws, ococc_stream_t stream);
+ * weight gradients in one launch: host_dws[i][k][e] = sum of the slabs of offset k, fixed order (deterministic).
+ * host_elems[i] = cin * cout of layer i.  Used to move the reductions of a backward pass behind its last kernel. */
+int ococc_sparse_conv_wgrad_reduce_multi(int32_t count, const void* const* host_workspaces,
+                                         const int32_t* const* host_indice_nums, const int32_t* host_kvols,
+                                         const int64_t* host_elems, float* const* host_dws, ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * B5  fused LayerNorm + GELU(erf) over feature rows (the norm/act pair that
@@ -515,8 +521,8 @@ int ococc_layernorm_act_dropout_bwd_bf16(const uint16_t* x, const uint16_t* dy, 
  * build_norm_layer(dict(type='LN')) layers use, returns the parameter gradients per layer:
  * mmdet3d/ops/sparse_block.py:216-289). */
 int32_t ococc_layernorm_act_bwd_partial_rows(int64_t n, int32_t c, int32_t dtype);
-int ococc_layernorm_param_reduce_multi(int32_t count, const void* const* partials, const int32_t* rows,
-                                       const int32_t* c, void* const* dgamma, void* const* dbeta,
+int ococc_layernorm_param_reduce_multi(int32_t count, const void* const* host_partials, const int32_t* host_rows,
+                                       const int32_t* host_c, void* const* host_dgamma, void* const* host_dbeta,
                                        ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
@@ -608,8 +614,8 @@ int ococc_tracklet_nonempty(const float* points, int64_t num_points, int32_t poi
  * both in the cloud's frame.  N, n <= 2^31 - 1; N == 0 or n == 0 is an empty result (counts zero-filled).
  * Membership of a point in box b (the same in both passes): the test of ococc_tracklet_crop_count on the untransformed
  *   point, bit for bit (a point may be in several boxes; a NaN x or y is in none, a NaN z passes the height test there
- *   and here), and, with `range`, the WRITTEN xyz (a NaN is outside every range)
- *   strictly inside range = (x0, y0, z0, x1, y1, z1), a HOST array of 6 floats or null.
+ *   and here), and, with `host_range`, the WRITTEN xyz (a NaN is outside every range)
+ *   strictly inside host_range = (x0, y0, z0, x1, y1, z1), a HOST array of 6 floats or null.
  * transforms [n, 12] f32 or null: row b's row-major 3x4 matrix m; the written xyz is
  *   x' = fmaf(z, m02, fmaf(y, m01, fmaf(x, m00, m03))), y' and z' the same with rows 1 and 2 (the identity returns the
  *   input bits, but for -0.0, which becomes +0.0); null: the input bits.
@@ -626,10 +632,10 @@ int ococc_tracklet_nonempty(const float* points, int64_t num_points, int32_t poi
  *   stores only; nothing is written at or past row M. */
 int64_t ococc_scene_rows_workspace_bytes(int64_t num_points, int64_t num_boxes);
 int ococc_scene_rows_count(const float* points, int64_t num_points, int32_t point_dim, const float* crop_boxes,
-                           int64_t num_boxes, const float* transforms, const float* range, int64_t* counts,
+                           int64_t num_boxes, const float* transforms, const float* host_range, int64_t* counts,
                            void* workspace, int64_t workspace_bytes, ococc_stream_t stream);
 int ococc_scene_rows_fill(const float* points, int64_t num_points, int32_t point_dim, const float* crop_boxes,
-                          int64_t num_boxes, const float* transforms, const float* range, int32_t attr_dims,
+                          int64_t num_boxes, const float* transforms, const float* host_range, int32_t attr_dims,
                           const float* row_feats, int32_t row_feat_dim, int64_t max_points, const int64_t* scan_all,
                           const int64_t* scan_out, float* out_xyz, float* out_feats, int64_t* out_row,
                           const void* workspace, int64_t workspace_bytes, ococc_stream_t stream);
@@ -841,7 +847,7 @@ int ococc_occ_frame_fill(const float* logits, const uint8_t* observed, const uin
  * Replaces, for a cloud and cells already on the device, the column slice, `occ_points[:, -1] > score_threshold`, the
  * np.pad calls and the np.concatenate of LoadPointsAndOccPredFromFile.__call__ and LoadOccPredFromFile.__call__
  *   (mmdet3d/datasets/pipelines/occ_pinelines.py:639-694 and :757-805).
- * points [N, C] f32 row-major, the scene cloud.  use_dim: a HOST array of D column indices, 3 <= D <= 16, each in
+ * points [N, C] f32 row-major, the scene cloud.  host_use_dim: a HOST array of D column indices, 3 <= D <= 16, each in
  *   [0, C), repeats allowed, the first three taken as x, y, z; checked here, passed to the kernel by value.
  * occ [M, 4] f32 (x, y, z, value), the packed rows of ococc_occ_frame_fill; start [R + 1] i64 on the device, the
  *   exclusive prefix of the cells per row: cell m belongs to row r with start[r] <= m < start[r + 1].
@@ -856,7 +862,7 @@ int ococc_occ_frame_fill(const float* logits, const uint8_t* observed, const uin
  *   per row (one integer atomic per tile).
  * ococc_occ_merge_fill: given tile_scan [max_tiles] i64, the exclusive prefix of tile_counts, and K, their sum, writes
  *   merged [N + K, D + 2] f32 in ONE launch with two block roles:
- *     row i < N: points[i, use_dim[j]] for j < D, then 0.0f, 0.0f;
+ *     row i < N: points[i, host_use_dim[j]] for j < D, then 0.0f, 0.0f;
  *     row N + k: the k-th survivor in input order: its x, y, z, 0.0f for the D - 3 other attributes, its score, 1.0f.
  *   One thread per output element.  Every value is copied as a 32-bit word: a NaN or denormal passes bit for bit.
  *   K == 0 (or M == 0, R == 0): the real rows only, nothing of occ / start / tile_scan is read.
@@ -865,10 +871,10 @@ int ococc_occ_frame_fill(const float* logits, const uint8_t* observed, const uin
 int ococc_occ_merge_count(const float* occ, int64_t M, const int64_t* start, int32_t R, const float* row_score,
                           const uint8_t* flags, int32_t drop_observed, float score_threshold, int64_t* tile_start,
                           int32_t* tile_counts, int64_t max_tiles, int64_t* row_counts, ococc_stream_t stream);
-int ococc_occ_merge_fill(const float* points, int64_t N, int32_t C, const int32_t* use_dim, int32_t D, const float* occ,
-                         int64_t M, const int64_t* start, const int64_t* tile_start, int32_t R, const float* row_score,
-                         const uint8_t* flags, int32_t drop_observed, float score_threshold, const int64_t* tile_scan,
-                         int64_t max_tiles, float* merged, int64_t K, ococc_stream_t stream);
+int ococc_occ_merge_fill(const float* points, int64_t N, int32_t C, const int32_t* host_use_dim, int32_t D,
+                         const float* occ, int64_t M, const int64_t* start, const int64_t* tile_start, int32_t R,
+                         const float* row_score, const uint8_t* flags, int32_t drop_observed, float score_threshold,
+                         const int64_t* tile_scan, int64_t max_tiles, float* merged, int64_t K, ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * observation sample of one online step (csrc/tune_sample.hip): the rows the shape latent of a step is tuned against,
@@ -1032,9 +1038,9 @@ int ococc_window_attn_bwd_bf16(const uint16_t* q, const uint16_t* k, const uint1
  * dx includes the residual path.  No atomics: bit-reproducible.
  * All four kernels run as persistent workgroups that keep the block's weight fragments in registers.
  * ------------------------------------------------------------------------ */
-int ococc_linear_fragments_bf16(int32_t count, const void* const* src, const int64_t* rows, const int64_t* cols,
-                                const int64_t* row_stride, const int64_t* col_stride, void* const* dst,
-                                ococc_stream_t stream);
+int ococc_linear_fragments_bf16(int32_t count, const void* const* host_src, const int64_t* host_rows,
+                                const int64_t* host_cols, const int64_t* host_row_stride, const int64_t* host_col_stride,
+                                void* const* host_dst, ococc_stream_t stream);
 int64_t ococc_window_tile_plan_workspace_bytes(int64_t num_windows);
 int64_t ococc_window_block_partial_rows(int64_t num_tiles);
 int ococc_window_tile_plan(const int32_t* win_len, const int64_t* win_off, const int32_t* tok, int64_t num_windows,
@@ -1086,14 +1092,15 @@ int ococc_token_ffn_block_bwd_bf16(const uint16_t* x, const uint16_t* dy, int64_
  * xadd_i (optional): a second bf16 [num_tokens, k_i] operand, rows n < add_rows_i of dW use bf16(X + xadd) (the q | k
  * rows of in_proj see x + pos, the v rows x).  The token range is cut into `slabs` (ococc_token_wgrad_slabs) and every
  * slab leaves f32 partials dw_partial_i [slabs, n_i, k_i], db_partial_i [slabs, n_i];
- * ococc_partial_rows_sum_f32 (dst[c] = sum_r src[r][c], fixed order) finishes them.  No atomics. */
+ * ococc_partial_rows_sum_f32 (dst[c] = sum_r src[r][c], fixed order) finishes them.  No atomics.  Entry i of every
+ * host_* table (HOST arrays of `count` entries) describes pair i: host_g[i] = G_i, host_ldg[i] = ldg_i, and so on. */
 int64_t ococc_token_wgrad_slabs(int64_t num_tokens);
-int ococc_token_wgrad_bf16(int32_t count, const void* const* g, const int64_t* ldg, const int64_t* n,
-                           const void* const* x, const void* const* xadd, const int64_t* add_rows, const int64_t* k,
-                           int64_t num_tokens, int64_t slabs, void* const* dw_partial, void* const* db_partial,
-                           ococc_stream_t stream);
-int ococc_partial_rows_sum_f32(int32_t count, const void* const* src, const int64_t* rows, const int64_t* cols,
-                               void* const* dst, ococc_stream_t stream);
+int ococc_token_wgrad_bf16(int32_t count, const void* const* host_g, const int64_t* host_ldg, const int64_t* host_n,
+                           const void* const* host_x, const void* const* host_xadd, const int64_t* host_add_rows,
+                           const int64_t* host_k, int64_t num_tokens, int64_t slabs, void* const* host_dw_partial,
+                           void* const* host_db_partial, ococc_stream_t stream);
+int ococc_partial_rows_sum_f32(int32_t count, const void* const* host_src, const int64_t* host_rows,
+                               const int64_t* host_cols, void* const* host_dst, ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * A6, fused  one per-point layer of the SIR encoders:  y = act(LayerNorm(W x)),  x assembled per row as
@@ -1123,8 +1130,8 @@ int ococc_point_mlp_force_tile(int32_t tile_rows);
 int ococc_point_mlp_pack_f32(const float* w, int32_t n, int32_t k, int64_t row_stride, int64_t col_stride, float* frag,
                              ococc_stream_t stream);
 /* the same for up to 32 matrices in one launch (HOST tables) */
-int ococc_point_mlp_pack_multi_f32(int32_t count, const void* const* w, const int32_t* n, const int32_t* k,
-                                   const int64_t* row_stride, const int64_t* col_stride, void* const* frag,
+int ococc_point_mlp_pack_multi_f32(int32_t count, const void* const* host_w, const int32_t* host_n, const int32_t* host_k,
+                                   const int64_t* host_row_stride, const int64_t* host_col_stride, void* const* host_frag,
                                    ococc_stream_t stream);
 int ococc_point_mlp_fwd_f32(const float* a, int32_t ka, int32_t lda, const float* mul, int32_t ldm, const float* colscale,
                             const float* b, int32_t kb, int32_t ldb, float bscale, const float* v, int32_t kv,
@@ -1140,10 +1147,12 @@ int ococc_point_mlp_segment_argmax(const float* y, const float* seg_max, const i
 int32_t ococc_point_mlp_wgrad_slices(int64_t rows);
 int ococc_point_mlp_wgrad_f32(const float* dz, const float* x_cat, int64_t rows, int32_t n, int32_t k, float* partial,
                               ococc_stream_t stream);
-/* The same product for ``count`` (1..8) layers over the same rows in one launch: dz[j] [rows, n[j]], x_cat[j]
- * [rows, k[j]], partial[j] as above.  (The blocks of one SIR layer's backward.) */
-int ococc_point_mlp_wgrad_multi_f32(int32_t count, const float* const* dz, const float* const* x_cat, int64_t rows,
-                                    const int32_t* n, const int32_t* k, float* const* partial, ococc_stream_t stream);
+/* The same product for ``count`` (1..8) layers over the same rows in one launch: host_dz[j] [rows, host_n[j]],
+ * host_x_cat[j] [rows, host_k[j]], host_partial[j] as above (HOST tables of device pointers and sizes).  (The blocks of one
+ * SIR layer's backward.) */
+int ococc_point_mlp_wgrad_multi_f32(int32_t count, const float* const* host_dz, const float* const* host_x_cat,
+                                    int64_t rows, const int32_t* host_n, const int32_t* host_k, float* const* host_partial,
+                                    ococc_stream_t stream);
 int ococc_point_mlp_bwd_f32(const float* a, int32_t ka, int32_t lda, const float* mul, int32_t ldm, const float* colscale,
                             const float* b, int32_t kb, int32_t ldb, float bscale, const float* v, int32_t kv,
                             const int32_t* inv, int64_t rows, const float* w_frag, const float* wt_frag, int32_t n,
@@ -1186,8 +1195,9 @@ int64_t ococc_sir_layer_fwd_floats(const ococc_sir_layer* layer, int64_t rows, i
 int ococc_sir_layer_fwd_f32(const ococc_sir_layer* layer, const float* features, const float* f_cluster, const int32_t* inv,
                             int64_t rows, int64_t groups, float* slab, float* y_out, float* groups_out,
                             ococc_stream_t stream);
-int ococc_sir_layer_bwd_layout(const ococc_sir_layer* layer, int64_t rows, int64_t groups, int64_t* ln_partial_off,
-                               int64_t* w_partial_off, int64_t* tiles, int32_t* slices, int64_t* total_floats);
+int ococc_sir_layer_bwd_layout(const ococc_sir_layer* layer, int64_t rows, int64_t groups, int64_t* host_ln_partial_off,
+                               int64_t* host_w_partial_off, int64_t* host_tiles, int32_t* host_slices,
+                               int64_t* host_total_floats);
 int ococc_sir_layer_bwd_f32(const ococc_sir_layer* layer, const float* features, const float* f_cluster, const int32_t* inv,
                             int64_t rows, int64_t groups, const float* fwd_slab, const float* y_out, const float* dy,
                             int64_t ld_dy, const float* d_groups, int64_t ld_dgroups, float* slab, float* dfeat,
@@ -1225,9 +1235,10 @@ int ococc_sir_layer_fused_debug(int32_t grid, int32_t timeout_ms);
  * All chains of a call have the same depth (<= 3 blocks) and cluster_cols; <= 8 chains per call.  Block widths: <= 64
  * output channels, the last block <= 64 or 129..144 -- ococc_sir_rel_chain_fwd_floats returns -1 for a chain outside
  * that (run its rel_mlp inside its layer: n_rel > 0).
- *   fwd: slabs[c] (ococc_sir_rel_chain_fwd_floats floats) keeps the inner blocks' rows, gates[c] [rows, n last].
- *   bwd: dgates[c] [rows, n last] -> per block the LayerNorm partial rows [tiles][2][n] and weight-gradient slices
- *        [slices][n][k] inside slabs[c] at the offsets ococc_sir_rel_chain_bwd_layout reports (finish with
+ *   fwd: host_slabs[c] (ococc_sir_rel_chain_fwd_floats floats) keeps the inner blocks' rows, host_gates[c] [rows, n last]
+ *        (HOST tables of `count` device pointers, as `chains` is a HOST array of `count` descriptors).
+ *   bwd: host_dgates[c] [rows, n last] -> per block the LayerNorm partial rows [tiles][2][n] and weight-gradient slices
+ *        [slices][n][k] inside host_slabs[c] at the offsets ococc_sir_rel_chain_bwd_layout reports (finish with
  *        ococc_layernorm_param_reduce_multi); f_cluster receives no gradient (the reference detaches it: voxel_encoder.py:781). */
 typedef struct {
   int32_t n_blocks, cluster_cols;
@@ -1241,14 +1252,15 @@ typedef struct {
   const float* ln_bias[4];
 } ococc_sir_rel_chain;
 int64_t ococc_sir_rel_chain_fwd_floats(const ococc_sir_rel_chain* chain, int64_t rows);
-int ococc_sir_rel_chain_bwd_layout(const ococc_sir_rel_chain* chain, int64_t rows, int64_t* ln_partial_off, int64_t* w_partial_off,
-                                   int64_t* tiles, int32_t* slices, int64_t* total_floats);
+int ococc_sir_rel_chain_bwd_layout(const ococc_sir_rel_chain* chain, int64_t rows, int64_t* host_ln_partial_off,
+                                   int64_t* host_w_partial_off, int64_t* host_tiles, int32_t* host_slices,
+                                   int64_t* host_total_floats);
 int ococc_sir_rel_chains_fwd_f32(int32_t count, const ococc_sir_rel_chain* chains, const float* f_cluster, int64_t rows,
-                                 float* const* slabs, float* const* gates, ococc_stream_t stream);
+                                 float* const* host_slabs, float* const* host_gates, ococc_stream_t stream);
 int ococc_sir_rel_chains_bwd_f32(int32_t count, const ococc_sir_rel_chain* chains, const float* f_cluster, int64_t rows,
-                                 const float* const* fwd_slabs, const float* const* gates, const float* const* dgates,
-                                 float* const* slabs, ococc_stream_t stream);
-int ococc_sir_layer_fused_status(ococc_stream_t stream, int32_t* status);
+                                 const float* const* host_fwd_slabs, const float* const* host_gates,
+                                 const float* const* host_dgates, float* const* host_slabs, ococc_stream_t stream);
+int ococc_sir_layer_fused_status(ococc_stream_t stream, int32_t* host_status);
 
 /* ------------------------------------------------------------------------
  * A9 / A10  f32 matrix products on the bf16 matrix cores at f32-level accuracy: the operand split.
@@ -1352,7 +1364,7 @@ int ococc_temporal_attention_chunk_f32(const float* q, int64_t ldq, const float*
  * (mmdet3d/ops/sst/sst_ops.py:333-360), and PosEncode.forward (occ_base.py:33-57).
  * bf16 operands, f32 accumulation, f32 LayerNorm statistics over the f32 sums, bf16 activations.
  * ococc_pos_encode_bf16: xyz f32 [rows, 3] -> out bf16 [rows, ld], columns [sin(pi 2^l x^) | cos(pi 2^l x^)] in the
- *   reference's [2L][3] order, x^ = x normalised to [-1, 1] by bound = {lo xyz, hi xyz} (HOST pointer; null: x^ = x),
+ *   reference's [2L][3] order, x^ = x normalised to [-1, 1] by host_bound = {lo xyz, hi xyz} (HOST pointer; null: x^ = x),
  *   columns 6L .. ld - 1 zero.
  * ococc_linear_fragments32_bf16: `count` (<= 16) f32 matrices S_i [rows_i, cols_i] (any strides; rows a multiple of
  *   32) -> bf16 operand fragments of v_mfma_f32_32x32x16_bf16, columns zero-padded to padded_cols_i (multiple of 16):
@@ -1364,38 +1376,40 @@ int ococc_temporal_attention_chunk_f32(const float* q, int64_t ldq, const float*
  *   head_out f32 [rows] (the head reads the bf16-rounded activation, as the next Linear would).
  * ococc_occ_mlp_fwd_bf16: the reference's decoder widths, 60 (padded to 64) -> 512 -> 1024 -> 1024 -> 1, in ONE launch;
  *   a 64-row tile's activations stay in LDS between the layers.  pe bf16 [rows, 64] (ococc_pos_encode_bf16), add_rows
- *   f32 [*, 512] with add_index [rows] (the per-RoI half of the first layer); w_frag / ln_weight / ln_bias: HOST tables
+ *   f32 [*, 512] with add_index [rows] (the per-RoI half of the first layer); host_w_frag / host_ln_weight /
+ *   host_ln_bias: HOST tables
  *   of 3 device pointers (fragments of [512, 64], [1024, 512], [1024, 1024]; f32 [n]); GELU after every LayerNorm;
- *   head_weight f32 [1024], head_bias [1] or null; dropout_seeds: HOST array of 3 (read when drop_threshold > 0), the
+ *   head_weight f32 [1024], head_bias [1] or null; host_dropout_seeds: HOST array of 3 (read when drop_threshold > 0), the
  *   masks of ococc_mlp_layer_fwd_bf16 called per layer with the same seeds.  out f32 [rows];  y0_out bf16 [rows, 512]
  *   / y1_out bf16 [rows, 1024]: optional copies of the hidden activations (what a backward pass starts from).
  *   Bit-identical to three ococc_mlp_layer_fwd_bf16 calls.
  * ------------------------------------------------------------------------ */
-int ococc_pos_encode_bf16(const float* xyz, int64_t rows, const float* bound, int32_t num_freqs, uint16_t* out, int32_t ld,
-                          ococc_stream_t stream);
-int ococc_linear_fragments32_bf16(int32_t count, const void* const* src, const int64_t* rows, const int64_t* cols,
-                                  const int64_t* padded_cols, const int64_t* row_stride, const int64_t* col_stride,
-                                  void* const* dst, ococc_stream_t stream);
+int ococc_pos_encode_bf16(const float* xyz, int64_t rows, const float* host_bound, int32_t num_freqs, uint16_t* out,
+                          int32_t ld, ococc_stream_t stream);
+int ococc_linear_fragments32_bf16(int32_t count, const void* const* host_src, const int64_t* host_rows,
+                                  const int64_t* host_cols, const int64_t* host_padded_cols, const int64_t* host_row_stride,
+                                  const int64_t* host_col_stride, void* const* host_dst, ococc_stream_t stream);
 int ococc_mlp_layer_fwd_bf16(const uint16_t* x, int64_t rows, int32_t k, const uint16_t* w_frag, int32_t n,
                              const float* bias, const float* add_rows, const int32_t* add_index, const float* ln_weight,
                              const float* ln_bias, float eps, int32_t act, uint32_t drop_threshold, uint64_t dropout_seed,
                              uint16_t* y, const float* head_weight, const float* head_bias, float* head_out,
                              ococc_stream_t stream);
 int ococc_occ_mlp_fwd_bf16(const uint16_t* pe, int64_t rows, const float* add_rows, const int32_t* add_index,
-                           const void* const* w_frag, const void* const* ln_weight, const void* const* ln_bias, float eps,
-                           const float* head_weight, const float* head_bias, uint32_t drop_threshold,
-                           const uint64_t* dropout_seeds, uint16_t* y0_out, uint16_t* y1_out, float* out,
-                           ococc_stream_t stream);
+                           const void* const* host_w_frag, const void* const* host_ln_weight,
+                           const void* const* host_ln_bias, float eps, const float* head_weight, const float* head_bias,
+                           uint32_t drop_threshold, const uint64_t* host_dropout_seeds, uint16_t* y0_out, uint16_t* y1_out,
+                           float* out, ococc_stream_t stream);
 /* the same launch in a training step: per layer l it also writes the LayerNorm input z_out[l] (bf16 [rows, n_l]; the
  * LayerNorm works on these rounded values), its row statistics stats_out[l] (f32 [rows, 2]: mean, rstd) and the activation
  * y_out[l] (bf16, after GELU and dropout) -- what the backward pass of OccDecoder.forward's conv_occ reads
- * (ococc_layernorm_act_bwd / _dropout_bwd_bf16 with the same (threshold, seed) per layer).  z_out, y_out, stats_out: HOST
- * tables of 3 device pointers, every entry required (a null one is an argument error). */
+ * (ococc_layernorm_act_bwd / _dropout_bwd_bf16 with the same (threshold, seed) per layer).  host_z_out, host_y_out,
+ * host_stats_out: HOST tables of 3 device pointers, every entry required (a null one is an argument error). */
 int ococc_occ_mlp_train_fwd_bf16(const uint16_t* pe, int64_t rows, const float* add_rows, const int32_t* add_index,
-                                 const void* const* w_frag, const void* const* ln_weight, const void* const* ln_bias,
-                                 float eps, const float* head_weight, const float* head_bias, uint32_t drop_threshold,
-                                 const uint64_t* dropout_seeds, void* const* z_out, void* const* y_out,
-                                 void* const* stats_out, float* out, ococc_stream_t stream);
+                                 const void* const* host_w_frag, const void* const* host_ln_weight,
+                                 const void* const* host_ln_bias, float eps, const float* head_weight,
+                                 const float* head_bias, uint32_t drop_threshold, const uint64_t* host_dropout_seeds,
+                                 void* const* host_z_out, void* const* host_y_out, void* const* host_stats_out, float* out,
+                                 ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Test-time tuning of the fused shape latent (OccBBoxHead.online_tuning, ococc_bbox_head.py:402-431;
@@ -1434,23 +1448,25 @@ int ococc_latent_ln_adam_f32(float* e, const float* d_n, float* m, float* v, int
 /* ------------------------------------------------------------------------
  * B6, element-wise halves of the SST input layer, one launch each (the mirror ran 20-50 torch operators per call):
  * ococc_sst_window_coors_i64: get_window_coors (mmdet3d/ops/sst/sst_ops.py:266-313) for BOTH window shifts.
- *   coors int64 [n, 4] (b, z, y, x); shapes as (x, y, z) HOST triples (2-D windows: pass window z = sparse z);
+ *   coors int64 [n, 4] (b, z, y, x); shapes (host_*_shape_xyz) as (x, y, z) HOST triples (2-D windows: pass window z =
+ *   sparse z);
  *   win_ids int64 [2, n] (shift 0 = unshifted, 1 = shifted by half a window), coors_in_win int64 [2, n, 3] (z, y, x).
  * ococc_sst_drop_level_i64: the level / keep decision of SSTInputLayerV2.drop_single_shift
  *   (mmdet3d/models/middle_encoders/sst_input_layer_v2.py:128-148) from one group-rank pass: window population =
- *   counts[conti[i]]; the LAST table row whose [lower, upper) holds it gives level_ids[r] and max_tokens[r] (none: -1,
- *   0); keep[i] = inner[i] < max_tokens.  Table rows are HOST arrays (<= 8).
+ *   counts[conti[i]]; the LAST table row whose [host_lower, host_upper) holds it gives host_level_ids[r] and
+ *   host_max_tokens[r] (none: -1, 0); keep[i] = inner[i] < max_tokens.  The table's columns are HOST arrays (<= 8 rows).
  * ococc_sst_pos_embed: get_pos_embed (sst_input_layer_v2.py:239-305) in flat token order: out [n, feat_dim] f32 / bf16,
  *   columns [x | y | z] blocks of pos_length (sin at even, cos at odd columns of e = p / inv_freq), zero padded;
  *   inv_freq: DEVICE f32 [pos_length], the table the reference builds with torch.pow.
  * ------------------------------------------------------------------------ */
-int ococc_sst_window_coors_i64(const int64_t* coors, int64_t n, const int32_t* sparse_shape_xyz,
-                               const int32_t* window_shape_xyz, int64_t* win_ids, int64_t* coors_in_win,
+int ococc_sst_window_coors_i64(const int64_t* coors, int64_t n, const int32_t* host_sparse_shape_xyz,
+                               const int32_t* host_window_shape_xyz, int64_t* win_ids, int64_t* coors_in_win,
                                ococc_stream_t stream);
 int ococc_sst_drop_level_i64(const int32_t* conti, const int32_t* inner, const int32_t* counts, int64_t n,
-                             int32_t num_levels, const int64_t* lower, const int64_t* upper, const int64_t* max_tokens,
-                             const int64_t* level_ids, uint8_t* keep, int64_t* level, ococc_stream_t stream);
-int ococc_sst_pos_embed(const int64_t* coors_in_win, int64_t n, const int32_t* window_shape_xyz, int32_t ndim,
+                             int32_t num_levels, const int64_t* host_lower, const int64_t* host_upper,
+                             const int64_t* host_max_tokens, const int64_t* host_level_ids, uint8_t* keep, int64_t* level,
+                             ococc_stream_t stream);
+int ococc_sst_pos_embed(const int64_t* coors_in_win, int64_t n, const int32_t* host_window_shape_xyz, int32_t ndim,
                         int32_t normalize_pos, const float* inv_freq, int32_t pos_length, int32_t feat_dim, void* out,
                         int32_t out_dtype, ococc_stream_t stream);
 
@@ -1461,8 +1477,8 @@ int ococc_cast_bf16_to_f32(const uint16_t* src, float* dst, int64_t count, ococc
 /* ---------------------------------------------------------------------------------------------
  * Fused multi-tensor AdamW step, torch.optim.AdamW semantics (amsgrad / maximize off) -- the
  * optimizer the reference configures at configs/_base_/schedules/cosine_2x.py:2-8 (lr override
- * configs/ococc/ococcnet.py:468-470).  params / grads / exp_avg / exp_avg_sq are HOST arrays of
- * num_tensors (<= 48) device pointers to contiguous f32 tensors of numel[i] elements.  `step` is a
+ * configs/ococc/ococcnet.py:468-470).  host_params / host_grads / host_exp_avg / host_exp_avg_sq are HOST arrays of
+ * num_tensors (<= 48) device pointers to contiguous f32 tensors of host_numel[i] elements.  `step` is a
  * DEVICE float holding the number of steps taken so far: the kernel uses step + 1 for the bias
  * corrections; with bump_step = 1 a one-thread kernel queued behind it stores step + 1 (pass 0 on all
  * but the last call when one optimizer step needs several calls), so the sequence can be replayed from
@@ -1470,29 +1486,31 @@ int ococc_cast_bf16_to_f32(const uint16_t* src, float* dst, int64_t count, ococc
  * the first call; launches of up to 2048 workgroups (2 M elements) then store count + 1 from their last
  * workgroup instead of a second launch (larger ones fall back to the one-thread kernel).
  * ------------------------------------------------------------------------------------------- */
-int ococc_adamw_f32(int32_t num_tensors, void* const* params, const void* const* grads,
-                    void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel, float lr,
+int ococc_adamw_f32(int32_t num_tensors, void* const* host_params, const void* const* host_grads,
+                    void* const* host_exp_avg, void* const* host_exp_avg_sq, const int64_t* host_numel, float lr,
                     float beta1, float beta2, float eps, float weight_decay, float* step,
                     int32_t bump_step, ococc_stream_t stream);
 /* The same update with the learning rate read from device memory at run time (one float): a learning-rate schedule
  * (the reference's cyclic policy, configs/_base_/schedules/cosine_2x.py:10-15, applied per iteration by mmcv's
  * CyclicLrUpdaterHook) then takes effect between replays of a captured HIP graph, where a scalar launch argument
  * would stay frozen at its capture-time value. */
-int ococc_adamw_lr_dev_f32(int32_t num_tensors, void* const* params, const void* const* grads,
-                           void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel,
+int ococc_adamw_lr_dev_f32(int32_t num_tensors, void* const* host_params, const void* const* host_grads,
+                           void* const* host_exp_avg, void* const* host_exp_avg_sq, const int64_t* host_numel,
                            const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
                            float* step, int32_t bump_step, ococc_stream_t stream);
 /* The same update that ALSO refreshes the bf16 kernel operands of convolution weights it has just written (what
  * ococc_weight_prepare_multi_bf16 would compute at the start of the next step: one launch less per step).  lr_dev null:
- * lr is used.  Operand o belongs to tensor operand_tensor[o] (an index into params, a contiguous f32 [kvol, cin, cout]),
- * is written in layout operand_mode[o] (the modes of ococc_weight_prepare_bf16, + 4 = fragment-major) to operand_dst[o]
- * (bf16, kvol * cin * cout elements); at most 8 operands per call.  All tables are HOST arrays. */
-int ococc_adamw_operands_f32(int32_t num_tensors, void* const* params, const void* const* grads, void* const* exp_avg,
-                             void* const* exp_avg_sq, const int64_t* numel, float lr, const float* lr_dev, float beta1,
-                             float beta2, float eps, float weight_decay, float* step, int32_t bump_step,
-                             int32_t num_operands, const int32_t* operand_tensor, const int32_t* operand_mode,
-                             const int32_t* operand_kvol, const int32_t* operand_cin, const int32_t* operand_cout,
-                             void* const* operand_dst, ococc_stream_t stream);
+ * lr is used.  Operand o belongs to tensor host_operand_tensor[o] (an index into host_params, a contiguous f32
+ * [kvol, cin, cout]), is written in layout host_operand_mode[o] (the modes of ococc_weight_prepare_bf16, + 4 =
+ * fragment-major) to host_operand_dst[o] (bf16, kvol * cin * cout elements); at most 8 operands per call.  All tables are
+ * HOST arrays. */
+int ococc_adamw_operands_f32(int32_t num_tensors, void* const* host_params, const void* const* host_grads,
+                             void* const* host_exp_avg, void* const* host_exp_avg_sq, const int64_t* host_numel, float lr,
+                             const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float* step,
+                             int32_t bump_step, int32_t num_operands, const int32_t* host_operand_tensor,
+                             const int32_t* host_operand_mode, const int32_t* host_operand_kvol,
+                             const int32_t* host_operand_cin, const int32_t* host_operand_cout,
+                             void* const* host_operand_dst, ococc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Stream timers (HIP events) for the measurement harness (bench.py roofline line).  No reference
@@ -1500,9 +1518,9 @@ int ococc_adamw_operands_f32(int32_t num_tensors, void* const* params, const voi
  * of the HIP graph being captured on `stream`, so that a kernel inside a replayed graph can be
  * timed; the elapsed time is read after the stream has been synchronised.
  * ------------------------------------------------------------------------------------------- */
-int ococc_timer_create(void** timer);
+int ococc_timer_create(void** host_timer);
 int ococc_timer_record(void* timer, int32_t in_graph, ococc_stream_t stream);
-int ococc_timer_elapsed_ms(void* start, void* stop, float* ms);
+int ococc_timer_elapsed_ms(void* start, void* stop, float* host_ms);
 int ococc_timer_destroy(void* timer);
 
 #ifdef __cplusplus

@@ -1,4 +1,5 @@
-"""ctypes binding of ``libococc_hip.so`` (C ABI declared in ``include/ococc_hip.h``).
+"""ctypes binding of ``libococc_hip.so``.  The C ABI is declared in ``include/ococc_hip.h`` and nowhere else: the
+signatures and descriptor structs below are read from the header when this module is imported (``_abi.py``).
 
 The library is the product: there is no CPU or PyTorch fallback behind these
 calls.  Importing this module without the built library raises, and every op
@@ -9,6 +10,8 @@ import os
 
 import torch
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('OCOCC_LIB_PATH') or os.path.join(_HERE, 'libococc_hip.so')   # (the override: diagnostic builds, tools/probe)
 
@@ -16,241 +19,12 @@ F32, BF16 = 0, 1
 REDUCE = {'sum': 0, 'mean': 1, 'avg': 1, 'max': 2}
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
-_F3 = ctypes.c_float * 3
-_F6 = ctypes.c_float * 6
-_I3 = ctypes.c_int32 * 3
-_I4 = ctypes.c_int32 * 4
 
+# ococc_conv_ln: the LayerNorm epilogue of the three convolution exports (pass None for a plain convolution)
+ConvLn = _abi.types['ococc_conv_ln']
 
-class ConvLn(ctypes.Structure):
-    """ococc_conv_ln of include/ococc_hip.h: the LayerNorm epilogue of the three convolution exports (pass None for a
-    plain convolution)"""
-    _fields_ = [('backward', c_i32), ('act', c_i32), ('eps', c_f32), ('gamma', c_vp), ('beta', c_vp), ('y', c_vp),
-                ('mean_rstd', c_vp), ('block_conv_out', c_vp), ('partials', c_vp), ('partial_rows', c_i64)]
-
-
-_LN = ctypes.POINTER(ConvLn)
-
-# name -> (restype, argtypes); one entry per function declared in ococc_hip.h
-SIGNATURES = {
-    'ococc_last_error': (ctypes.c_char_p, []),
-    'ococc_version': (c_i32, []),
-    'ococc_arch': (ctypes.c_char_p, []),
-    'ococc_dynamic_voxelize_f32': (c_i32, [c_vp, c_i64, c_i32, _F3, _F6, c_vp, c_vp]),
-    'ococc_hard_voxelize_workspace_bytes': (c_i64, [c_i64, _F3, _F6]),
-    'ococc_hard_voxelize_f32': (c_i32, [c_vp, c_i64, c_i32, _F3, _F6, c_i32, c_i32, c_vp, c_vp,
-                                        c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_grid_unique_workspace_bytes': (c_i64, [c_i32, _I4]),
-    'ococc_grid_unique_workspace_layout': (c_i32, [c_i32, _I4, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
-    'ococc_grid_unique_i32': (c_i32, [c_vp, c_i64, c_i32, _I4, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
-                                      c_vp, c_i64, c_vp]),
-    'ococc_voxelize_scatter_workspace_bytes': (c_i64, [c_i64, c_i32, _I3]),
-    'ococc_object_grid_geometry_workspace_bytes': (c_i64, [c_i64, c_i32, _I3, c_i32]),
-    'ococc_object_grid_geometry_f32': (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_i32, _F3, _F6, c_i32, _I3, c_i32,
-                                               c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                               c_vp, c_i64, c_vp]),
-    'ococc_object_grid_geometry_order_f32': (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_i32, _F3, _F6, c_i32, _I3, c_i32,
-                                                     c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                                     c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
-    'ococc_voxelize_scatter_mean_f32': (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, c_i32, _F3, _F6, c_i32, _I3,
-                                                c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_occ_visibility_f64': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32,
-                                         c_vp, c_vp, c_vp, c_vp]),
-    'ococc_segment_count_i32': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp]),
-    'ococc_segment_reduce_f32': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64,
-                                         c_vp]),
-    'ococc_segment_reduce_bwd_f32': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp,
-                                             c_i64, c_vp]),
-    'ococc_subm_rulebook_workspace_bytes': (c_i64, [c_i64, c_i32, _I3, _I3]),
-    'ococc_subm_rulebook_build': (c_i32, [c_vp, c_i64, c_i32, _I3, _I3, _I3, c_vp, c_vp, c_vp, c_vp,
-                                          c_vp, c_i64, c_vp]),
-    'ococc_subm_rulebook_build_sorted': (c_i32, [c_vp, c_i64, c_i32, _I3, _I3, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                                 c_i32, c_vp, c_i64, c_vp]),
-    'ococc_conv_rulebook_workspace_bytes': (c_i64, [c_i64, c_i32, _I3, _I3]),
-    'ococc_conv_rulebook_build': (c_i32, [c_vp, c_i64, c_i32, _I3, _I3, _I3, _I3, _I3, c_i32, c_vp, c_i64, c_vp,
-                                          c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_rulebook_pairs_to_table': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i64, c_vp, c_vp,
-                                              c_vp]),
-    'ococc_sparse_conv_wgrad_reduce_multi': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_indice_maxpool': (c_i32, [c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp]),
-    'ococc_indice_maxpool_backward': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp]),
-    'ococc_sparse_conv_wgrad_multi_bf16': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_backward_param_reduce_multi': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_sparse_conv_tile_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp,
-                                            c_i32, _LN, c_vp]),
-    'ococc_sparse_conv_tile_lnbwd_partial_rows': (c_i64, [c_i64, c_i32, c_i32]),
-    'ococc_sparse_conv_gather_gemm_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp,
-                                                   c_vp, c_i64, c_vp, c_vp, c_i32, _LN, c_vp]),
-    'ococc_subm_row_order_scratch_bytes': (c_i64, [c_i64]),
-    'ococc_subm_row_order_counter_bytes': (c_i64, []),
-    'ococc_subm_row_order_place': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_subm_row_order': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_sparse_conv_sorted_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64,
-                                              c_vp, c_vp, c_i32, _LN, c_vp]),
-    'ococc_sparse_conv_sorted_lnbwd_partial_rows': (c_i64, [c_i64]),
-    'ococc_weight_prepare_multi_bf16': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
-                                                ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_vp), c_vp]),
-    'ococc_weight_prepare_bf16': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
-    'ococc_sparse_conv_wgrad_workspace_bytes': (c_i64, [c_i32, c_i64, c_i32, c_i32]),
-    'ococc_sparse_conv_wgrad_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp,
-                                             c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_layernorm_act_fwd': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_i32, c_vp, c_vp,
-                                        c_i32, c_vp]),
-    'ococc_layernorm_act_bwd_workspace_bytes': (c_i64, [c_i64, c_i32]),
-    'ococc_layernorm_act_bwd': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp,
-                                        c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
-    'ococc_layernorm_act_dropout_fwd_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_i32, ctypes.c_uint32,
-                                                     ctypes.c_uint64, c_vp, c_vp, c_vp]),
-    'ococc_layernorm_act_dropout_bwd_bf16': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, ctypes.c_uint32,
-                                                     ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_layernorm_act_bwd_partial_rows': (c_i32, [c_i64, c_i32, c_i32]),
-    'ococc_layernorm_param_reduce_multi': (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_point_pool_workspace_bytes': (c_i64, [c_i64, c_i64]),
-    'ococc_dynamic_point_pool_mixed': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, _F3, c_i32, c_i64, c_vp,
-                                               c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_aligned_iou3d_f32': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
-    'ococc_tracklet_max_iou_f32': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
-    'ococc_tracklet_crop_count': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_tracklet_crop_fill': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp,
-                                         c_vp]),
-    'ococc_tracklet_nonempty': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp]),
-    'ococc_scene_rows_workspace_bytes': (c_i64, [c_i64, c_i64]),
-    'ococc_scene_rows_count': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, ctypes.POINTER(c_f32), c_vp, c_vp, c_i64, c_vp]),
-    'ococc_scene_rows_fill': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, ctypes.POINTER(c_f32), c_i32, c_vp, c_i32, c_i64,
-                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_track_extend_f64': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp,
-                                       c_vp, c_i64, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_frame_match_workspace_bytes': (c_i64, [c_i64]),
-    'ococc_frame_match_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32,
-                                      c_i64, c_i64, c_i32, ctypes.c_float * 5, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_frame_assign_i32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32,
-                                       c_i64, c_i64, c_i32, c_i32, ctypes.c_float * 5, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_occ_iou_count': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_f32, c_vp, c_i64, c_i64, c_vp]),
-    'ococc_occ_loss_masks_pass_rows': (c_i64, []),
-    'ococc_occ_loss_masks_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_i32, c_vp, c_vp, c_vp,
-                                         c_vp]),
-    'ococc_dense_grid_cells_f32': (c_i32, [c_vp, c_vp, c_vp, c_i32, c_f32, c_i64, c_i64, c_vp, c_vp, c_vp]),
-    'ococc_occ_select_max_tiles': (c_i64, [c_i64, c_i32]),
-    'ococc_occ_select_count': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp, c_vp]),
-    'ococc_occ_select_fill': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_f32, c_vp, c_i64, c_vp, c_vp, c_f32, c_i32, c_vp,
-                                      c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
-    'ococc_occ_frame_mark': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp, c_i64, c_vp]),
-    'ococc_occ_frame_count': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp, c_vp]),
-    'ococc_occ_frame_fill': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i32, c_f32, c_vp, c_i64, c_vp, c_vp, c_f32,
-                                     c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_occ_merge_count': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_f32, c_vp, c_vp, c_i64, c_vp, c_vp]),
-    'ococc_occ_merge_fill': (c_i32, [c_vp, c_i64, c_i32, ctypes.POINTER(c_i32), c_i32, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp,
-                                     c_vp, c_i32, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp]),
-    'ococc_tune_sample_count': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
-    'ococc_tune_sample_fill': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                       c_vp, c_i64, c_vp]),
-    'ococc_gt_occ_crop_tiles': (c_i64, [c_i64, c_i64]),
-    'ococc_gt_occ_crop_count': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
-                                        c_vp, c_vp]),
-    'ococc_gt_occ_crop_fill': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
-                                       c_vp, c_vp, c_i64, c_vp]),
-    'ococc_group_rank_workspace_bytes': (c_i64, [c_i64, c_i64]),
-    'ococc_group_rank_i32': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_window_attn_fwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32,
-                                           c_f32, c_vp, c_i64, c_vp, c_f32, c_vp, c_vp]),
-    'ococc_window_attn_bwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
-                                           c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
-                                           c_f32, c_vp, c_vp]),
-    'ococc_linear_fragments_bf16': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
-                                            ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp), c_vp]),
-    'ococc_window_tile_plan_workspace_bytes': (c_i64, [c_i64]),
-    'ococc_window_block_partial_rows': (c_i64, [c_i64]),
-    'ococc_window_tile_plan': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_window_attn_block_fwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
-                                                 c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp]),
-    'ococc_window_attn_block_bwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp,
-                                                 c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                                 c_f32, c_vp, c_vp]),
-    'ococc_token_ffn_block_fwd_bf16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32,
-                                               c_i32, c_vp, c_vp]),
-    'ococc_token_ffn_block_bwd_bf16': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32,
-                                               c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_token_wgrad_slabs': (c_i64, [c_i64]),
-    'ococc_token_wgrad_bf16': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_i64, c_i64, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
-    'ococc_partial_rows_sum_f32': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp), c_vp]),
-    'ococc_point_mlp_fragment_floats': (c_i64, [c_i32, c_i32]),
-    'ococc_point_mlp_tiles': (c_i64, [c_i64]),
-    'ococc_point_mlp_pack_f32': (c_i32, [c_vp, c_i32, c_i32, c_i64, c_i64, c_vp, c_vp]),
-    'ococc_point_mlp_pack_multi_f32': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp), c_vp]),
-    'ococc_point_mlp_fwd_f32': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_i32, c_vp,
-                                        c_i64, c_vp, c_i32, c_vp, c_vp, c_f32, c_i32, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_point_mlp_segment_argmax': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp]),
-    'ococc_point_mlp_wgrad_slices': (c_i32, [c_i64]),
-    'ococc_point_mlp_force_tile': (c_i32, [c_i32]),
-    'ococc_sir_layer_fwd_floats': (c_i64, [c_vp, c_i64, c_i64]),
-    'ococc_sir_layer_fwd_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_sir_layer_bwd_layout': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_sir_layer_bwd_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
-    'ococc_rotate_z_f32': (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
-    'ococc_points_box_to_box_f32': (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
-    'ococc_roi_box_targets_f32': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp]),
-    'ococc_sir_rel_chain_fwd_floats': (c_i64, [c_vp, c_i64]),
-    'ococc_sir_rel_chain_bwd_layout': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_sir_rel_chains_fwd_f32': (c_i32, [c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
-    'ococc_sir_rel_chains_bwd_f32': (c_i32, [c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_sir_layer_set_fused': (c_i32, [c_i32]),
-    'ococc_sir_layer_fused_status': (c_i32, [c_vp, ctypes.POINTER(c_i32)]),
-    'ococc_split3_bf16': (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_vp, c_i32, c_vp]),
-    'ococc_temporal_attention_fwd_f32': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32,
-                                                 c_i32, c_f32, c_f32, ctypes.c_uint64, c_vp, c_vp, c_vp, c_i64, c_vp]),
-    'ococc_temporal_attention_bwd_f32': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32,
-                                                 c_f32, ctypes.c_uint64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp,
-                                                 c_i64, c_vp, c_i64, c_vp]),
-    'ococc_temporal_attention_step_f32': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
-                                                  c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_i64, c_vp]),
-    'ococc_temporal_attention_step_long_f32': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32,
-                                                       c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_vp, c_i64, c_vp]),
-    'ococc_temporal_attention_chunk_f32': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
-                                                   c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_vp, c_i64, c_vp]),
-    'ococc_sir_layer_fused_check': (c_i32, []),
-    'ococc_sir_layer_fused_debug': (c_i32, [c_i32, c_i32]),
-    'ococc_point_mlp_wgrad_f32': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
-    'ococc_point_mlp_wgrad_multi_f32': (c_i32, [c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_point_mlp_bwd_f32': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_i32, c_vp,
-                                        c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
-                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_pos_encode_bf16': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_f32), c_i32, c_vp, c_i32, c_vp]),
-    'ococc_linear_fragments32_bf16': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp), c_vp]),
-    'ococc_mlp_layer_fwd_bf16': (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32,
-                                         ctypes.c_uint32, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    'ococc_occ_mlp_fwd_bf16': (c_i32, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
-                                       c_f32, c_vp, c_vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), c_vp, c_vp, c_vp,
-                                       c_vp]),
-    'ococc_occ_mlp_train_fwd_bf16': (c_i32, [c_vp, c_i64, c_vp, c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
-                                             ctypes.POINTER(c_vp), c_f32, c_vp, c_vp, ctypes.c_uint32,
-                                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
-                                             ctypes.POINTER(c_vp), c_vp, c_vp]),
-    'ococc_occ_tune_head_lnbwd_bf16': (c_i32, [c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp]),
-    'ococc_segment_sum_bf16': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp]),
-    'ococc_latent_ln_adam_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_f32, c_i32, ctypes.c_double,
-                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i32, c_vp, c_vp]),
-    'ococc_sst_window_coors_i64': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_vp, c_vp, c_vp]),
-    'ococc_sst_drop_level_i64': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
-                                         ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_vp, c_vp, c_vp]),
-    'ococc_sst_pos_embed': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i32), c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp]),
-    'ococc_cast_f32_to_bf16': (c_i32, [c_vp, c_vp, c_i64, c_vp]),
-    'ococc_cast_bf16_to_f32': (c_i32, [c_vp, c_vp, c_i64, c_vp]),
-    'ococc_adamw_f32': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
-                                ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_f32, c_f32, c_f32, c_f32, c_f32,
-                                c_vp, c_i32, c_vp]),
-    'ococc_adamw_lr_dev_f32': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
-                                       ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_vp, c_f32, c_f32, c_f32, c_f32,
-                                       c_vp, c_i32, c_vp]),
-    'ococc_adamw_operands_f32': (c_i32, [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
-                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_f32, c_vp, c_f32, c_f32, c_f32, c_f32,
-                                         c_vp, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
-                                         ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
-                                         ctypes.POINTER(c_vp), c_vp]),
-    'ococc_timer_create': (c_i32, [ctypes.POINTER(c_vp)]),
-    'ococc_timer_record': (c_i32, [c_vp, c_i32, c_vp]),
-    'ococc_timer_elapsed_ms': (c_i32, [c_vp, c_vp, ctypes.POINTER(c_f32)]),
-    'ococc_timer_destroy': (c_i32, [c_vp]),
-}
+# name -> (restype, argtypes) of every function include/ococc_hip.h declares, derived from its prototypes (_abi.py)
+SIGNATURES = {name: (res, [ct for ct, _ in params]) for name, (res, params) in _abi.functions.items()}
 
 
 class Timer(object):
@@ -326,20 +100,20 @@ def stream():
 
 
 def f3(v):
-    return _F3(*[float(x) for x in v])
+    return (c_f32 * 3)(*[float(x) for x in v])
 
 
 def f6(v):
-    return _F6(*[float(x) for x in v])
+    return (c_f32 * 6)(*[float(x) for x in v])
 
 
 def i3(v):
-    return _I3(*[int(x) for x in v])
+    return (c_i32 * 3)(*[int(x) for x in v])
 
 
 def i4(v):
     v = list(v) + [1] * (4 - len(v))
-    return _I4(*[int(x) for x in v])
+    return (c_i32 * 4)(*[int(x) for x in v])
 
 
 def dtype_code(dt):

@@ -17,6 +17,7 @@ from torch import nn
 
 from ._lib import const_tensor
 from .linear import Linear
+from . import _abi
 from . import _deferred
 from . import _lib as L
 from .point_mlp import PackPlan, layer_backward, layer_forward, ln_param_grads, pack_weight, point_layer, prepack, refresh_plans
@@ -68,14 +69,7 @@ def check_barriers():
     L.check(L.lib.ococc_sir_layer_fused_check(), 'sir_layer barrier check')
 
 
-class _SirLayerDesc(ctypes.Structure):   # ococc_sir_layer of include/ococc_hip.h
-    _fields_ = [('n_rel', ctypes.c_int32), ('n_vfe', ctypes.c_int32), ('feat_cols', ctypes.c_int32),
-                ('cluster_cols', ctypes.c_int32), ('with_cluster_center', ctypes.c_int32), ('shortcut', ctypes.c_int32),
-                ('bscale', ctypes.c_float), ('inference', ctypes.c_int32), ('rel_colscale', ctypes.c_void_p),
-                ('colscale', ctypes.c_void_p), ('n', ctypes.c_int32 * 8), ('act', ctypes.c_int32 * 8),
-                ('eps', ctypes.c_float * 8), ('w_frag', ctypes.c_void_p * 8), ('wt_frag', ctypes.c_void_p * 8),
-                ('ln_weight', ctypes.c_void_p * 8), ('ln_bias', ctypes.c_void_p * 8), ('gate', ctypes.c_void_p),
-                ('dgate', ctypes.c_void_p)]
+_SirLayerDesc = _abi.types['ococc_sir_layer']   # the struct of include/ococc_hip.h, fields read from the header
 
 
 class _Ptr(object):
@@ -246,11 +240,7 @@ _REL_PLANS = weakref.WeakKeyDictionary()      # SIRLayer -> _RelPlan
 _VFE_PLANS = weakref.WeakKeyDictionary()      # SIRLayer -> _NativePlan of its vfe blocks alone (the gate comes from outside)
 
 
-class _RelChainDesc(ctypes.Structure):   # ococc_sir_rel_chain of include/ococc_hip.h
-    _fields_ = [('n_blocks', ctypes.c_int32), ('cluster_cols', ctypes.c_int32), ('rel_colscale', ctypes.c_void_p),
-                ('n', ctypes.c_int32 * 4), ('act', ctypes.c_int32 * 4), ('eps', ctypes.c_float * 4),
-                ('w_frag', ctypes.c_void_p * 4), ('wt_frag', ctypes.c_void_p * 4), ('ln_weight', ctypes.c_void_p * 4),
-                ('ln_bias', ctypes.c_void_p * 4)]
+_RelChainDesc = _abi.types['ococc_sir_rel_chain']   # the struct of include/ococc_hip.h, fields read from the header
 
 
 class _RelPlan(object):

@@ -640,6 +640,43 @@ int ococc_scene_rows_fill(const float* points, int64_t num_points, int32_t point
                           const int64_t* scan_out, float* out_xyz, float* out_feats, int64_t* out_row,
                           const void* workspace, int64_t workspace_bytes, ococc_stream_t stream);
 
+/* The scene clouds of SEVERAL sensor frames into the step rows of a chunked online step (csrc/scene_rows.hip, the
+ * same kernel with blockIdx.y = frame), host layer: objectcentricocccompletion_amd/scene_rows.py (scene_steps_rows)
+ * replaces, for F frames in one call, the chain ococc_scene_rows_count / _fill replace for one: the crop of
+ *   tools/ctrl/generate_track_input.py:84-99, the per-frame cap of LoadTrackletPoints
+ *   (mmdet3d/datasets/pipelines/tracklet_pipelines.py:26-91), TrackletPoseTransform (tracklet_pipelines.py:228-303),
+ *   PointDecoration and PointsRangeFilter -- there a pass each per frame, and with the one-cloud exports a count launch,
+ *   a read-back and a fill launch per frame -- by ONE count launch, one read-back and one fill launch.
+ * points [N, point_dim] f32 the clouds of `frames` frames back to back, cloud_offsets [frames+1] i64 (device);
+ * crop_boxes [n, 7] f32 GROUPED BY FRAME, box_offsets [frames+1] i64 (device); box b of frame f sees the points
+ * [cloud_offsets[f], cloud_offsets[f+1]) only.  max_frame_points / max_frame_boxes: the largest frame's points / boxes
+ * (the host made the offsets; a frame whose offsets leave [0, N] or [0, n] is skipped).  frames <= 65535, N, n <= 2^31 - 1;
+ * frames, N or n == 0 is an empty result (counts zero-filled).
+ * Membership, transforms [n, 12], host_range and the written xyz: those of ococc_scene_rows_count, bit for bit.
+ * workspace: ococc_scene_rows_workspace_bytes(max_frame_points, n), written by _count and read by _fill of the SAME input.
+ * _count: counts [n] i64, uncapped, in the boxes' (frame-major) order.
+ * _fill: caller_rows [n] i64, the caller's row number of each box; box_totals [n] i64 = counts; box_starts [n] i64, the
+ *   first output row of each box -- the host orders the boxes by caller's row and scans min(counts, max_points) (counts
+ *   when max_points <= 0) in THAT order; num_out = M, the rows in all.  The pick under the cap is that of
+ *   ococc_scene_rows_fill.  Row r of box b, r in [box_starts[b], box_starts[b] + min(counts[b], cap)): out_xyz, out_feats
+ *   as there (row_feats [n, row_feat_dim] in the boxes' order), out_row [M] i64 = caller_rows[b].  With distinct caller
+ *   rows the output is sorted by (caller's row, point index within the frame); written straight to the final places,
+ *   vector stores only, nothing at or past row M. */
+int ococc_scene_rows_frames_count(const float* points, int64_t num_points, int32_t point_dim,
+                                  const int64_t* cloud_offsets, const float* crop_boxes, int64_t num_boxes,
+                                  const int64_t* box_offsets, int32_t frames, int64_t max_frame_points,
+                                  int64_t max_frame_boxes, const float* transforms, const float* host_range,
+                                  int64_t* counts, void* workspace, int64_t workspace_bytes, ococc_stream_t stream);
+int ococc_scene_rows_frames_fill(const float* points, int64_t num_points, int32_t point_dim,
+                                 const int64_t* cloud_offsets, const float* crop_boxes, int64_t num_boxes,
+                                 const int64_t* box_offsets, int32_t frames, int64_t max_frame_points,
+                                 int64_t max_frame_boxes, const float* transforms, const float* host_range,
+                                 int32_t attr_dims, const float* row_feats, int32_t row_feat_dim,
+                                 const int64_t* caller_rows, int64_t max_points, const int64_t* box_totals,
+                                 const int64_t* box_starts, int64_t num_out, float* out_xyz, float* out_feats,
+                                 int64_t* out_row, const void* workspace, int64_t workspace_bytes,
+                                 ococc_stream_t stream);
+
 /* Track extension by a constant-velocity model, all tracklets of a call in one launch
  * replaces the per-tracklet loop of tools/ctrl/extend_tracks.py:156-190 over LiDARTracklet.frame_transform,
  *   set_velocity, extend / extend_all and shared2ego (mmdet3d/core/bbox/structures/lidar_tracklet.py:345-387, 452-498,

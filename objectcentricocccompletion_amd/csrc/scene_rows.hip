@@ -28,6 +28,17 @@
 // of boxes and matrices per workgroup (L2); count: + T * n * 4 B workspace out, n * 8 B counts (integer atomics, the only
 // ones); fill: + about T/2 * n * 4 B workspace in per wave tile (L2), M * A * 4 B of attributes in (the lines of the xyz) and
 // M * (12 + (A + K) * 4 + 8) B of rows out.  T = ceil(N / 1024) wave tiles, M = scan_out[n].  Vector stores only.
+//
+// Several frames per call (ococc_scene_rows_frames_count / _fill; TrackletRoIHeadOCC.simple_test_scene_steps): the same
+// kernel with blockIdx.y = frame, as tracklet_crop.hip has it -- the clouds back to back with cloud_offsets [F+1], the
+// boxes grouped by frame with box_offsets [F+1], and box b tested against the points of ITS frame only, so the work is
+// sum_f N_f * n_f and not N * n.  blockIdx.z splits the frame's boxes by the rule of box_span over ALL frames' workgroups:
+// at one frame the launch is the one-cloud launch, from about 14 frames of 150 000 points on the split is gone.  The
+// workspace is [wave tiles of the LARGEST frame, n].  The output is in the CALLER's row order, not frame-major: the host,
+// which has the counts, gives every box its first output row (box_starts) and its total (box_totals, for the pick), the
+// kernel writes row caller_rows[b] -- straight to the final places, no gather afterwards.  Per pass the bytes are those
+// above summed over the frames, plus 32 B of offsets per workgroup and, in the fill pass, n * 24 B of starts, totals
+// and caller rows where the one-cloud pass reads n * 16 B of scans.
 #include "common.hpp"
 #include "box_crop.hpp"
 
@@ -41,29 +52,56 @@ struct Range6 {
   float v[6];
 };
 
-// XR: a transform or a range is given (without either, the test is the box's alone and needs fewer registers)
-template <bool FILL, bool XR>
+// What the many-cloud exports add (FRAMES; all null / 0 otherwise): where each frame's points and boxes lie, the
+// caller's row number of every box, and the rows of the output
+struct FrameArgs {
+  const int64_t* cloud_offsets;   // [frames + 1]
+  const int64_t* box_offsets;     // [frames + 1]
+  const int64_t* caller_rows;     // [nb] (fill)
+  int64_t num_out;                // (fill)
+};
+
+// XR: a transform or a range is given (without either, the test is the box's alone and needs fewer registers).
+// FRAMES: blockIdx.y = frame, blockIdx.z = a span of the frame's boxes; `n` is then the points of ALL frames and the
+// frame's own are cloud_offsets[f] .. cloud_offsets[f+1]; the boxes are frame-major, the workspace is [wave tiles of the
+// largest frame, nb], and in the fill pass scan_all is the boxes' totals [nb] and scan_out their first output rows [nb]
+// (the output is in the caller's row order, which the host scans).  Otherwise: one cloud, blockIdx.y = a span of the boxes.
+template <bool FILL, bool XR, bool FRAMES>
 __global__ void __launch_bounds__(64 * kWaves)
 scene_rows_kernel(const float* __restrict__ points, int64_t n, int32_t C, const float* __restrict__ boxes, int32_t nb,
                   int32_t span, const float* __restrict__ transforms, Range6 range, int32_t has_range, int32_t* __restrict__ tile_counts,
                   unsigned long long* __restrict__ counts, int32_t A, const float* __restrict__ row_feats, int32_t K,
                   int64_t cap, const int64_t* __restrict__ scan_all, const int64_t* __restrict__ scan_out,
-                  float* __restrict__ out_xyz, float* __restrict__ out_feats, int64_t* __restrict__ out_row) {
+                  float* __restrict__ out_xyz, float* __restrict__ out_feats, int64_t* __restrict__ out_row, FrameArgs fr) {
   __shared__ BoxChunk sb;
   __shared__ float sm[12][kChunk];   // the box's 3x4 matrix, row-major
+  int b_begin = 0, b_end = 0;        // this workgroup's boxes
+  if (FRAMES) {
+    const int f = blockIdx.y;
+    const int64_t p0 = fr.cloud_offsets[f], p1 = fr.cloud_offsets[f + 1];
+    const int64_t b0 = fr.box_offsets[f], b1 = fr.box_offsets[f + 1];
+    if (p0 < 0 || p1 > n || p1 <= p0 || b0 < 0 || b1 > nb || b1 <= b0) return;   // an empty frame, or offsets that lie
+    if ((int64_t)blockIdx.z * span >= b1 - b0) return;
+    b_begin = (int)(b0 + (int64_t)blockIdx.z * span);
+    b_end = (int)min(b1, (int64_t)b_begin + span);
+    points += p0 * C;
+    n = p1 - p0;
+  }
   const int64_t tile0 = (int64_t)blockIdx.x * kBlockTile;
   if (tile0 >= n) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t w0 = tile0 + (int64_t)wave * kCropWaveTile;   // index of this wave's first point
-  const int64_t wt = (int64_t)blockIdx.x * kWaves + wave;  // wave tile
+  const int64_t w0 = tile0 + (int64_t)wave * kCropWaveTile;   // index of this wave's first point (in its cloud)
+  const int64_t wt = (int64_t)blockIdx.x * kWaves + wave;  // wave tile (of its cloud)
   const bool xform = XR && transforms != nullptr;
 
   WavePoints p;
   p.load(points, C, n, w0, lane);
 
-  // this workgroup's boxes: [blockIdx.y * span, b_end)
-  const int b_end = (int)min((int64_t)nb, ((int64_t)blockIdx.y + 1) * span);
-  for (int c0 = blockIdx.y * span; c0 < b_end; c0 += kChunk) {
+  if (!FRAMES) {   // [blockIdx.y * span, b_end)
+    b_begin = blockIdx.y * span;
+    b_end = (int)min((int64_t)nb, ((int64_t)blockIdx.y + 1) * span);
+  }
+  for (int c0 = b_begin; c0 < b_end; c0 += kChunk) {
     const int cn = min(kChunk, b_end - c0);
     __syncthreads();
     if (tid < cn) {
@@ -82,8 +120,14 @@ scene_rows_kernel(const float* __restrict__ points, int64_t n, int32_t C, const 
     if (FILL) {
       if (lane < cn) {
         const int64_t b = c0 + lane;
-        total = scan_all[b + 1] - scan_all[b];
-        start = scan_out[b], end = scan_out[b + 1];
+        if (FRAMES) {
+          total = scan_all[b], start = scan_out[b];
+          end = start + ((cap > 0 && total > cap) ? cap : total);
+          if (start < 0 || end > fr.num_out) end = start = 0;   // (a start the host did not make: nothing is written)
+        } else {
+          total = scan_all[b + 1] - scan_all[b];
+          start = scan_out[b], end = scan_out[b + 1];
+        }
         for (int64_t k = 0; k < wt; ++k) base += tile_counts[k * nb + b];
       }
     }
@@ -122,7 +166,7 @@ scene_rows_kernel(const float* __restrict__ points, int64_t n, int32_t C, const 
             const int64_t i = w0 + r * 64 + lane;
             float* o = out_xyz + pos * 3;
             o[0] = ox, o[1] = oy, o[2] = oz;
-            out_row[pos] = c0 + j;
+            out_row[pos] = FRAMES ? fr.caller_rows[c0 + j] : (int64_t)(c0 + j);
             float* f = out_feats + pos * (A + K);
             const float* q = points + i * C + 3;
             for (int a = 0; a < A; ++a) f[a] = q[a];
@@ -158,12 +202,36 @@ int rows_check(const float* points, int64_t n, int32_t c, const float* boxes, in
 // Boxes per workgroup (blockIdx.y takes `span` consecutive boxes).  One sensor frame is few workgroups along the points
 // (37 at 150 000 points), so the boxes are split until about two workgroups per CU are in flight, 8 boxes at the least;
 // every split re-reads the cloud (L2), which is small beside the box tests it spreads.
-int32_t box_span(int64_t n, int64_t b) {
-  const int64_t tiles = ococc_cdiv(n, kBlockTile);
+// Several frames: n and b are the largest frame's, and every frame brings its workgroups along the points.
+int32_t box_span(int64_t n, int64_t b, int64_t frames = 1) {
+  const int64_t tiles = ococc_cdiv(n, kBlockTile) * frames;
   int64_t parts = ococc_cdiv(512, tiles);
   if (parts > ococc_cdiv(b, 8)) parts = ococc_cdiv(b, 8);
   if (parts > 65535) parts = 65535;
   return (int32_t)ococc_cdiv(b, parts < 1 ? 1 : parts);
+}
+
+// the checks of the many-cloud exports -- 1: nothing to do, 0: launch, < 0: reported
+int frames_check(const float* points, int64_t n, int32_t c, const int64_t* cloud_offsets, const float* boxes, int64_t b,
+                 const int64_t* box_offsets, int32_t frames, int64_t max_frame_points, int64_t max_frame_boxes,
+                 const void* workspace, int64_t workspace_bytes, const char* fn) {
+  if (n < 0 || b < 0 || frames < 0 || max_frame_points < 0 || max_frame_boxes < 0)
+    return ococc_fail(OCOCC_EINVAL, fn, "negative size");
+  if (n > 2147483647LL || b > 2147483647LL) return ococc_fail(OCOCC_EINVAL, fn, "at most 2^31 - 1 points and boxes");
+  if (max_frame_points > n || max_frame_boxes > b)
+    return ococc_fail(OCOCC_EINVAL, fn, "max_frame_points > num_points or max_frame_boxes > num_boxes");
+  if (c < 3) return ococc_fail(OCOCC_EINVAL, fn, "points need at least 3 columns");
+  if (frames > 65535) return ococc_fail(OCOCC_EINVAL, fn, "at most 65535 frames per call");
+  if (b == 0 || n == 0 || frames == 0 || max_frame_points == 0 || max_frame_boxes == 0) return 1;
+  if (!points || !cloud_offsets || !boxes || !box_offsets || !workspace) return ococc_fail(OCOCC_EINVAL, fn, "null pointer");
+  if (workspace_bytes < ococc_scene_rows_workspace_bytes(max_frame_points, b))
+    return ococc_fail(OCOCC_EINVAL, fn, "workspace too small: ococc_scene_rows_workspace_bytes(max_frame_points, num_boxes)");
+  return OCOCC_OK;
+}
+
+// blockIdx.x: workgroups along the largest frame's points, y: frame, z: spans of the frame's boxes
+dim3 frames_grid(int32_t frames, int64_t max_frame_points, int64_t max_frame_boxes, int32_t span) {
+  return dim3((unsigned)ococc_cdiv(max_frame_points, kBlockTile), (unsigned)frames, (unsigned)ococc_cdiv(max_frame_boxes, span));
 }
 
 Range6 range_arg(const float* range) {
@@ -191,14 +259,14 @@ extern "C" int ococc_scene_rows_count(const float* points, int64_t num_points, i
     OCOCC_HIP(hipMemsetAsync(counts, 0, num_boxes * sizeof(int64_t), stream));
   }
   if (rc == 1) return OCOCC_OK;
-  const auto kernel = (transforms || range) ? scene_rows_kernel<false, true> : scene_rows_kernel<false, false>;
+  const auto kernel = (transforms || range) ? scene_rows_kernel<false, true, false> : scene_rows_kernel<false, false, false>;
   const int32_t span = box_span(num_points, num_boxes);
   hipLaunchKernelGGL(kernel, dim3((unsigned)ococc_cdiv(num_points, kBlockTile), (unsigned)ococc_cdiv(num_boxes, span)),
                      dim3(64 * kWaves), 0, stream, points, num_points, point_dim, crop_boxes, (int32_t)num_boxes, span,
                      transforms, range_arg(range), (int32_t)(range != nullptr), (int32_t*)workspace,
                      (unsigned long long*)counts, 0,
                      (const float*)nullptr, 0, (int64_t)0, (const int64_t*)nullptr, (const int64_t*)nullptr,
-                     (float*)nullptr, (float*)nullptr, (int64_t*)nullptr);
+                     (float*)nullptr, (float*)nullptr, (int64_t*)nullptr, FrameArgs{nullptr, nullptr, nullptr, 0});
   OCOCC_CHECK_LAUNCH();
   return OCOCC_OK;
 }
@@ -218,13 +286,72 @@ extern "C" int ococc_scene_rows_fill(const float* points, int64_t num_points, in
   OCOCC_REQUIRE(scan_all && scan_out && out_xyz && out_row, "null scan_all, scan_out, out_xyz or out_row");
   OCOCC_REQUIRE(row_feat_dim == 0 || row_feats, "null row_feats");
   OCOCC_REQUIRE(attr_dims + row_feat_dim == 0 || out_feats, "null out_feats");
-  const auto kernel = (transforms || range) ? scene_rows_kernel<true, true> : scene_rows_kernel<true, false>;
+  const auto kernel = (transforms || range) ? scene_rows_kernel<true, true, false> : scene_rows_kernel<true, false, false>;
   const int32_t span = box_span(num_points, num_boxes);
   hipLaunchKernelGGL(kernel, dim3((unsigned)ococc_cdiv(num_points, kBlockTile), (unsigned)ococc_cdiv(num_boxes, span)),
                      dim3(64 * kWaves), 0, (hipStream_t)stream_, points, num_points, point_dim, crop_boxes,
                      (int32_t)num_boxes, span, transforms, range_arg(range), (int32_t)(range != nullptr),
                      (int32_t*)const_cast<void*>(workspace), (unsigned long long*)nullptr, attr_dims, row_feats, row_feat_dim, max_points, scan_all, scan_out,
-                     out_xyz, out_feats, out_row);
+                     out_xyz, out_feats, out_row, FrameArgs{nullptr, nullptr, nullptr, 0});
+  OCOCC_CHECK_LAUNCH();
+  return OCOCC_OK;
+}
+
+extern "C" int ococc_scene_rows_frames_count(const float* points, int64_t num_points, int32_t point_dim,
+                                             const int64_t* cloud_offsets, const float* crop_boxes, int64_t num_boxes,
+                                             const int64_t* box_offsets, int32_t frames, int64_t max_frame_points,
+                                             int64_t max_frame_boxes, const float* transforms, const float* range,
+                                             int64_t* counts, void* workspace, int64_t workspace_bytes,
+                                             ococc_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const int rc = frames_check(points, num_points, point_dim, cloud_offsets, crop_boxes, num_boxes, box_offsets, frames,
+                              max_frame_points, max_frame_boxes, workspace, workspace_bytes, __func__);
+  if (rc < 0) return rc;
+  if (num_boxes > 0) {
+    OCOCC_REQUIRE(counts, "null counts");
+    OCOCC_HIP(hipMemsetAsync(counts, 0, num_boxes * sizeof(int64_t), stream));
+  }
+  if (rc == 1) return OCOCC_OK;
+  const auto kernel = (transforms || range) ? scene_rows_kernel<false, true, true> : scene_rows_kernel<false, false, true>;
+  const int32_t span = box_span(max_frame_points, max_frame_boxes, frames);
+  hipLaunchKernelGGL(kernel, frames_grid(frames, max_frame_points, max_frame_boxes, span), dim3(64 * kWaves), 0, stream,
+                     points, num_points, point_dim, crop_boxes, (int32_t)num_boxes, span, transforms, range_arg(range),
+                     (int32_t)(range != nullptr), (int32_t*)workspace, (unsigned long long*)counts, 0,
+                     (const float*)nullptr, 0, (int64_t)0, (const int64_t*)nullptr, (const int64_t*)nullptr,
+                     (float*)nullptr, (float*)nullptr, (int64_t*)nullptr,
+                     FrameArgs{cloud_offsets, box_offsets, nullptr, 0});
+  OCOCC_CHECK_LAUNCH();
+  return OCOCC_OK;
+}
+
+extern "C" int ococc_scene_rows_frames_fill(const float* points, int64_t num_points, int32_t point_dim,
+                                            const int64_t* cloud_offsets, const float* crop_boxes, int64_t num_boxes,
+                                            const int64_t* box_offsets, int32_t frames, int64_t max_frame_points,
+                                            int64_t max_frame_boxes, const float* transforms, const float* range,
+                                            int32_t attr_dims, const float* row_feats, int32_t row_feat_dim,
+                                            const int64_t* caller_rows, int64_t max_points, const int64_t* box_totals,
+                                            const int64_t* box_starts, int64_t num_out, float* out_xyz,
+                                            float* out_feats, int64_t* out_row, const void* workspace,
+                                            int64_t workspace_bytes, ococc_stream_t stream_) {
+  const int rc = frames_check(points, num_points, point_dim, cloud_offsets, crop_boxes, num_boxes, box_offsets, frames,
+                              max_frame_points, max_frame_boxes, workspace, workspace_bytes, __func__);
+  if (rc < 0) return rc;
+  OCOCC_REQUIRE(attr_dims >= 0 && row_feat_dim >= 0 && 3 + (int64_t)attr_dims <= point_dim,
+                "attr_dims and row_feat_dim are >= 0, and 3 + attr_dims <= point_dim");
+  OCOCC_REQUIRE(max_points <= 2147483647LL, "max_points is at most 2^31 - 1 (<= 0: no cap)");
+  OCOCC_REQUIRE(num_out >= 0, "negative num_out");
+  if (rc == 1 || num_out == 0) return OCOCC_OK;
+  OCOCC_REQUIRE(caller_rows && box_totals && box_starts && out_xyz && out_row,
+                "null caller_rows, box_totals, box_starts, out_xyz or out_row");
+  OCOCC_REQUIRE(row_feat_dim == 0 || row_feats, "null row_feats");
+  OCOCC_REQUIRE(attr_dims + row_feat_dim == 0 || out_feats, "null out_feats");
+  const auto kernel = (transforms || range) ? scene_rows_kernel<true, true, true> : scene_rows_kernel<true, false, true>;
+  const int32_t span = box_span(max_frame_points, max_frame_boxes, frames);
+  hipLaunchKernelGGL(kernel, frames_grid(frames, max_frame_points, max_frame_boxes, span), dim3(64 * kWaves), 0,
+                     (hipStream_t)stream_, points, num_points, point_dim, crop_boxes, (int32_t)num_boxes, span, transforms,
+                     range_arg(range), (int32_t)(range != nullptr), (int32_t*)const_cast<void*>(workspace),
+                     (unsigned long long*)nullptr, attr_dims, row_feats, row_feat_dim, max_points, box_totals, box_starts,
+                     out_xyz, out_feats, out_row, FrameArgs{cloud_offsets, box_offsets, caller_rows, num_out});
   OCOCC_CHECK_LAUNCH();
   return OCOCC_OK;
 }

@@ -454,7 +454,7 @@ class TrackletRoIHeadOCC(nn.Module):
 
     @torch.no_grad()
     def simple_test_steps(self, pts_xyz, pts_feats, pts_row_idx, boxes, scores, labels, slot_rows, state, gt_rois=None,
-                          occ=False, tune=None):
+                          occ=False, tune=None, occ_transforms=None):
         """``simple_test_step`` for one OR MORE new frames per tracklet in one call -- a tracklet that arrives with
         history (a track confirmed after several hits, a dropped batch), or a recorded one fed T frames at a time.  A row
         is one (tracklet, frame): ``pts_row_idx`` the ROW 0..n-1 a point belongs to, boxes [n, 7], scores [n], labels [n]
@@ -463,8 +463,9 @@ class TrackletRoIHeadOCC(nn.Module):
         continue where its earlier steps stopped.  Pooling, decode and the returned dict are those of simple_test_step,
         n rows in input order; the temporal transformer takes all rows in one launch per layer
         (OccBBoxHead.forward_steps).  The coordinate-frame rule of simple_test_step holds, and ``occ=True`` adds its three
-        keys ``occ``, ``occ_flags`` and ``occ_counts`` for the n rows; ``tune`` is that of simple_test_step, and a row draws
-        the sample the single step of its (slot, frame) draws.
+        keys ``occ``, ``occ_flags`` and ``occ_counts`` for the n rows (``occ_transforms`` [n, 12], per row, as there;
+        default None); ``tune`` is that of simple_test_step, and a row draws the sample the single step of its (slot, frame)
+        draws.
 
         Reported on the host before anything is launched: slots out of range, rows of a slot that are not consecutive, a
         run past the cache's cap (OcoccError), CPU tensors (OcoccError), training mode (RuntimeError)."""
@@ -472,7 +473,7 @@ class TrackletRoIHeadOCC(nn.Module):
             raise RuntimeError('simple_test_steps is inference only: call .eval() first')
         slots, offsets, _ = state.cache.check_steps(slot_rows)
         return self._simple_test_rows(self.bbox_head.forward_steps, slots, offsets, pts_xyz, pts_feats, pts_row_idx, boxes,
-                                      scores, labels, state, gt_rois, occ, None, tune)
+                                      scores, labels, state, gt_rois, occ, occ_transforms, tune)
 
     def _simple_test_rows(self, head_step, slots, offsets, pts_xyz, pts_feats, pts_row_idx, boxes, scores, labels, state,
                           gt_rois, occ, occ_transforms, tune):
@@ -688,6 +689,114 @@ class TrackletRoIHeadOCC(nn.Module):
                 points, out['occ_ego'], out['occ_counts'], merged_cfg['use_dim'], row_score=row_score,
                 flags=out['occ_flags'], drop_observed=merged_cfg['drop_observed'],
                 score_threshold=merged_cfg['score_threshold'])
+        return out
+
+    @torch.no_grad()
+    def simple_test_scene_steps(self, points, cloud_sizes, poses, boxes, scores, labels, frame_rows, slot_rows, state,
+                                gt_rois=None, occ=False, tune=None):
+        """simple_test_steps from what SEVERAL sensor frames bring -- a track confirmed after three hits comes with three
+        boxes in three clouds under three poses: ``points`` [N, >= 3 + attr] f32, the F scene clouds concatenated, each in its
+        own ego frame, ``cloud_sizes`` their F lengths (ints on the host), ``poses`` [F, 4, 4] the ego -> world pose of each
+        cloud (numpy or torch).  A row is one (tracklet, frame) exactly as in simple_test_steps: ``boxes`` [n, 7] each in the
+        ego frame of the row's own cloud, ``scores`` [n], ``labels`` [n], ``frame_rows`` the cloud 0..F-1 of every row,
+        ``slot_rows`` its slot; the rows of a slot are consecutive and in frame order, so within a slot's run ``frame_rows``
+        is strictly increasing (gaps are fine: a track may miss a frame).
+
+        Origins as in simple_test_scene_step: a slot whose frame counter is 0 takes inverse(pose of its FIRST row's cloud),
+        any other slot ``state.origin[slot]``; they are stored only after every host check has passed.  Row i gets
+        M_i = float32(origin[slot_i] @ poses[frame_rows[i]]) (float64 on the host; M and inverse(M) of all rows go up in
+        one copy), the boxes go through M_i, scene_rows.scene_steps_rows builds the rows of ALL clouds with one count launch,
+        one read-back and one fill launch (test_cfg.scene_rows as in the single step), and simple_test_steps runs on them.
+
+        Returns the keys of simple_test_scene_step for the n rows in input order: the dict of simple_test_steps,
+        ``boxes_ego`` (rows with valid == False their input box bit for bit), ``num_points`` [n] i64 on the host (uncapped),
+        and with ``occ=True`` ``occ_ego`` (each row's cells in the ego frame of ITS cloud), ``occ_flags``, ``occ_counts``.
+        ``tune`` passes through.  n == 0 returns empty tensors for every key, launches nothing and leaves the state as it is.
+
+        There is no ``merged=`` here: the occupancy-enhanced cloud is one array per sensor frame and occ_merge a count, a
+        read-back and a fill per cloud, so a caller who needs merged clouds steps frame by frame (simple_test_scene_step).
+
+        Reported on the host before anything is launched: what simple_test_steps reports, poses that are not [F, 4, 4], not
+        finite or singular, cloud_sizes of another length than F, frame_rows outside 0..F-1, repeating or going back inside
+        a slot's run, a slot in mid-tracklet without an origin (OcoccError), training mode (RuntimeError)."""
+        import numpy as np
+        from . import _lib as L
+        from .scene_rows import scene_steps_rows
+        from .tracklet import host_index
+        if self.training:
+            raise RuntimeError('simple_test_scene_steps is inference only: call .eval() first')
+        pose64 = np.asarray(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float64)
+        sizes, frame_rows = [int(v) for v in cloud_sizes], [int(v) for v in frame_rows]
+        F = len(sizes)
+        if F == 0 and pose64.size == 0:
+            pose64 = pose64.reshape(0, 4, 4)
+        if pose64.shape != (F, 4, 4) or not np.isfinite(pose64).all():
+            raise L.OcoccError(f'poses must be finite ego -> world matrices [F = {F}, 4, 4], one per cloud, got shape {pose64.shape}')
+        slots, offsets, _ = state.cache.check_steps(slot_rows)
+        n = len(slots)
+        if len(frame_rows) != n or any(not 0 <= f < F for f in frame_rows):
+            raise L.OcoccError(f'frame_rows must hold the cloud 0..{F - 1} of each of the {n} rows, got {len(frame_rows)} values'
+                               + (f' from {min(frame_rows)} to {max(frame_rows)}' if frame_rows else ''))
+        for i in range(1, n):
+            if offsets[i] and frame_rows[i] <= frame_rows[i - 1]:
+                raise L.OcoccError(f'the rows of slot {slots[i]} go from cloud {frame_rows[i - 1]} to cloud {frame_rows[i]}: '
+                                   'within a slot\'s run frame_rows is strictly increasing (its frames in time order, none twice)')
+        inverse, started, origins = {}, {}, []
+        for i, s in enumerate(slots):
+            if offsets[i] == 0 and state.frames[s] == 0:                # a slot that starts here: its first row's cloud
+                f = frame_rows[i]
+                if f not in inverse:
+                    try:
+                        inverse[f] = np.linalg.inv(pose64[f])
+                    except np.linalg.LinAlgError:
+                        raise L.OcoccError(f'pose {f} is singular: not an ego -> world transform')
+                started[s] = inverse[f]
+            if s in started:
+                origins.append(started[s])
+            elif state.origin[s] is None:
+                raise L.OcoccError(f'slot {s} holds {state.frames[s]} frames and no origin: it was stepped through '
+                                   'simple_test_step, whose caller keeps the fixed frame (reset the slot)')
+            else:
+                origins.append(state.origin[s])
+        if boxes.size(0) != n or scores.size(0) != n or labels.size(0) != n:
+            raise L.OcoccError(f'{n} slots, {scores.size(0)} scores, {labels.size(0)} labels for {boxes.size(0)} boxes')
+        if points.dim() != 2 or sum(sizes) != points.size(0) or min(sizes, default=0) < 0:
+            raise L.OcoccError(f'cloud_sizes must be >= 0 and sum to the points given, got {sum(sizes)} for {tuple(points.shape)}')
+        L.require_device(points, boxes, scores, labels, state.cache.pos)
+        dev = boxes.device
+        if n == 0:
+            feats = boxes.new_zeros((0, self.bbox_head.roi_feature_channels))
+            out = dict(boxes=boxes.new_zeros((0, 7)), scores=scores.new_zeros((0,)), labels=labels.new_zeros((0,)),
+                       valid=torch.zeros((0,), dtype=torch.bool, device=dev), fused_roi_feats=feats, ori_roi_feats=feats,
+                       boxes_ego=boxes.new_zeros((0, 7)), num_points=torch.zeros((0,), dtype=torch.long))
+            if occ:
+                out.update(occ_ego=boxes.new_zeros((0, 4)), occ_flags=torch.zeros((0,), dtype=torch.uint8, device=dev),
+                           occ_counts=[])
+            return out
+        cfg = dict(self.SCENE_ROWS_DEFAULTS, **(self.test_cfg.get('scene_rows', None) or {}))
+        if occ:
+            self.online_occ_cfg()                                       # (a wrong test_cfg.online_occ: before the origins)
+        to_fixed = np.stack([o @ pose64[f] for o, f in zip(origins, frame_rows)])
+        try:
+            from_fixed = np.linalg.inv(to_fixed)
+        except np.linalg.LinAlgError:
+            raise L.OcoccError('a pose is singular: not an ego -> world transform')
+        mats = host_index(np.stack([to_fixed[:, :3].reshape(n, 12), from_fixed[:, :3].reshape(n, 12)]), dev,
+                          dtype=torch.float64)                         # [2, n, 12]: M and inverse(M), one copy
+        fixed_boxes = self._boxes_through(boxes, mats[0])
+        xyz, feats, row, counts = scene_steps_rows(
+            points, sizes, boxes, scores, frame_rows, transforms=mats[0].float(), extra_width=cfg['extra_width'],
+            attr_dims=cfg['attr_dims'], point_cloud_range=cfg['point_cloud_range'], max_points=cfg['max_points'],
+            deco_boxes=fixed_boxes)
+        for s, o in started.items():                                    # (every host check has passed)
+            state.origin[s] = o
+        kw = dict(occ=True, occ_transforms=mats[1].float()) if occ else {}
+        out = self.simple_test_steps(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois, tune=tune, **kw)
+        if occ:
+            out['occ_ego'] = out.pop('occ')
+        out['boxes_ego'] = torch.where(out['valid'].to(dev).bool()[:, None], self._boxes_through(out['boxes'], mats[1]),
+                                       boxes[:, :7])
+        out['num_points'] = counts
         return out
 
     def online_chunk(self):

@@ -3,14 +3,16 @@
 (tools/ctrl/data_configs/*.yaml: bin_path, mm_data_root with idx2timestamp.pkl / idx2contextname.pkl and the velodyne
 clouds) stepped through frame by frame, the way the method is deployed -- no track-input database, no per-tracklet files:
 
-    python tools/online_raw.py <config> <checkpoint> <raw.yaml> [--slots 64] [--out FILE.bin] [--poses poses.pkl]
+    python tools/online_raw.py <config> <checkpoint> <raw.yaml> [--slots 64] [--out FILE.bin] [--poses poses.pkl] [--chunk T]
                                [--save-occ DIR] [--step-tuning N [--step-tuning-samples S]] [--cfg-options k=v ...]
                                [--save-merged DIR [--merged-use-dim 5] [--merged-score-threshold 0] [--merged-drop-observed]]
 
 Per segment and frame, in time order: the frame's scene cloud is loaded once, every track that starts at the frame gets a
 free slot of the temporal K/V cache, TrackletRoIHeadOCC.simple_test_scene_step refines all live tracks in one call (crop,
 pose transform, decoration, range filter and cap on the device: csrc/scene_rows.hip), and a track's slot is released after
-its last frame.  More live tracks than slots is an error that names --slots.  The cache is chosen from the longest track as
+its last frame.  With --chunk T, T consecutive timestamps go into one TrackletRoIHeadOCC.simple_test_scene_steps call (the
+rows of T clouds from one count, one read-back and one fill launch, one head pass), slots given before and released after
+the call.  More live tracks than slots is an error that names --slots.  The cache is chosen from the longest track as
 simple_test_online chooses it: plain up to 256 frames, a ring with test_cfg.attn_window_size, else a long cache.
 
 The refined objects (``boxes_ego``: each in its own frame's ego frame) are written as a Waymo metrics file; an object whose
@@ -54,7 +56,8 @@ def choose_cache(roi_head, longest):
                        f'holds at most {TemporalCache.MAX_LONG_CAP} frames of history')
 
 
-def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_occ=None, save_merged=None, merged=True):
+def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_occ=None, save_merged=None, merged=True,
+           chunk=1):
     """``model``: a TrackletDetectorOCC in eval mode on a ROCm device; ``raw_yaml``: the track-input yaml (path or mapping,
     ctrl_prep.load_config); ``poses``: {timestamp: 4x4 ego -> world} or the path of its pickle (default: the yaml's
     ``poses_path``, else <mm_data_root>/poses.pkl).  Returns (records, state): one record per object of the tracker's
@@ -65,11 +68,18 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_oc
     file per frame and object (occ_export.write_tracklet_occ), and every record gets ``occ_cells``, the rows of its file.
     With ``save_merged`` (a directory) the occupancy-enhanced cloud of every replayed frame is written to
     <save_merged>/<segment>/<timestamp>.bin (``merged``: True or the dict simple_test_scene_step takes), and every record
-    gets ``merged_cells``, the cells of its object in that file."""
+    gets ``merged_cells``, the cells of its object in that file.
+    ``chunk`` = T > 1: T consecutive timestamps of a segment per simple_test_scene_steps call, rows slot-major (the last call
+    of a segment takes the rest); a track that starts inside the T timestamps has its slot before the call, one that ends
+    inside them gives it back after the call, so the call needs a slot for every track live anywhere in it.  Records and
+    files are those of chunk = 1; not with ``save_merged`` (the merged cloud is made per frame: simple_test_scene_steps)."""
     import numpy as np
     import torch
     from objectcentricocccompletion_amd import _lib as L
     from objectcentricocccompletion_amd import ctrl_prep, occ_export, waymo_io
+    chunk = int(chunk)
+    if chunk < 1 or (chunk > 1 and save_merged):
+        raise ValueError('chunk is the number of timestamps per call, an int >= 1, and 1 with save_merged')
     cfg, _ = ctrl_prep.load_config(raw_yaml)
     rh = model.roi_head
     dev = torch.device(device) if device is not None else next(model.parameters()).device
@@ -103,44 +113,55 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_oc
             raise KeyError(f'{len(missing)} timestamps of segment {seg} have no frame in idx2timestamp.pkl or no pose '
                            f'(e.g. {sorted(missing)[0]})')
         free, slot_of = list(range(state.slots))[::-1], {}
-        for ts in sorted(at):
-            rows = at[ts]
-            for k, i in rows:
-                if i == 0:
-                    if not free:
-                        raise L.OcoccError(f'segment {seg} has more than {state.slots} live tracks at timestamp {ts}: '
-                                           'raise --slots')
-                    slot_of[k] = free.pop()
-            cloud = np.fromfile(os.path.join(pc_root, f'{ts2idx[ts]}.bin'), dtype=np.float32).reshape(-1, 6)
-            boxes = torch.stack([tracklets[k].boxes[i, :7].float() for k, i in rows]).to(dev)
-            scores = torch.stack([tracklets[k].scores[i].float() for k, i in rows]).to(dev)
-            labels = torch.tensor([WAYMO_TYPE_TO_LABEL[tracklets[k].type] for k, _ in rows], dtype=torch.long).to(dev)
-            res = rh.simple_test_scene_step(torch.from_numpy(cloud).to(dev), np.asarray(poses[ts], dtype=np.float64), boxes,
-                                            scores, labels, [slot_of[k] for k, _ in rows], state, **step_kw)
+        stamps = sorted(at)
+        for c0 in range(0, len(stamps), chunk):      # `chunk` timestamps per call, the last call takes the rest
+            group = stamps[c0:c0 + chunk]
+            runs = {}                                # tracklet -> [(cloud of the call, position in the tracklet)], in time order
+            for f, ts in enumerate(group):
+                for k, i in at[ts]:
+                    if i == 0:
+                        if not free:
+                            raise L.OcoccError(f'segment {seg} has more than {state.slots} live tracks at timestamp {ts}: '
+                                               'raise --slots')
+                        slot_of[k] = free.pop()
+                    runs.setdefault(k, []).append((f, i))
+            rows = [(k, i, f) for k, run in runs.items() for f, i in run]      # slot-major (one frame: the frame's order)
+            clouds = [np.fromfile(os.path.join(pc_root, f'{ts2idx[ts]}.bin'), dtype=np.float32).reshape(-1, 6) for ts in group]
+            boxes = torch.stack([tracklets[k].boxes[i, :7].float() for k, i, _ in rows]).to(dev)
+            scores = torch.stack([tracklets[k].scores[i].float() for k, i, _ in rows]).to(dev)
+            labels = torch.tensor([WAYMO_TYPE_TO_LABEL[tracklets[k].type] for k, _, _ in rows], dtype=torch.long).to(dev)
+            if chunk == 1:
+                res = rh.simple_test_scene_step(torch.from_numpy(clouds[0]).to(dev), np.asarray(poses[group[0]], dtype=np.float64),
+                                                boxes, scores, labels, [slot_of[k] for k, _, _ in rows], state, **step_kw)
+            else:                                    # the clouds of the call: one host -> device copy
+                res = rh.simple_test_scene_steps(torch.from_numpy(np.concatenate(clouds)).to(dev), [len(c) for c in clouds],
+                                                 np.stack([np.asarray(poses[ts], dtype=np.float64) for ts in group]), boxes,
+                                                 scores, labels, [f for _, _, f in rows], [slot_of[k] for k, _, _ in rows],
+                                                 state, **step_kw)
             valid = res['valid'].to(dev).bool()
             back = torch.cat([res['boxes_ego'], torch.where(valid, res['scores'].float(), scores)[:, None],
                               valid[:, None].float()], 1)
-            if save_occ or save_merged:                                   # boxes, scores, cells, cloud: still one read-back per frame
+            if save_occ or save_merged:                                   # boxes, scores, cells, cloud: still one read-back per call
                 parts = [back] + ([res['occ_ego']] if save_occ else []) + ([res['points_merged']] if save_merged else [])
                 flat = torch.cat([p.reshape(-1) for p in parts]).cpu().split([p.numel() for p in parts])
                 back = flat[0].view(-1, 9)
                 if save_occ:
                     cells = flat[1].view(-1, 4).numpy()
                     cuts = np.cumsum([0] + list(res['occ_counts']))
-                if save_merged:
-                    path = os.path.join(save_merged, str(seg), f'{ts}.bin')
+                if save_merged:                                           # (chunk == 1: the frame of the call)
+                    path = os.path.join(save_merged, str(seg), f'{group[0]}.bin')
                     os.makedirs(os.path.dirname(path), exist_ok=True)
                     flat[-1].numpy().tofile(path)
             else:
-                back = back.cpu()                                         # one read-back per frame
+                back = back.cpu()                                         # one read-back per call
             done = []
-            for r, (k, i) in enumerate(rows):
+            for r, (k, i, f) in enumerate(rows):
                 boxes_out[k][i], scores_out[k][i] = back[r, :7], back[r, 7]
                 refined[k][i], num_points[k][i] = bool(back[r, 8]), int(res['num_points'][r])
                 if save_occ:
                     mine = cells[cuts[r]:cuts[r + 1]].copy()
                     mine[:, 3] = float(back[r, 7])                        # the score column of the exported files
-                    occ_export.write_tracklet_occ(save_occ, seg, [ts], tracklets[k].type, tracklets[k].id, mine,
+                    occ_export.write_tracklet_occ(save_occ, seg, [group[f]], tracklets[k].type, tracklets[k].id, mine,
                                                   [len(mine)])
                     occ_cells[k][i] = len(mine)
                 if save_merged:
@@ -190,6 +211,9 @@ def parse_args(argv=None):
                     help='a cell is kept iff its object\'s score of the frame is > T (default 0, or test_cfg.online_merged)')
     ap.add_argument('--merged-drop-observed', action='store_true',
                     help='leave out the cells a real point of the frame fell into')
+    ap.add_argument('--chunk', type=int, metavar='T', default=1,
+                    help='T consecutive timestamps of a segment per call (simple_test_scene_steps: the rows of T clouds from one '
+                    'count launch, one read-back and one fill launch, one head pass); not with --save-merged')
     ap.add_argument('--step-tuning', type=int, metavar='N', default=None,
                     help='tune the fused shape latent of every live track against the frame\'s own points with N Adam steps '
                     'inside the step (sets test_cfg.online_step_tuning = dict(num_iter=N, downsample_size=S, '
@@ -200,6 +224,10 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.slots < 1:
         ap.error('--slots takes a number of tracks >= 1')
+    if args.chunk < 1:
+        ap.error('--chunk takes a number of timestamps >= 1')
+    if args.chunk > 1 and args.save_merged is not None:
+        ap.error('--chunk above 1 does not go with --save-merged: the occupancy-enhanced cloud is made per frame')
     if args.step_tuning is not None and args.step_tuning < 0:
         ap.error('--step-tuning takes a number of iterations >= 0')
     if args.step_tuning_samples is not None and args.step_tuning is None:
@@ -249,7 +277,7 @@ def main(argv=None):
     raw, _ = ctrl_prep.load_config(args.raw_yaml)
     out = args.out or os.path.splitext(ctrl_prep.bin_path_for_split(raw))[0] + '_online.bin'
     records, _ = replay(model, args.raw_yaml, slots=args.slots, out=out, poses=args.poses, device=dev, save_occ=args.save_occ,
-                        save_merged=args.save_merged, merged=merged_arg(args))
+                        save_merged=args.save_merged, merged=merged_arg(args), chunk=args.chunk)
     print(f'{len(records)} objects, {sum(r["refined"] for r in records)} refined; wrote {out}')
     if args.save_occ:
         print(f'{sum(r.get("occ_cells", 0) for r in records)} occupancy cells in {args.save_occ}')

@@ -914,6 +914,50 @@ int ococc_occ_merge_fill(const float* points, int64_t N, int32_t C, const int32_
                          const int64_t* tile_scan, int64_t max_tiles, float* merged, int64_t K, ococc_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * occupancy-enhanced scene clouds of SEVERAL frames in one call (csrc/occ_merge.hip, the kernels of the pair above with a
+ * frame table), behind occ_ops.occ_merge_frames and TrackletRoIHeadOCC.simple_test_scene_steps_merged: what F calls of
+ * ococc_occ_merge_count / _fill write, frame after frame in one array, with one table, one count and one fill launch and
+ * one read-back for any F.
+ * points [N, C] f32: the F clouds back to back; cloud_start [F + 1] i64 their exclusive prefix (0 ... N).
+ * occ [M, 4], start [R + 1], row_score [R], flags [M], drop_observed, score_threshold, host_use_dim, D and the survival
+ *   rule: those of the pair above.  The R rows are in the CALLER's order (slot-major in a chunked step), not by frame.
+ * row_frame [R] i64: the frame 0..F-1 of every row.  order [R] i64: the rows sorted by frame, stable (a frame's rows
+ *   keep the caller's order); frame_first [F + 1] i64: where the rows of frame f begin in order (0 ... R).  All five
+ *   tables are on the device; the caller builds them on the host and may send them up in one copy.  0 <= F <= 65535;
+ *   F == 0 needs R == 0 and N == 0.
+ * Tiles are laid out along the order: tile_start [R + 1] i64 is the prefix of ceil(cells / 1024) of row order[p], so
+ *   tile_scan, the exclusive prefix of tile_counts, ranks a survivor among the survivors of the whole call, frame major.
+ * ococc_occ_merge_frames_count checks, in its one-wave launch: start as above; order[p] in [0, R); row_frame[r] in
+ *   [0, F) and non-decreasing along the order, with frame_first[f] <= p < frame_first[f + 1] for f = row_frame[order[p]];
+ *   cloud_start ascending from 0 to N; frame_first ascending from 0 to R.  A failed check: tile_start = 0, no tile runs,
+ *   row_counts [R] = -1 (reported by the caller after its read-back).  Otherwise row_counts[r] is the survivors of row
+ *   r, in the caller's row order.
+ * ococc_occ_merge_frames_fill writes merged [N + K, D + 2] f32, K the sum of tile_counts, in one launch.  With S_f the
+ *   survivors of the frames before f -- taken on the device from tile_scan at the first tile of frame f, K past the last
+ *   tile; nothing is uploaded after the read-back -- segment f begins at row cloud_start[f] + S_f and holds
+ *     the rows of cloud f: points[i, host_use_dim[j]] for j < D, then 0.0f, 0.0f;
+ *     then the survivors of the rows r with row_frame[r] == f, r ascending, a row's cells in input order: x, y, z,
+ *     0.0f for the D - 3 other attributes, the score, 1.0f.
+ *   Segment f is byte for byte what ococc_occ_merge_fill writes for cloud f and the cells of its rows.  Every index
+ *   taken from a table is clamped: a wrong table reads nothing outside [0, M) and [0, N) and writes inside merged.
+ *   K == 0 (or M == 0, R == 0): the real rows only, no table is read.
+ * Integer atomics only; the same input gives the same bytes.
+ * ------------------------------------------------------------------------ */
+int ococc_occ_merge_frames_count(const float* occ, int64_t M, const int64_t* start, const int64_t* order,
+                                 const int64_t* row_frame, int32_t R, const int64_t* cloud_start,
+                                 const int64_t* frame_first, int32_t F, int64_t N, const float* row_score,
+                                 const uint8_t* flags, int32_t drop_observed, float score_threshold,
+                                 int64_t* tile_start, int32_t* tile_counts, int64_t max_tiles, int64_t* row_counts,
+                                 ococc_stream_t stream);
+int ococc_occ_merge_frames_fill(const float* points, int64_t N, int32_t C, const int32_t* host_use_dim, int32_t D,
+                                const float* occ, int64_t M, const int64_t* start, const int64_t* order,
+                                const int64_t* row_frame, const int64_t* tile_start, int32_t R,
+                                const int64_t* cloud_start, const int64_t* frame_first, int32_t F,
+                                const float* row_score, const uint8_t* flags, int32_t drop_observed,
+                                float score_threshold, const int64_t* tile_scan, int64_t max_tiles, float* merged,
+                                int64_t K, ococc_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * observation sample of one online step (csrc/tune_sample.hip): the rows the shape latent of a step is tuned against,
  * behind occ_ops.tune_sample and the ``tune=`` argument of OccBBoxHead.forward_step / forward_steps.  Replaces, for the
  * step, OccAutoEncoder.sample_observation with balance_sample and its cap

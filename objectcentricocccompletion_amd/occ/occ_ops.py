@@ -694,3 +694,125 @@ def occ_merge_aten(points, occ, counts, use_dim=(0, 1, 2, 3, 4), row_score=None,
     tail = torch.cat([occ[keep, :3], occ.new_zeros((int(keep.sum()), D - 3)), score[keep][:, None]], 1)
     tail = torch.cat([tail, torch.ones_like(tail[:, :1])], 1)
     return torch.cat([head, tail], 0), torch.bincount(row[keep], minlength=R).tolist()
+
+
+MERGE_MAX_FRAMES = 65535     # the limit of scene_rows.scene_steps_rows
+
+
+def _occ_merge_frames_shapes(L, what, points, cloud_sizes, occ, counts, frame_rows, use_dim, row_score, flags):
+    """_occ_merge_shapes and what the frames add: (N, C, M, R, use_dim, counts, cloud_sizes, frame_rows), or OcoccError"""
+    N, C, M, R, dim, counts = _occ_merge_shapes(L, what, points, occ, counts, use_dim, row_score, flags)
+    sizes, frame_rows = [int(v) for v in cloud_sizes], [int(v) for v in frame_rows]
+    F = len(sizes)
+    if F > MERGE_MAX_FRAMES:
+        raise L.OcoccError(f'{what}: {F} clouds, at most {MERGE_MAX_FRAMES} per call')
+    if any(s < 0 for s in sizes) or sum(sizes) != N:
+        raise L.OcoccError(f'{what}: cloud_sizes {sizes if F <= 8 else sizes[:8] + ["..."]} must be >= 0 and sum to the {N} points given')
+    if len(frame_rows) != R or any(not 0 <= f < F for f in frame_rows):
+        raise L.OcoccError(f'{what}: frame_rows must hold the cloud 0..{F - 1} of each of the {R} rows of counts, got '
+                           f'{len(frame_rows)} values' + (f' from {min(frame_rows)} to {max(frame_rows)}' if frame_rows else ''))
+    return N, C, M, R, dim, counts, sizes, frame_rows
+
+
+def _prefix(values):
+    out = [0]
+    for v in values:
+        out.append(out[-1] + v)
+    return out
+
+
+def merged_offsets(cloud_sizes, frame_rows, kept):
+    """offsets [F + 1] of the segments of occ_merge_frames: the rows of a frame's cloud and the survivors of its rows"""
+    rows = list(cloud_sizes)
+    for f, k in zip(frame_rows, kept):
+        rows[f] += k
+    return _prefix(rows)
+
+
+def occ_merge_frames(points, cloud_sizes, occ, counts, frame_rows, use_dim=(0, 1, 2, 3, 4), row_score=None, flags=None,
+                     drop_observed=False, score_threshold=0.0):
+    """``occ_merge`` for the clouds of F sensor frames in one call (TrackletRoIHeadOCC.simple_test_scene_steps_merged):
+    ``points`` [N, C] f32 the F clouds back to back, ``cloud_sizes`` their F lengths (ints on the host); ``occ`` [M, 4],
+    ``counts``, ``row_score`` [R], ``flags`` [M] per ROW in the caller's order as in occ_merge, and ``frame_rows``, R ints
+    on the host: the cloud 0..F-1 a row belongs to.  The rows need not be grouped by frame (a chunked step has them
+    slot-major).
+
+    Returns (merged [N + K, D + 2] f32, offsets, kept): segment f = merged[offsets[f]:offsets[f + 1]] is, byte for byte,
+    what occ_merge returns for cloud f and the cells, scores and flags of the rows with frame_rows[i] == f in ascending i;
+    ``offsets`` F + 1 ints and ``kept``, the survivors per input row, are host lists.
+
+    The stable frame-major order of the rows is made on the host (scene_rows.frame_major) and goes up with the cell
+    prefix, the row frames, the cloud prefix and the frames' first positions in ONE copy; then one table and one count
+    launch, one cumsum, ONE read-back (the survivors per row) and one fill launch for any F
+    (ococc_occ_merge_frames_count / _fill, csrc/occ_merge.hip): the fill kernel takes the survivors in front of a frame
+    from the scan, nothing is uploaded after the read-back.  R == 0 or M == 0 skips the count launches and the read-back;
+    F == 0 is an empty [0, D + 2] array with offsets [0].  ``occ_merge_frames_aten`` is the same result as F operator
+    chains: what OCOCC_OCC_MERGE_KERNEL=0 runs.
+
+    Reported before any launch (OcoccError): what occ_merge reports, cloud_sizes that hold a negative or do not sum to N,
+    more than 65535 clouds, frame_rows of another length than counts or outside 0..F-1."""
+    import ctypes
+    from .. import _lib as L
+    from ..scene_rows import frame_major
+    from ..tracklet import host_index_many
+    N, C, M, R, dim, counts, sizes, frame_rows = _occ_merge_frames_shapes(
+        L, 'occ_merge_frames', points, cloud_sizes, occ, counts, frame_rows, use_dim, row_score, flags)
+    L.require_device(points, occ, row_score, flags)
+    if not OCC_MERGE_KERNEL:
+        return occ_merge_frames_aten(points, sizes, occ, counts, frame_rows, dim, row_score, flags, drop_observed,
+                                     score_threshold)
+    dev = points.device
+    D, F = len(dim), len(sizes)
+    points, occ = points.contiguous(), occ.contiguous()
+    row_score = row_score.contiguous() if row_score is not None else None
+    flags = flags.contiguous() if flags is not None and drop_observed else None
+    tiles = int(L.lib.ococc_occ_select_max_tiles(M, R))
+    tab = [None] * 5
+    tile_start = scan = None
+    kept = [0] * R
+    if M:
+        order, first = frame_major(frame_rows, F)
+        tab = host_index_many([_prefix(counts), order, frame_rows, _prefix(sizes), first], dev)
+        tile_start = L.empty((R + 1,), torch.int64, dev)
+        tile_counts = L.empty((tiles,), torch.int32, dev)
+        row_counts = L.empty((R,), torch.int64, dev)
+        L.check(L.lib.ococc_occ_merge_frames_count(
+            L.ptr(occ), M, L.ptr(tab[0]), L.ptr(tab[1]), L.ptr(tab[2]), R, L.ptr(tab[3]), L.ptr(tab[4]), F, N,
+            L.ptr(row_score), L.ptr(flags), int(flags is not None), float(score_threshold), L.ptr(tile_start),
+            L.ptr(tile_counts), tiles, L.ptr(row_counts), L.stream()), 'occ_merge_frames_count')
+        scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts
+        kept = [int(v) for v in row_counts.tolist()]   # the one read-back
+        if min(kept) < 0:
+            raise L.OcoccError('occ_merge_frames: the tables failed the check on the device: start ascending inside '
+                               f'[0, {M}], order inside [0, {R}), frames inside [0, {F}) and non-decreasing along the '
+                               f'order, cloud_start ascending from 0 to {N}')
+    K = sum(kept)
+    merged = L.empty((N + K, D + 2), torch.float32, dev)
+    L.check(L.lib.ococc_occ_merge_frames_fill(
+        L.ptr(points), N, C, (ctypes.c_int32 * D)(*dim), D, L.ptr(occ), M, L.ptr(tab[0]), L.ptr(tab[1]), L.ptr(tab[2]),
+        L.ptr(tile_start), R, L.ptr(tab[3]), L.ptr(tab[4]), F, L.ptr(row_score), L.ptr(flags), int(flags is not None),
+        float(score_threshold), L.ptr(scan), tiles, L.ptr(merged), K, L.stream()), 'occ_merge_frames_fill')
+    return merged, merged_offsets(sizes, frame_rows, kept), kept
+
+
+def occ_merge_frames_aten(points, cloud_sizes, occ, counts, frame_rows, use_dim=(0, 1, 2, 3, 4), row_score=None, flags=None,
+                          drop_observed=False, score_threshold=0.0):
+    """``occ_merge_frames`` as an operator chain on any device, the same bytes: occ_merge_aten per frame on the cloud and
+    the cells, scores and flags of the frame's rows, and one ``cat``.  What OCOCC_OCC_MERGE_KERNEL=0 selects and what the
+    kernels are timed against."""
+    from .. import _lib as L
+    N, C, M, R, dim, counts, sizes, frame_rows = _occ_merge_frames_shapes(
+        L, 'occ_merge_frames_aten', points, cloud_sizes, occ, counts, frame_rows, use_dim, row_score, flags)
+    cloud, cell = _prefix(sizes), _prefix(counts)
+    parts, kept = [], [0] * R
+    for f in range(len(sizes)):
+        rows = [i for i in range(R) if frame_rows[i] == f]
+        pick = lambda t: None if t is None else (torch.cat([t[cell[i]:cell[i + 1]] for i in rows]) if rows else t[:0])
+        score = None if row_score is None else row_score[rows]
+        part, k = occ_merge_aten(points[cloud[f]:cloud[f + 1]], pick(occ), [counts[i] for i in rows], dim, score,
+                                 pick(flags), drop_observed, score_threshold)
+        parts.append(part)
+        for i, v in zip(rows, k):
+            kept[i] = int(v)
+    merged = torch.cat(parts, 0) if parts else points.new_zeros((0, len(dim) + 2))
+    return merged, merged_offsets(sizes, frame_rows, kept), kept

@@ -713,8 +713,8 @@ class TrackletRoIHeadOCC(nn.Module):
         and with ``occ=True`` ``occ_ego`` (each row's cells in the ego frame of ITS cloud), ``occ_flags``, ``occ_counts``.
         ``tune`` passes through.  n == 0 returns empty tensors for every key, launches nothing and leaves the state as it is.
 
-        There is no ``merged=`` here: the occupancy-enhanced cloud is one array per sensor frame and occ_merge a count, a
-        read-back and a fill per cloud, so a caller who needs merged clouds steps frame by frame (simple_test_scene_step).
+        The occupancy-enhanced clouds of the F frames of such a call come from simple_test_scene_steps_merged, which runs
+        this method with ``occ=True`` and merges all F clouds with one count launch, one read-back and one fill launch.
 
         Reported on the host before anything is launched: what simple_test_steps reports, poses that are not [F, 4, 4], not
         finite or singular, cloud_sizes of another length than F, frame_rows outside 0..F-1, repeating or going back inside
@@ -797,6 +797,42 @@ class TrackletRoIHeadOCC(nn.Module):
         out['boxes_ego'] = torch.where(out['valid'].to(dev).bool()[:, None], self._boxes_through(out['boxes'], mats[1]),
                                        boxes[:, :7])
         out['num_points'] = counts
+        return out
+
+    @torch.no_grad()
+    def simple_test_scene_steps_merged(self, points, cloud_sizes, poses, boxes, scores, labels, frame_rows, slot_rows, state,
+                                       merged=True, gt_rois=None, tune=None):
+        """simple_test_scene_steps with ``occ=True`` and the occupancy-enhanced cloud of EVERY frame of the call, the arrays
+        F calls of simple_test_scene_step(merged=...) return as ``points_merged``, in one array: ``merged`` is True
+        (test_cfg.online_merged) or a dict that overrides it (online_merged_cfg); the other arguments are those of
+        simple_test_scene_steps.
+
+        Returns the dict of simple_test_scene_steps(..., occ=True) and three more keys: ``points_merged`` [N + K, D + 2]
+        f32, frame after frame -- the rows of cloud f as ``points[:, use_dim]`` with two zero columns, then the surviving
+        cells of the rows with frame_rows[i] == f in ascending i as x, y, z, D - 3 zeros, the row's score, 1 --,
+        ``merged_offsets``, F + 1 ints on the host: frame f is points_merged[merged_offsets[f]:merged_offsets[f + 1]], and
+        ``merged_counts``, the survivors per input row as a list of int on the host.  The score of a row is
+        where(valid, refined score, input score) as f32, the rule of simple_test_scene_step.  All F clouds are merged by
+        occ_ops.occ_merge_frames: one count launch, one read-back and one fill launch, whatever F.
+
+        With n == 0 nothing is stepped and the state is as it was: ``points_merged`` is the F clouds with their two zero
+        columns and ``merged_offsets`` the prefix of cloud_sizes.
+
+        Reported on the host before anything is launched: what simple_test_scene_steps reports, a wrong ``merged`` or
+        test_cfg.online_merged (ValueError), a ``use_dim`` beyond the cloud's columns (OcoccError)."""
+        from . import _lib as L
+        from .occ.occ_ops import occ_merge_frames
+        if self.training:
+            raise RuntimeError('simple_test_scene_steps_merged is inference only: call .eval() first')
+        cfg = self.online_merged_cfg(merged)
+        if points.dim() != 2 or max(cfg['use_dim']) >= points.size(1):
+            raise L.OcoccError(f'merged: use_dim {cfg["use_dim"]} of a cloud {tuple(points.shape)}')
+        out = self.simple_test_scene_steps(points, cloud_sizes, poses, boxes, scores, labels, frame_rows, slot_rows, state,
+                                           gt_rois=gt_rois, occ=True, tune=tune)
+        row_score = torch.where(out['valid'].to(boxes.device).bool(), out['scores'].float(), scores.float())
+        out['points_merged'], out['merged_offsets'], out['merged_counts'] = occ_merge_frames(
+            points, cloud_sizes, out['occ_ego'], out['occ_counts'], frame_rows, cfg['use_dim'], row_score=row_score,
+            flags=out['occ_flags'], drop_observed=cfg['drop_observed'], score_threshold=cfg['score_threshold'])
         return out
 
     def online_chunk(self):

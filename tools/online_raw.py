@@ -5,7 +5,8 @@ clouds) stepped through frame by frame, the way the method is deployed -- no tra
 
     python tools/online_raw.py <config> <checkpoint> <raw.yaml> [--slots 64] [--out FILE.bin] [--poses poses.pkl] [--chunk T]
                                [--save-occ DIR] [--step-tuning N [--step-tuning-samples S]] [--cfg-options k=v ...]
-                               [--save-merged DIR [--merged-use-dim 5] [--merged-score-threshold 0] [--merged-drop-observed]]
+                               [--save-merged DIR [--merged-use-dim 5] [--merged-score-threshold 0] [--merged-drop-observed]
+                                [--merged-per-call]]
 
 Per segment and frame, in time order: the frame's scene cloud is loaded once, every track that starts at the frame gets a
 free slot of the temporal K/V cache, TrackletRoIHeadOCC.simple_test_scene_step refines all live tracks in one call (crop,
@@ -26,6 +27,9 @@ merged=...): ``points_merged``, csrc/occ_merge.hip) and the tool writes ``<DIR>/
 frame, float32 [N + K, D + 2]: the first D columns of the frame's cloud with two zero columns, then the cells of the
 frame's objects whose score passes --merged-score-threshold as x, y, z, D - 3 zeros, score, 1 -- the array
 pipelines.LoadPointsAndOccPredFromFile builds from the cloud file and the --save-occ files of the frame.
+--chunk T with --save-merged needs --merged-per-call: the T clouds of a call are then merged by ONE
+TrackletRoIHeadOCC.simple_test_scene_steps_merged call (occ_ops.occ_merge_frames: one count launch, one read-back, one
+fill launch for the T clouds) and cut into the same per-timestamp files at ``merged_offsets``.
 Config and checkpoint are loaded as tools/test.py loads them."""
 import argparse
 import os
@@ -57,7 +61,7 @@ def choose_cache(roi_head, longest):
 
 
 def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_occ=None, save_merged=None, merged=True,
-           chunk=1):
+           chunk=1, merged_per_call=False):
     """``model``: a TrackletDetectorOCC in eval mode on a ROCm device; ``raw_yaml``: the track-input yaml (path or mapping,
     ctrl_prep.load_config); ``poses``: {timestamp: 4x4 ego -> world} or the path of its pickle (default: the yaml's
     ``poses_path``, else <mm_data_root>/poses.pkl).  Returns (records, state): one record per object of the tracker's
@@ -72,14 +76,19 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_oc
     ``chunk`` = T > 1: T consecutive timestamps of a segment per simple_test_scene_steps call, rows slot-major (the last call
     of a segment takes the rest); a track that starts inside the T timestamps has its slot before the call, one that ends
     inside them gives it back after the call, so the call needs a slot for every track live anywhere in it.  Records and
-    files are those of chunk = 1; not with ``save_merged`` (the merged cloud is made per frame: simple_test_scene_steps)."""
+    files are those of chunk = 1.  ``chunk`` > 1 with ``save_merged`` is refused unless ``merged_per_call`` is set: the call
+    is then simple_test_scene_steps_merged, which merges the T clouds of the call at once, and the files of its timestamps
+    are cut from ``points_merged`` at ``merged_offsets`` -- still one read-back per call."""
     import numpy as np
     import torch
     from objectcentricocccompletion_amd import _lib as L
     from objectcentricocccompletion_amd import ctrl_prep, occ_export, waymo_io
     chunk = int(chunk)
-    if chunk < 1 or (chunk > 1 and save_merged):
-        raise ValueError('chunk is the number of timestamps per call, an int >= 1, and 1 with save_merged')
+    if chunk < 1 or (chunk > 1 and save_merged and not merged_per_call):
+        raise ValueError('chunk is the number of timestamps per call, an int >= 1, and 1 with save_merged unless '
+                         'merged_per_call (--merged-per-call) is set')
+    if merged_per_call and not save_merged:
+        raise ValueError('merged_per_call goes with save_merged')
     cfg, _ = ctrl_prep.load_config(raw_yaml)
     rh = model.roi_head
     dev = torch.device(device) if device is not None else next(model.parameters()).device
@@ -134,10 +143,11 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_oc
                 res = rh.simple_test_scene_step(torch.from_numpy(clouds[0]).to(dev), np.asarray(poses[group[0]], dtype=np.float64),
                                                 boxes, scores, labels, [slot_of[k] for k, _, _ in rows], state, **step_kw)
             else:                                    # the clouds of the call: one host -> device copy
-                res = rh.simple_test_scene_steps(torch.from_numpy(np.concatenate(clouds)).to(dev), [len(c) for c in clouds],
-                                                 np.stack([np.asarray(poses[ts], dtype=np.float64) for ts in group]), boxes,
-                                                 scores, labels, [f for _, _, f in rows], [slot_of[k] for k, _, _ in rows],
-                                                 state, **step_kw)
+                steps = rh.simple_test_scene_steps_merged if save_merged else rh.simple_test_scene_steps
+                res = steps(torch.from_numpy(np.concatenate(clouds)).to(dev), [len(c) for c in clouds],
+                            np.stack([np.asarray(poses[ts], dtype=np.float64) for ts in group]), boxes, scores, labels,
+                            [f for _, _, f in rows], [slot_of[k] for k, _, _ in rows], state,
+                            **({'merged': merged} if save_merged else step_kw))
             valid = res['valid'].to(dev).bool()
             back = torch.cat([res['boxes_ego'], torch.where(valid, res['scores'].float(), scores)[:, None],
                               valid[:, None].float()], 1)
@@ -148,10 +158,14 @@ def replay(model, raw_yaml, slots=64, out=None, poses=None, device=None, save_oc
                 if save_occ:
                     cells = flat[1].view(-1, 4).numpy()
                     cuts = np.cumsum([0] + list(res['occ_counts']))
-                if save_merged:                                           # (chunk == 1: the frame of the call)
-                    path = os.path.join(save_merged, str(seg), f'{group[0]}.bin')
-                    os.makedirs(os.path.dirname(path), exist_ok=True)
-                    flat[-1].numpy().tofile(path)
+                if save_merged:                                           # a file per timestamp of the call
+                    cloud = flat[-1].numpy()
+                    width = res['points_merged'].size(1)
+                    at_row = res.get('merged_offsets', [0, res['points_merged'].size(0)])
+                    for f, ts in enumerate(group):
+                        path = os.path.join(save_merged, str(seg), f'{ts}.bin')
+                        os.makedirs(os.path.dirname(path), exist_ok=True)
+                        cloud[at_row[f] * width:at_row[f + 1] * width].tofile(path)
             else:
                 back = back.cpu()                                         # one read-back per call
             done = []
@@ -213,7 +227,11 @@ def parse_args(argv=None):
                     help='leave out the cells a real point of the frame fell into')
     ap.add_argument('--chunk', type=int, metavar='T', default=1,
                     help='T consecutive timestamps of a segment per call (simple_test_scene_steps: the rows of T clouds from one '
-                    'count launch, one read-back and one fill launch, one head pass); not with --save-merged')
+                    'count launch, one read-back and one fill launch, one head pass); with --save-merged only together '
+                    'with --merged-per-call')
+    ap.add_argument('--merged-per-call', action='store_true',
+                    help='with --chunk T and --save-merged: merge the T clouds of a call at once '
+                    '(simple_test_scene_steps_merged) and cut the per-timestamp files from the result')
     ap.add_argument('--step-tuning', type=int, metavar='N', default=None,
                     help='tune the fused shape latent of every live track against the frame\'s own points with N Adam steps '
                     'inside the step (sets test_cfg.online_step_tuning = dict(num_iter=N, downsample_size=S, '
@@ -226,8 +244,11 @@ def parse_args(argv=None):
         ap.error('--slots takes a number of tracks >= 1')
     if args.chunk < 1:
         ap.error('--chunk takes a number of timestamps >= 1')
-    if args.chunk > 1 and args.save_merged is not None:
-        ap.error('--chunk above 1 does not go with --save-merged: the occupancy-enhanced cloud is made per frame')
+    if args.merged_per_call and args.save_merged is None:
+        ap.error('--merged-per-call goes with --save-merged')
+    if args.chunk > 1 and args.save_merged is not None and not args.merged_per_call:
+        ap.error('--chunk above 1 goes with --save-merged only under --merged-per-call: the occupancy-enhanced clouds of '
+                 'a call are then merged at once')
     if args.step_tuning is not None and args.step_tuning < 0:
         ap.error('--step-tuning takes a number of iterations >= 0')
     if args.step_tuning_samples is not None and args.step_tuning is None:
@@ -277,7 +298,8 @@ def main(argv=None):
     raw, _ = ctrl_prep.load_config(args.raw_yaml)
     out = args.out or os.path.splitext(ctrl_prep.bin_path_for_split(raw))[0] + '_online.bin'
     records, _ = replay(model, args.raw_yaml, slots=args.slots, out=out, poses=args.poses, device=dev, save_occ=args.save_occ,
-                        save_merged=args.save_merged, merged=merged_arg(args), chunk=args.chunk)
+                        save_merged=args.save_merged, merged=merged_arg(args), chunk=args.chunk,
+                        merged_per_call=args.merged_per_call)
     print(f'{len(records)} objects, {sum(r["refined"] for r in records)} refined; wrote {out}')
     if args.save_occ:
         print(f'{sum(r.get("occ_cells", 0) for r in records)} occupancy cells in {args.save_occ}')

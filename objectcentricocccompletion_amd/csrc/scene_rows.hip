@@ -186,16 +186,56 @@ scene_rows_kernel(const float* __restrict__ points, int64_t n, int32_t C, const 
   }
 }
 
+// ---- the host side: one check and one pass behind the four exports (as merge_count / merge_fill, occ_merge.hip)
+#define ROWS_REQUIRE(cond, msg)                               \
+  do {                                                        \
+    if (!(cond)) return ococc_fail(OCOCC_EINVAL, fn, msg);    \
+  } while (0)
+#define ROWS_HIP(call)                                                                   \
+  do {                                                                                   \
+    hipError_t e__ = (call);                                                             \
+    if (e__ != hipSuccess) return ococc_fail(OCOCC_EHIP, fn, hipGetErrorString(e__));    \
+  } while (0)
+
+// An export's arguments.  The one-cloud exports (`many` false) have one frame, and its largest frame is the cloud; the
+// count exports leave what follows `fr` zero.
+struct RowsArgs {
+  const float* points;
+  int64_t n;
+  int32_t c;
+  const float* boxes;
+  int64_t b;
+  const float *transforms, *range;
+  const void* workspace;
+  int64_t workspace_bytes;
+  bool many;
+  int32_t frames;
+  int64_t max_points, max_boxes;   // of the largest frame
+  FrameArgs fr;
+  int32_t A, K;   // attr_dims, row_feat_dim
+  const float* row_feats;
+  int64_t cap;
+  const int64_t *scan_all, *scan_out;   // many: the boxes' totals and first output rows
+  float *out_xyz, *out_feats;
+  int64_t* out_row;
+};
+
 // 1: nothing to do (an empty cloud or no boxes), 0: launch, < 0: reported
-int rows_check(const float* points, int64_t n, int32_t c, const float* boxes, int64_t b, const void* workspace,
-               int64_t workspace_bytes, const char* fn) {
-  if (n < 0 || b < 0) return ococc_fail(OCOCC_EINVAL, fn, "negative size");
-  if (n > 2147483647LL || b > 2147483647LL) return ococc_fail(OCOCC_EINVAL, fn, "at most 2^31 - 1 points and boxes");
-  if (c < 3) return ococc_fail(OCOCC_EINVAL, fn, "points need at least 3 columns");
-  if (b == 0 || n == 0) return 1;
-  if (!points || !boxes || !workspace) return ococc_fail(OCOCC_EINVAL, fn, "null pointer");
-  if (workspace_bytes < ococc_scene_rows_workspace_bytes(n, b))
-    return ococc_fail(OCOCC_EINVAL, fn, "workspace too small: ococc_scene_rows_workspace_bytes(num_points, num_boxes)");
+int rows_check(const char* fn, const RowsArgs& in) {
+  if (in.n < 0 || in.b < 0 || in.frames < 0 || in.max_points < 0 || in.max_boxes < 0)
+    return ococc_fail(OCOCC_EINVAL, fn, "negative size");
+  if (in.n > 2147483647LL || in.b > 2147483647LL) return ococc_fail(OCOCC_EINVAL, fn, "at most 2^31 - 1 points and boxes");
+  if (in.max_points > in.n || in.max_boxes > in.b)
+    return ococc_fail(OCOCC_EINVAL, fn, "max_frame_points > num_points or max_frame_boxes > num_boxes");
+  if (in.c < 3) return ococc_fail(OCOCC_EINVAL, fn, "points need at least 3 columns");
+  if (in.frames > 65535) return ococc_fail(OCOCC_EINVAL, fn, "at most 65535 frames per call");
+  if (in.b == 0 || in.n == 0 || in.frames == 0 || in.max_points == 0 || in.max_boxes == 0) return 1;
+  if (!in.points || !in.boxes || !in.workspace || (in.many && (!in.fr.cloud_offsets || !in.fr.box_offsets)))
+    return ococc_fail(OCOCC_EINVAL, fn, "null pointer");
+  if (in.workspace_bytes < ococc_scene_rows_workspace_bytes(in.max_points, in.b))
+    return ococc_fail(OCOCC_EINVAL, fn,
+                      in.many ? "workspace too small: ococc_scene_rows_workspace_bytes(max_frame_points, num_boxes)"
+                              : "workspace too small: ococc_scene_rows_workspace_bytes(num_points, num_boxes)");
   return OCOCC_OK;
 }
 
@@ -211,33 +251,49 @@ int32_t box_span(int64_t n, int64_t b, int64_t frames = 1) {
   return (int32_t)ococc_cdiv(b, parts < 1 ? 1 : parts);
 }
 
-// the checks of the many-cloud exports -- 1: nothing to do, 0: launch, < 0: reported
-int frames_check(const float* points, int64_t n, int32_t c, const int64_t* cloud_offsets, const float* boxes, int64_t b,
-                 const int64_t* box_offsets, int32_t frames, int64_t max_frame_points, int64_t max_frame_boxes,
-                 const void* workspace, int64_t workspace_bytes, const char* fn) {
-  if (n < 0 || b < 0 || frames < 0 || max_frame_points < 0 || max_frame_boxes < 0)
-    return ococc_fail(OCOCC_EINVAL, fn, "negative size");
-  if (n > 2147483647LL || b > 2147483647LL) return ococc_fail(OCOCC_EINVAL, fn, "at most 2^31 - 1 points and boxes");
-  if (max_frame_points > n || max_frame_boxes > b)
-    return ococc_fail(OCOCC_EINVAL, fn, "max_frame_points > num_points or max_frame_boxes > num_boxes");
-  if (c < 3) return ococc_fail(OCOCC_EINVAL, fn, "points need at least 3 columns");
-  if (frames > 65535) return ococc_fail(OCOCC_EINVAL, fn, "at most 65535 frames per call");
-  if (b == 0 || n == 0 || frames == 0 || max_frame_points == 0 || max_frame_boxes == 0) return 1;
-  if (!points || !cloud_offsets || !boxes || !box_offsets || !workspace) return ococc_fail(OCOCC_EINVAL, fn, "null pointer");
-  if (workspace_bytes < ococc_scene_rows_workspace_bytes(max_frame_points, b))
-    return ococc_fail(OCOCC_EINVAL, fn, "workspace too small: ococc_scene_rows_workspace_bytes(max_frame_points, num_boxes)");
-  return OCOCC_OK;
-}
-
-// blockIdx.x: workgroups along the largest frame's points, y: frame, z: spans of the frame's boxes
-dim3 frames_grid(int32_t frames, int64_t max_frame_points, int64_t max_frame_boxes, int32_t span) {
-  return dim3((unsigned)ococc_cdiv(max_frame_points, kBlockTile), (unsigned)frames, (unsigned)ococc_cdiv(max_frame_boxes, span));
-}
-
 Range6 range_arg(const float* range) {
   Range6 r = {{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}};
   if (range) memcpy(r.v, range, sizeof(r.v));
   return r;
+}
+
+// Either pass: the checks, then the launch.  Grid: blockIdx.x the workgroups along the (largest frame's) points; one cloud:
+// y the spans of the boxes; many: y the frame, z the spans of the frame's boxes.
+int rows_pass(bool fill, const char* fn, const RowsArgs& in, int64_t* counts, hipStream_t stream) {
+  const int rc = rows_check(fn, in);
+  if (rc < 0) return rc;
+  if (!fill && in.b > 0) {
+    ROWS_REQUIRE(counts, "null counts");
+    ROWS_HIP(hipMemsetAsync(counts, 0, in.b * sizeof(int64_t), stream));
+  }
+  if (fill) {
+    ROWS_REQUIRE(in.A >= 0 && in.K >= 0 && 3 + (int64_t)in.A <= in.c,
+                 "attr_dims and row_feat_dim are >= 0, and 3 + attr_dims <= point_dim");
+    ROWS_REQUIRE(in.cap <= 2147483647LL, "max_points is at most 2^31 - 1 (<= 0: no cap)");
+    ROWS_REQUIRE(in.fr.num_out >= 0, "negative num_out");
+  }
+  if (rc == 1 || (fill && in.many && in.fr.num_out == 0)) return OCOCC_OK;
+  if (fill) {
+    ROWS_REQUIRE(in.scan_all && in.scan_out && in.out_xyz && in.out_row && (in.fr.caller_rows || !in.many),
+                 in.many ? "null caller_rows, box_totals, box_starts, out_xyz or out_row"
+                         : "null scan_all, scan_out, out_xyz or out_row");
+    ROWS_REQUIRE(in.K == 0 || in.row_feats, "null row_feats");
+    ROWS_REQUIRE(in.A + in.K == 0 || in.out_feats, "null out_feats");
+  }
+  static const decltype(&scene_rows_kernel<false, true, false>) kernels[2][2][2] = {   // [many][fill][no transforms, no range]
+      {{scene_rows_kernel<false, true, false>, scene_rows_kernel<false, false, false>},
+       {scene_rows_kernel<true, true, false>, scene_rows_kernel<true, false, false>}},
+      {{scene_rows_kernel<false, true, true>, scene_rows_kernel<false, false, true>},
+       {scene_rows_kernel<true, true, true>, scene_rows_kernel<true, false, true>}}};
+  const auto kernel = kernels[in.many][fill][!(in.transforms || in.range)];
+  const int32_t span = box_span(in.max_points, in.max_boxes, in.frames);
+  const unsigned tiles = (unsigned)ococc_cdiv(in.max_points, kBlockTile), spans = (unsigned)ococc_cdiv(in.max_boxes, span);
+  hipLaunchKernelGGL(kernel, in.many ? dim3(tiles, (unsigned)in.frames, spans) : dim3(tiles, spans), dim3(64 * kWaves), 0,
+                     stream, in.points, in.n, in.c, in.boxes, (int32_t)in.b, span, in.transforms, range_arg(in.range),
+                     (int32_t)(in.range != nullptr), (int32_t*)const_cast<void*>(in.workspace), (unsigned long long*)counts,
+                     in.A, in.row_feats, in.K, in.cap, in.scan_all, in.scan_out, in.out_xyz, in.out_feats, in.out_row, in.fr);
+  ROWS_HIP(hipGetLastError());
+  return OCOCC_OK;
 }
 
 }  // namespace
@@ -250,25 +306,10 @@ extern "C" int64_t ococc_scene_rows_workspace_bytes(int64_t num_points, int64_t 
 extern "C" int ococc_scene_rows_count(const float* points, int64_t num_points, int32_t point_dim,
                                       const float* crop_boxes, int64_t num_boxes, const float* transforms,
                                       const float* range, int64_t* counts, void* workspace, int64_t workspace_bytes,
-                                      ococc_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const int rc = rows_check(points, num_points, point_dim, crop_boxes, num_boxes, workspace, workspace_bytes, __func__);
-  if (rc < 0) return rc;
-  if (num_boxes > 0) {
-    OCOCC_REQUIRE(counts, "null counts");
-    OCOCC_HIP(hipMemsetAsync(counts, 0, num_boxes * sizeof(int64_t), stream));
-  }
-  if (rc == 1) return OCOCC_OK;
-  const auto kernel = (transforms || range) ? scene_rows_kernel<false, true, false> : scene_rows_kernel<false, false, false>;
-  const int32_t span = box_span(num_points, num_boxes);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)ococc_cdiv(num_points, kBlockTile), (unsigned)ococc_cdiv(num_boxes, span)),
-                     dim3(64 * kWaves), 0, stream, points, num_points, point_dim, crop_boxes, (int32_t)num_boxes, span,
-                     transforms, range_arg(range), (int32_t)(range != nullptr), (int32_t*)workspace,
-                     (unsigned long long*)counts, 0,
-                     (const float*)nullptr, 0, (int64_t)0, (const int64_t*)nullptr, (const int64_t*)nullptr,
-                     (float*)nullptr, (float*)nullptr, (int64_t*)nullptr, FrameArgs{nullptr, nullptr, nullptr, 0});
-  OCOCC_CHECK_LAUNCH();
-  return OCOCC_OK;
+                                      ococc_stream_t stream) {
+  return rows_pass(false, __func__, RowsArgs{points, num_points, point_dim, crop_boxes, num_boxes, transforms, range,
+                                             workspace, workspace_bytes, false, 1, num_points, num_boxes},
+                          counts, (hipStream_t)stream);
 }
 
 extern "C" int ococc_scene_rows_fill(const float* points, int64_t num_points, int32_t point_dim, const float* crop_boxes,
@@ -276,25 +317,12 @@ extern "C" int ococc_scene_rows_fill(const float* points, int64_t num_points, in
                                      const float* row_feats, int32_t row_feat_dim, int64_t max_points,
                                      const int64_t* scan_all, const int64_t* scan_out, float* out_xyz, float* out_feats,
                                      int64_t* out_row, const void* workspace, int64_t workspace_bytes,
-                                     ococc_stream_t stream_) {
-  const int rc = rows_check(points, num_points, point_dim, crop_boxes, num_boxes, workspace, workspace_bytes, __func__);
-  if (rc < 0) return rc;
-  OCOCC_REQUIRE(attr_dims >= 0 && row_feat_dim >= 0 && 3 + (int64_t)attr_dims <= point_dim,
-                "attr_dims and row_feat_dim are >= 0, and 3 + attr_dims <= point_dim");
-  OCOCC_REQUIRE(max_points <= 2147483647LL, "max_points is at most 2^31 - 1 (<= 0: no cap)");
-  if (rc == 1) return OCOCC_OK;
-  OCOCC_REQUIRE(scan_all && scan_out && out_xyz && out_row, "null scan_all, scan_out, out_xyz or out_row");
-  OCOCC_REQUIRE(row_feat_dim == 0 || row_feats, "null row_feats");
-  OCOCC_REQUIRE(attr_dims + row_feat_dim == 0 || out_feats, "null out_feats");
-  const auto kernel = (transforms || range) ? scene_rows_kernel<true, true, false> : scene_rows_kernel<true, false, false>;
-  const int32_t span = box_span(num_points, num_boxes);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)ococc_cdiv(num_points, kBlockTile), (unsigned)ococc_cdiv(num_boxes, span)),
-                     dim3(64 * kWaves), 0, (hipStream_t)stream_, points, num_points, point_dim, crop_boxes,
-                     (int32_t)num_boxes, span, transforms, range_arg(range), (int32_t)(range != nullptr),
-                     (int32_t*)const_cast<void*>(workspace), (unsigned long long*)nullptr, attr_dims, row_feats, row_feat_dim, max_points, scan_all, scan_out,
-                     out_xyz, out_feats, out_row, FrameArgs{nullptr, nullptr, nullptr, 0});
-  OCOCC_CHECK_LAUNCH();
-  return OCOCC_OK;
+                                     ococc_stream_t stream) {
+  return rows_pass(true, __func__, RowsArgs{points, num_points, point_dim, crop_boxes, num_boxes, transforms, range,
+                                            workspace, workspace_bytes, false, 1, num_points, num_boxes, FrameArgs{},
+                                            attr_dims, row_feat_dim, row_feats, max_points, scan_all, scan_out, out_xyz,
+                                            out_feats, out_row},
+                         nullptr, (hipStream_t)stream);
 }
 
 extern "C" int ococc_scene_rows_frames_count(const float* points, int64_t num_points, int32_t point_dim,
@@ -302,26 +330,11 @@ extern "C" int ococc_scene_rows_frames_count(const float* points, int64_t num_po
                                              const int64_t* box_offsets, int32_t frames, int64_t max_frame_points,
                                              int64_t max_frame_boxes, const float* transforms, const float* range,
                                              int64_t* counts, void* workspace, int64_t workspace_bytes,
-                                             ococc_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  const int rc = frames_check(points, num_points, point_dim, cloud_offsets, crop_boxes, num_boxes, box_offsets, frames,
-                              max_frame_points, max_frame_boxes, workspace, workspace_bytes, __func__);
-  if (rc < 0) return rc;
-  if (num_boxes > 0) {
-    OCOCC_REQUIRE(counts, "null counts");
-    OCOCC_HIP(hipMemsetAsync(counts, 0, num_boxes * sizeof(int64_t), stream));
-  }
-  if (rc == 1) return OCOCC_OK;
-  const auto kernel = (transforms || range) ? scene_rows_kernel<false, true, true> : scene_rows_kernel<false, false, true>;
-  const int32_t span = box_span(max_frame_points, max_frame_boxes, frames);
-  hipLaunchKernelGGL(kernel, frames_grid(frames, max_frame_points, max_frame_boxes, span), dim3(64 * kWaves), 0, stream,
-                     points, num_points, point_dim, crop_boxes, (int32_t)num_boxes, span, transforms, range_arg(range),
-                     (int32_t)(range != nullptr), (int32_t*)workspace, (unsigned long long*)counts, 0,
-                     (const float*)nullptr, 0, (int64_t)0, (const int64_t*)nullptr, (const int64_t*)nullptr,
-                     (float*)nullptr, (float*)nullptr, (int64_t*)nullptr,
-                     FrameArgs{cloud_offsets, box_offsets, nullptr, 0});
-  OCOCC_CHECK_LAUNCH();
-  return OCOCC_OK;
+                                             ococc_stream_t stream) {
+  return rows_pass(false, __func__, RowsArgs{points, num_points, point_dim, crop_boxes, num_boxes, transforms, range,
+                                             workspace, workspace_bytes, true, frames, max_frame_points, max_frame_boxes,
+                                             FrameArgs{cloud_offsets, box_offsets, nullptr, 0}},
+                          counts, (hipStream_t)stream);
 }
 
 extern "C" int ococc_scene_rows_frames_fill(const float* points, int64_t num_points, int32_t point_dim,
@@ -332,26 +345,11 @@ extern "C" int ococc_scene_rows_frames_fill(const float* points, int64_t num_poi
                                             const int64_t* caller_rows, int64_t max_points, const int64_t* box_totals,
                                             const int64_t* box_starts, int64_t num_out, float* out_xyz,
                                             float* out_feats, int64_t* out_row, const void* workspace,
-                                            int64_t workspace_bytes, ococc_stream_t stream_) {
-  const int rc = frames_check(points, num_points, point_dim, cloud_offsets, crop_boxes, num_boxes, box_offsets, frames,
-                              max_frame_points, max_frame_boxes, workspace, workspace_bytes, __func__);
-  if (rc < 0) return rc;
-  OCOCC_REQUIRE(attr_dims >= 0 && row_feat_dim >= 0 && 3 + (int64_t)attr_dims <= point_dim,
-                "attr_dims and row_feat_dim are >= 0, and 3 + attr_dims <= point_dim");
-  OCOCC_REQUIRE(max_points <= 2147483647LL, "max_points is at most 2^31 - 1 (<= 0: no cap)");
-  OCOCC_REQUIRE(num_out >= 0, "negative num_out");
-  if (rc == 1 || num_out == 0) return OCOCC_OK;
-  OCOCC_REQUIRE(caller_rows && box_totals && box_starts && out_xyz && out_row,
-                "null caller_rows, box_totals, box_starts, out_xyz or out_row");
-  OCOCC_REQUIRE(row_feat_dim == 0 || row_feats, "null row_feats");
-  OCOCC_REQUIRE(attr_dims + row_feat_dim == 0 || out_feats, "null out_feats");
-  const auto kernel = (transforms || range) ? scene_rows_kernel<true, true, true> : scene_rows_kernel<true, false, true>;
-  const int32_t span = box_span(max_frame_points, max_frame_boxes, frames);
-  hipLaunchKernelGGL(kernel, frames_grid(frames, max_frame_points, max_frame_boxes, span), dim3(64 * kWaves), 0,
-                     (hipStream_t)stream_, points, num_points, point_dim, crop_boxes, (int32_t)num_boxes, span, transforms,
-                     range_arg(range), (int32_t)(range != nullptr), (int32_t*)const_cast<void*>(workspace),
-                     (unsigned long long*)nullptr, attr_dims, row_feats, row_feat_dim, max_points, box_totals, box_starts,
-                     out_xyz, out_feats, out_row, FrameArgs{cloud_offsets, box_offsets, caller_rows, num_out});
-  OCOCC_CHECK_LAUNCH();
-  return OCOCC_OK;
+                                            int64_t workspace_bytes, ococc_stream_t stream) {
+  return rows_pass(true, __func__, RowsArgs{points, num_points, point_dim, crop_boxes, num_boxes, transforms, range,
+                                            workspace, workspace_bytes, true, frames, max_frame_points, max_frame_boxes,
+                                            FrameArgs{cloud_offsets, box_offsets, caller_rows, num_out}, attr_dims,
+                                            row_feat_dim, row_feats, max_points, box_totals, box_starts, out_xyz,
+                                            out_feats, out_row},
+                         nullptr, (hipStream_t)stream);
 }

@@ -597,8 +597,12 @@ def merge_use_dim(use_dim):
     return tuple(int(v) for v in use_dim)
 
 
-def _occ_merge_shapes(L, what, points, occ, counts, use_dim, row_score, flags):
-    """(N, C, M, R, use_dim as a tuple, counts as a list of int) of the inputs of occ_merge / occ_merge_aten, or OcoccError."""
+MERGE_MAX_FRAMES = 65535     # the limit of scene_rows.scene_steps_rows
+
+
+def _occ_merge_shapes(L, what, points, occ, counts, use_dim, row_score, flags, frames=None):
+    """(N, C, M, R, use_dim as a tuple, counts as a list of int, frames) of the inputs of occ_merge(_frames) and their
+    ``_aten`` chains, or OcoccError; ``frames`` None (one cloud) or (cloud_sizes, frame_rows), returned as lists of int."""
     if points.dtype != torch.float32 or points.dim() != 2:
         raise L.OcoccError(f'{what}: points {tuple(points.shape)} {points.dtype} are not f32 [N, C]')
     if occ.dtype != torch.float32 or occ.dim() != 2 or occ.size(1) != 4:
@@ -615,7 +619,17 @@ def _occ_merge_shapes(L, what, points, occ, counts, use_dim, row_score, flags):
         raise L.OcoccError(f'{what}: row_score {tuple(row_score.shape)} {row_score.dtype} is not f32 [{R}]')
     if flags is not None and (flags.dtype != torch.uint8 or tuple(flags.shape) != (M,)):
         raise L.OcoccError(f'{what}: flags {tuple(flags.shape)} {flags.dtype} are not uint8 [{M}]')
-    return N, C, M, R, dim, counts
+    if frames is not None:
+        sizes, frame_rows = frames = [int(v) for v in frames[0]], [int(v) for v in frames[1]]
+        F = len(sizes)
+        if F > MERGE_MAX_FRAMES:
+            raise L.OcoccError(f'{what}: {F} clouds, at most {MERGE_MAX_FRAMES} per call')
+        if any(s < 0 for s in sizes) or sum(sizes) != N:
+            raise L.OcoccError(f'{what}: cloud_sizes {sizes if F <= 8 else sizes[:8] + ["..."]} must be >= 0 and sum to the {N} points given')
+        if len(frame_rows) != R or any(not 0 <= f < F for f in frame_rows):
+            raise L.OcoccError(f'{what}: frame_rows must hold the cloud 0..{F - 1} of each of the {R} rows of counts, got '
+                               f'{len(frame_rows)} values' + (f' from {min(frame_rows)} to {max(frame_rows)}' if frame_rows else ''))
+    return N, C, M, R, dim, counts, frames
 
 
 def occ_merge(points, occ, counts, use_dim=(0, 1, 2, 3, 4), row_score=None, flags=None, drop_observed=False,
@@ -635,43 +649,7 @@ def occ_merge(points, occ, counts, use_dim=(0, 1, 2, 3, 4), row_score=None, flag
     One table and one count launch, one cumsum, ONE read-back (the survivors per object; K is their sum), one fill launch
     that also copies the real rows (csrc/occ_merge.hip); without cells the count launches and the read-back are skipped.
     ``occ_merge_aten`` is the same result as a torch operator chain: what OCOCC_OCC_MERGE_KERNEL=0 runs."""
-    import ctypes
-    from .. import _lib as L
-    from ..tracklet import host_index
-    N, C, M, R, dim, counts = _occ_merge_shapes(L, 'occ_merge', points, occ, counts, use_dim, row_score, flags)
-    L.require_device(points, occ, row_score, flags)
-    if not OCC_MERGE_KERNEL:
-        return occ_merge_aten(points, occ, counts, dim, row_score, flags, drop_observed, score_threshold)
-    dev = points.device
-    D = len(dim)
-    points, occ = points.contiguous(), occ.contiguous()
-    row_score = row_score.contiguous() if row_score is not None else None
-    flags = flags.contiguous() if flags is not None and drop_observed else None
-    tiles = int(L.lib.ococc_occ_select_max_tiles(M, R))
-    start = tile_start = scan = None
-    kept = [0] * R
-    if M:
-        prefix = [0]
-        for c in counts:
-            prefix.append(prefix[-1] + c)
-        start = host_index(prefix, dev)
-        tile_start = L.empty((R + 1,), torch.int64, dev)
-        tile_counts = L.empty((tiles,), torch.int32, dev)
-        row_counts = L.empty((R,), torch.int64, dev)
-        L.check(L.lib.ococc_occ_merge_count(L.ptr(occ), M, L.ptr(start), R, L.ptr(row_score), L.ptr(flags),
-                                            int(flags is not None), float(score_threshold), L.ptr(tile_start),
-                                            L.ptr(tile_counts), tiles, L.ptr(row_counts), L.stream()), 'occ_merge_count')
-        scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts
-        kept = [int(v) for v in row_counts.tolist()]   # the one read-back
-        if min(kept) < 0:
-            raise L.OcoccError(f'occ_merge: start is not an ascending table inside [0, {M}]')
-    K = sum(kept)
-    merged = L.empty((N + K, D + 2), torch.float32, dev)
-    L.check(L.lib.ococc_occ_merge_fill(L.ptr(points), N, C, (ctypes.c_int32 * D)(*dim), D, L.ptr(occ), M, L.ptr(start),
-                                       L.ptr(tile_start), R, L.ptr(row_score), L.ptr(flags), int(flags is not None),
-                                       float(score_threshold), L.ptr(scan), tiles, L.ptr(merged), K, L.stream()),
-            'occ_merge_fill')
-    return merged, kept
+    return _occ_merge(points, occ, counts, None, use_dim, row_score, flags, drop_observed, score_threshold)
 
 
 def occ_merge_aten(points, occ, counts, use_dim=(0, 1, 2, 3, 4), row_score=None, flags=None, drop_observed=False,
@@ -680,7 +658,7 @@ def occ_merge_aten(points, occ, counts, use_dim=(0, 1, 2, 3, 4), row_score=None,
     index, zero / one columns and two ``cat``.  What OCOCC_OCC_MERGE_KERNEL=0 selects and what the kernels are timed
     against."""
     from .. import _lib as L
-    N, C, M, R, dim, counts = _occ_merge_shapes(L, 'occ_merge_aten', points, occ, counts, use_dim, row_score, flags)
+    N, C, M, R, dim, counts, _ = _occ_merge_shapes(L, 'occ_merge_aten', points, occ, counts, use_dim, row_score, flags)
     dev = points.device
     D = len(dim)
     head = torch.cat([points[:, list(dim)], points.new_zeros((N, 2))], 1)
@@ -694,24 +672,6 @@ def occ_merge_aten(points, occ, counts, use_dim=(0, 1, 2, 3, 4), row_score=None,
     tail = torch.cat([occ[keep, :3], occ.new_zeros((int(keep.sum()), D - 3)), score[keep][:, None]], 1)
     tail = torch.cat([tail, torch.ones_like(tail[:, :1])], 1)
     return torch.cat([head, tail], 0), torch.bincount(row[keep], minlength=R).tolist()
-
-
-MERGE_MAX_FRAMES = 65535     # the limit of scene_rows.scene_steps_rows
-
-
-def _occ_merge_frames_shapes(L, what, points, cloud_sizes, occ, counts, frame_rows, use_dim, row_score, flags):
-    """_occ_merge_shapes and what the frames add: (N, C, M, R, use_dim, counts, cloud_sizes, frame_rows), or OcoccError"""
-    N, C, M, R, dim, counts = _occ_merge_shapes(L, what, points, occ, counts, use_dim, row_score, flags)
-    sizes, frame_rows = [int(v) for v in cloud_sizes], [int(v) for v in frame_rows]
-    F = len(sizes)
-    if F > MERGE_MAX_FRAMES:
-        raise L.OcoccError(f'{what}: {F} clouds, at most {MERGE_MAX_FRAMES} per call')
-    if any(s < 0 for s in sizes) or sum(sizes) != N:
-        raise L.OcoccError(f'{what}: cloud_sizes {sizes if F <= 8 else sizes[:8] + ["..."]} must be >= 0 and sum to the {N} points given')
-    if len(frame_rows) != R or any(not 0 <= f < F for f in frame_rows):
-        raise L.OcoccError(f'{what}: frame_rows must hold the cloud 0..{F - 1} of each of the {R} rows of counts, got '
-                           f'{len(frame_rows)} values' + (f' from {min(frame_rows)} to {max(frame_rows)}' if frame_rows else ''))
-    return N, C, M, R, dim, counts, sizes, frame_rows
 
 
 def _prefix(values):
@@ -751,48 +711,66 @@ def occ_merge_frames(points, cloud_sizes, occ, counts, frame_rows, use_dim=(0, 1
 
     Reported before any launch (OcoccError): what occ_merge reports, cloud_sizes that hold a negative or do not sum to N,
     more than 65535 clouds, frame_rows of another length than counts or outside 0..F-1."""
+    return _occ_merge(points, occ, counts, (cloud_sizes, frame_rows), use_dim, row_score, flags, drop_observed, score_threshold)
+
+
+def _occ_merge(points, occ, counts, frames, use_dim, row_score, flags, drop_observed, score_threshold):
+    """the body of occ_merge (``frames`` None: the table that goes up is the cell prefix, R + 1 integers) and
+    occ_merge_frames (``frames`` = (cloud_sizes, frame_rows): five tables in one copy, the ``_frames`` exports, the
+    segment offsets in the result)"""
     import ctypes
     from .. import _lib as L
     from ..scene_rows import frame_major
-    from ..tracklet import host_index_many
-    N, C, M, R, dim, counts, sizes, frame_rows = _occ_merge_frames_shapes(
-        L, 'occ_merge_frames', points, cloud_sizes, occ, counts, frame_rows, use_dim, row_score, flags)
+    from ..tracklet import host_index, host_index_many
+    what = 'occ_merge' if frames is None else 'occ_merge_frames'
+    N, C, M, R, dim, counts, frames = _occ_merge_shapes(L, what, points, occ, counts, use_dim, row_score, flags, frames)
     L.require_device(points, occ, row_score, flags)
     if not OCC_MERGE_KERNEL:
-        return occ_merge_frames_aten(points, sizes, occ, counts, frame_rows, dim, row_score, flags, drop_observed,
+        if frames is None:
+            return occ_merge_aten(points, occ, counts, dim, row_score, flags, drop_observed, score_threshold)
+        return occ_merge_frames_aten(points, frames[0], occ, counts, frames[1], dim, row_score, flags, drop_observed,
                                      score_threshold)
     dev = points.device
-    D, F = len(dim), len(sizes)
+    D = len(dim)
     points, occ = points.contiguous(), occ.contiguous()
     row_score = row_score.contiguous() if row_score is not None else None
     flags = flags.contiguous() if flags is not None and drop_observed else None
     tiles = int(L.lib.ococc_occ_select_max_tiles(M, R))
-    tab = [None] * 5
+    tab = [None] * (1 if frames is None else 5)   # the cell prefix; frames: and order, row frames, cloud prefix, firsts
+    if M and frames is None:
+        tab = [host_index(_prefix(counts), dev)]
+    elif M:
+        order, first = frame_major(frames[1], len(frames[0]))
+        tab = host_index_many([_prefix(counts), order, frames[1], _prefix(frames[0]), first], dev)
+    # what the ``_frames`` exports take more: order and row frames after the prefix, the clouds after R
+    start, rows_by_frame = L.ptr(tab[0]), [L.ptr(t) for t in tab[1:3]]
+    clouds = [] if frames is None else [L.ptr(tab[3]), L.ptr(tab[4]), len(frames[0])]
+    score = (L.ptr(row_score), L.ptr(flags), int(flags is not None), float(score_threshold))
     tile_start = scan = None
     kept = [0] * R
     if M:
-        order, first = frame_major(frame_rows, F)
-        tab = host_index_many([_prefix(counts), order, frame_rows, _prefix(sizes), first], dev)
         tile_start = L.empty((R + 1,), torch.int64, dev)
         tile_counts = L.empty((tiles,), torch.int32, dev)
         row_counts = L.empty((R,), torch.int64, dev)
-        L.check(L.lib.ococc_occ_merge_frames_count(
-            L.ptr(occ), M, L.ptr(tab[0]), L.ptr(tab[1]), L.ptr(tab[2]), R, L.ptr(tab[3]), L.ptr(tab[4]), F, N,
-            L.ptr(row_score), L.ptr(flags), int(flags is not None), float(score_threshold), L.ptr(tile_start),
-            L.ptr(tile_counts), tiles, L.ptr(row_counts), L.stream()), 'occ_merge_frames_count')
+        L.check(getattr(L.lib, f'ococc_{what}_count')(
+            L.ptr(occ), M, start, *rows_by_frame, R, *clouds, *([] if frames is None else [N]), *score, L.ptr(tile_start),
+            L.ptr(tile_counts), tiles, L.ptr(row_counts), L.stream()), f'{what}_count')
         scan = torch.cumsum(tile_counts, 0, dtype=torch.int64) - tile_counts
         kept = [int(v) for v in row_counts.tolist()]   # the one read-back
+        if min(kept) < 0 and frames is None:
+            raise L.OcoccError(f'occ_merge: start is not an ascending table inside [0, {M}]')
         if min(kept) < 0:
             raise L.OcoccError('occ_merge_frames: the tables failed the check on the device: start ascending inside '
-                               f'[0, {M}], order inside [0, {R}), frames inside [0, {F}) and non-decreasing along the '
-                               f'order, cloud_start ascending from 0 to {N}')
+                               f'[0, {M}], order inside [0, {R}), frames inside [0, {len(frames[0])}) and non-decreasing '
+                               f'along the order, cloud_start ascending from 0 to {N}')
     K = sum(kept)
     merged = L.empty((N + K, D + 2), torch.float32, dev)
-    L.check(L.lib.ococc_occ_merge_frames_fill(
-        L.ptr(points), N, C, (ctypes.c_int32 * D)(*dim), D, L.ptr(occ), M, L.ptr(tab[0]), L.ptr(tab[1]), L.ptr(tab[2]),
-        L.ptr(tile_start), R, L.ptr(tab[3]), L.ptr(tab[4]), F, L.ptr(row_score), L.ptr(flags), int(flags is not None),
-        float(score_threshold), L.ptr(scan), tiles, L.ptr(merged), K, L.stream()), 'occ_merge_frames_fill')
-    return merged, merged_offsets(sizes, frame_rows, kept), kept
+    L.check(getattr(L.lib, f'ococc_{what}_fill')(
+        L.ptr(points), N, C, (ctypes.c_int32 * D)(*dim), D, L.ptr(occ), M, start, *rows_by_frame, L.ptr(tile_start), R,
+        *clouds, *score, L.ptr(scan), tiles, L.ptr(merged), K, L.stream()), f'{what}_fill')
+    if frames is None:
+        return merged, kept
+    return merged, merged_offsets(frames[0], frames[1], kept), kept
 
 
 def occ_merge_frames_aten(points, cloud_sizes, occ, counts, frame_rows, use_dim=(0, 1, 2, 3, 4), row_score=None, flags=None,
@@ -801,8 +779,8 @@ def occ_merge_frames_aten(points, cloud_sizes, occ, counts, frame_rows, use_dim=
     the cells, scores and flags of the frame's rows, and one ``cat``.  What OCOCC_OCC_MERGE_KERNEL=0 selects and what the
     kernels are timed against."""
     from .. import _lib as L
-    N, C, M, R, dim, counts, sizes, frame_rows = _occ_merge_frames_shapes(
-        L, 'occ_merge_frames_aten', points, cloud_sizes, occ, counts, frame_rows, use_dim, row_score, flags)
+    N, C, M, R, dim, counts, (sizes, frame_rows) = _occ_merge_shapes(
+        L, 'occ_merge_frames_aten', points, occ, counts, use_dim, row_score, flags, (cloud_sizes, frame_rows))
     cloud, cell = _prefix(sizes), _prefix(counts)
     parts, kept = [], [0] * R
     for f in range(len(sizes)):

@@ -615,7 +615,9 @@ class TrackletRoIHeadOCC(nn.Module):
         ``merged_counts``, the survivors per input row as a list of int on the host.  The score of a row is what
         tools/online_raw.py writes into column 3 of its files: where(valid, refined score, input score) as f32.  Without
         ``merged`` nothing of this is launched and the keys are absent.  A frame without boxes (n == 0) with ``merged`` is
-        not stepped: every key of the step is empty and ``points_merged`` is the cloud with its two zero columns.
+        not stepped: every key of the step is empty and ``points_merged`` is the cloud with its two zero columns.  Without
+        ``merged`` n == 0 returns empty tensors for every key, launches nothing and leaves the state as it is; a slot's
+        origin is stored once the rows are built, so a refused step leaves none behind (the chunked call's rules).
 
         Reported on the host before anything is launched: what simple_test_step reports, a pose that is not 4x4 or not
         finite (OcoccError), a slot in mid-tracklet without an origin -- it was stepped through simple_test_step
@@ -623,108 +625,31 @@ class TrackletRoIHeadOCC(nn.Module):
         (OcoccError)."""
         import numpy as np
         from . import _lib as L
-        from .scene_rows import scene_step_rows
-        from .tracklet import host_index
         if self.training:
             raise RuntimeError('simple_test_scene_step is inference only: call .eval() first')
         merged_cfg = None
         if merged is not None and merged is not False:
-            merged_cfg, occ = self.online_merged_cfg(merged), True
-            if points.dim() != 2 or max(merged_cfg['use_dim']) >= points.size(1):
-                raise L.OcoccError(f'merged: use_dim {merged_cfg["use_dim"]} of a cloud {tuple(points.shape)}')
+            merged_cfg, occ = self._merged_cfg_for(points, merged), True
         pose64 = np.asarray(pose.detach().cpu().numpy() if torch.is_tensor(pose) else pose, dtype=np.float64)
         if pose64.shape != (4, 4) or not np.isfinite(pose64).all():
             raise L.OcoccError(f'pose must be a finite 4x4 ego -> world matrix, got shape {pose64.shape}')
-        slots = state.cache.check_step(slot)
-        first = None                                                    # inverse(pose), if a slot starts here
-        origins = []
-        for s in slots:
-            if state.frames[s] == 0:
-                if first is None:
-                    try:
-                        first = np.linalg.inv(pose64)
-                    except np.linalg.LinAlgError:
-                        raise L.OcoccError('pose is singular: not an ego -> world transform')
-                origins.append(first)
-            elif state.origin[s] is None:
-                raise L.OcoccError(f'slot {s} holds {state.frames[s]} frames and no origin: it was stepped through '
-                                   'simple_test_step, whose caller keeps the fixed frame (reset the slot)')
-            else:
-                origins.append(state.origin[s])
-        L.require_device(points, boxes, scores, labels, state.cache.pos)
-        n, dev = boxes.size(0), boxes.device
-        if len(slots) != n or scores.size(0) != n or labels.size(0) != n:
-            raise L.OcoccError(f'{len(slots)} slots, {scores.size(0)} scores, {labels.size(0)} labels for {n} boxes')
-        if n == 0 and merged_cfg is not None:                          # a frame without tracks: its cloud, nothing to step
-            from .occ.occ_ops import occ_merge
-            feats = boxes.new_zeros((0, self.bbox_head.roi_feature_channels))
-            out = dict(boxes=boxes.new_zeros((0, 7)), scores=scores.new_zeros((0,)), labels=labels.new_zeros((0,)),
-                       valid=torch.zeros((0,), dtype=torch.bool, device=dev), fused_roi_feats=feats, ori_roi_feats=feats,
-                       occ_ego=boxes.new_zeros((0, 4)), occ_flags=torch.zeros((0,), dtype=torch.uint8, device=dev),
-                       occ_counts=[], boxes_ego=boxes.new_zeros((0, 7)), num_points=torch.zeros((0,), dtype=torch.long))
-            out['points_merged'], out['merged_counts'] = occ_merge(points, out['occ_ego'], [], merged_cfg['use_dim'])
-            return out
-        cfg = dict(self.SCENE_ROWS_DEFAULTS, **(self.test_cfg.get('scene_rows', None) or {}))
-        for s in slots:
-            if state.frames[s] == 0:
-                state.origin[s] = first
-        to_fixed = np.stack([o @ pose64 for o in origins]) if n else np.zeros((0, 4, 4))
-        mats = host_index(np.stack([to_fixed[:, :3].reshape(n, 12), np.linalg.inv(to_fixed)[:, :3].reshape(n, 12)]), dev,
-                          dtype=torch.float64)                         # [2, n, 12]: M and inverse(M), one copy
-        fixed_boxes = self._boxes_through(boxes, mats[0])
-        xyz, feats, row, counts = scene_step_rows(
-            points, boxes, scores, transforms=mats[0].float(), extra_width=cfg['extra_width'], attr_dims=cfg['attr_dims'],
-            point_cloud_range=cfg['point_cloud_range'], max_points=cfg['max_points'], deco_boxes=fixed_boxes)
-        kw = dict(occ=True, occ_transforms=mats[1].float()) if occ else {}
-        out = self.simple_test_step(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois, tune=tune, **kw)
-        if occ:
-            out['occ_ego'] = out.pop('occ')
-        out['boxes_ego'] = torch.where(out['valid'].to(dev).bool()[:, None], self._boxes_through(out['boxes'], mats[1]),
-                                       boxes[:, :7])
-        out['num_points'] = counts
-        if merged_cfg is not None:
-            from .occ.occ_ops import occ_merge
-            row_score = torch.where(out['valid'].to(dev).bool(), out['scores'].float(), scores.float())
-            out['points_merged'], out['merged_counts'] = occ_merge(
-                points, out['occ_ego'], out['occ_counts'], merged_cfg['use_dim'], row_score=row_score,
-                flags=out['occ_flags'], drop_observed=merged_cfg['drop_observed'],
-                score_threshold=merged_cfg['score_threshold'])
-        return out
+        return self._simple_test_scene_rows(points, None, pose64[None], boxes, scores, labels, slot, state, gt_rois, occ,
+                                            tune, merged_cfg)
 
-    @torch.no_grad()
-    def simple_test_scene_steps(self, points, cloud_sizes, poses, boxes, scores, labels, frame_rows, slot_rows, state,
-                                gt_rois=None, occ=False, tune=None):
-        """simple_test_steps from what SEVERAL sensor frames bring -- a track confirmed after three hits comes with three
-        boxes in three clouds under three poses: ``points`` [N, >= 3 + attr] f32, the F scene clouds concatenated, each in its
-        own ego frame, ``cloud_sizes`` their F lengths (ints on the host), ``poses`` [F, 4, 4] the ego -> world pose of each
-        cloud (numpy or torch).  A row is one (tracklet, frame) exactly as in simple_test_steps: ``boxes`` [n, 7] each in the
-        ego frame of the row's own cloud, ``scores`` [n], ``labels`` [n], ``frame_rows`` the cloud 0..F-1 of every row,
-        ``slot_rows`` its slot; the rows of a slot are consecutive and in frame order, so within a slot's run ``frame_rows``
-        is strictly increasing (gaps are fine: a track may miss a frame).
+    def _merged_cfg_for(self, points, merged):
+        """online_merged_cfg(merged), and its use_dim against the cloud's columns: what the merged forms check first"""
+        from . import _lib as L
+        cfg = self.online_merged_cfg(merged)
+        if points.dim() != 2 or max(cfg['use_dim']) >= points.size(1):
+            raise L.OcoccError(f'merged: use_dim {cfg["use_dim"]} of a cloud {tuple(points.shape)}')
+        return cfg
 
-        Origins as in simple_test_scene_step: a slot whose frame counter is 0 takes inverse(pose of its FIRST row's cloud),
-        any other slot ``state.origin[slot]``; they are stored only after every host check has passed.  Row i gets
-        M_i = float32(origin[slot_i] @ poses[frame_rows[i]]) (float64 on the host; M and inverse(M) of all rows go up in
-        one copy), the boxes go through M_i, scene_rows.scene_steps_rows builds the rows of ALL clouds with one count launch,
-        one read-back and one fill launch (test_cfg.scene_rows as in the single step), and simple_test_steps runs on them.
-
-        Returns the keys of simple_test_scene_step for the n rows in input order: the dict of simple_test_steps,
-        ``boxes_ego`` (rows with valid == False their input box bit for bit), ``num_points`` [n] i64 on the host (uncapped),
-        and with ``occ=True`` ``occ_ego`` (each row's cells in the ego frame of ITS cloud), ``occ_flags``, ``occ_counts``.
-        ``tune`` passes through.  n == 0 returns empty tensors for every key, launches nothing and leaves the state as it is.
-
-        The occupancy-enhanced clouds of the F frames of such a call come from simple_test_scene_steps_merged, which runs
-        this method with ``occ=True`` and merges all F clouds with one count launch, one read-back and one fill launch.
-
-        Reported on the host before anything is launched: what simple_test_steps reports, poses that are not [F, 4, 4], not
-        finite or singular, cloud_sizes of another length than F, frame_rows outside 0..F-1, repeating or going back inside
-        a slot's run, a slot in mid-tracklet without an origin (OcoccError), training mode (RuntimeError)."""
+    @staticmethod
+    def _scene_frames(poses, cloud_sizes, frame_rows):
+        """the frames arguments of a chunked scene call on the host: (poses as float64 [F, 4, 4] -- finite, one per
+        cloud, or OcoccError --, (cloud_sizes, frame_rows) as lists of int)"""
         import numpy as np
         from . import _lib as L
-        from .scene_rows import scene_steps_rows
-        from .tracklet import host_index
-        if self.training:
-            raise RuntimeError('simple_test_scene_steps is inference only: call .eval() first')
         pose64 = np.asarray(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float64)
         sizes, frame_rows = [int(v) for v in cloud_sizes], [int(v) for v in frame_rows]
         F = len(sizes)
@@ -732,7 +657,28 @@ class TrackletRoIHeadOCC(nn.Module):
             pose64 = pose64.reshape(0, 4, 4)
         if pose64.shape != (F, 4, 4) or not np.isfinite(pose64).all():
             raise L.OcoccError(f'poses must be finite ego -> world matrices [F = {F}, 4, 4], one per cloud, got shape {pose64.shape}')
-        slots, offsets, _ = state.cache.check_steps(slot_rows)
+        return pose64, (sizes, frame_rows)
+
+    def _simple_test_scene_rows(self, points, frames, pose64, boxes, scores, labels, slot, state, gt_rois, occ, tune,
+                                merged_cfg):
+        """the body of simple_test_scene_step (``frames`` None: one cloud under pose64 [1, 4, 4], every row its slot's
+        first row, the one-cloud operators and simple_test_step) and of simple_test_scene_steps(_merged) (``frames`` =
+        (cloud_sizes, frame_rows) as lists of int, pose64 [F, 4, 4]: the frames operators and simple_test_steps): the host
+        checks in one order, the origins, the matrices in one copy, the rows, the step, the ego-frame keys, and with
+        ``merged_cfg`` the merged cloud(s).  Nothing is launched and the state is untouched until every host check has
+        passed; the origins are stored once the rows are built."""
+        import numpy as np
+        from . import _lib as L
+        from .occ.occ_ops import occ_merge, occ_merge_frames
+        from .scene_rows import scene_step_rows, scene_steps_rows
+        from .tracklet import host_index
+        F = len(pose64)
+        if frames is None:
+            slots = state.cache.check_step(slot)
+            offsets = frame_rows = [0] * len(slots)
+        else:
+            sizes, frame_rows = frames
+            slots, offsets, _ = state.cache.check_steps(slot)
         n = len(slots)
         if len(frame_rows) != n or any(not 0 <= f < F for f in frame_rows):
             raise L.OcoccError(f'frame_rows must hold the cloud 0..{F - 1} of each of the {n} rows, got {len(frame_rows)} values'
@@ -760,11 +706,11 @@ class TrackletRoIHeadOCC(nn.Module):
                 origins.append(state.origin[s])
         if boxes.size(0) != n or scores.size(0) != n or labels.size(0) != n:
             raise L.OcoccError(f'{n} slots, {scores.size(0)} scores, {labels.size(0)} labels for {boxes.size(0)} boxes')
-        if points.dim() != 2 or sum(sizes) != points.size(0) or min(sizes, default=0) < 0:
+        if frames is not None and (points.dim() != 2 or sum(sizes) != points.size(0) or min(sizes, default=0) < 0):
             raise L.OcoccError(f'cloud_sizes must be >= 0 and sum to the points given, got {sum(sizes)} for {tuple(points.shape)}')
         L.require_device(points, boxes, scores, labels, state.cache.pos)
         dev = boxes.device
-        if n == 0:
+        if n == 0:                                                      # nothing to step: every key empty, no launch
             feats = boxes.new_zeros((0, self.bbox_head.roi_feature_channels))
             out = dict(boxes=boxes.new_zeros((0, 7)), scores=scores.new_zeros((0,)), labels=labels.new_zeros((0,)),
                        valid=torch.zeros((0,), dtype=torch.bool, device=dev), fused_roi_feats=feats, ori_roi_feats=feats,
@@ -772,32 +718,78 @@ class TrackletRoIHeadOCC(nn.Module):
             if occ:
                 out.update(occ_ego=boxes.new_zeros((0, 4)), occ_flags=torch.zeros((0,), dtype=torch.uint8, device=dev),
                            occ_counts=[])
-            return out
-        cfg = dict(self.SCENE_ROWS_DEFAULTS, **(self.test_cfg.get('scene_rows', None) or {}))
-        if occ:
-            self.online_occ_cfg()                                       # (a wrong test_cfg.online_occ: before the origins)
-        to_fixed = np.stack([o @ pose64[f] for o, f in zip(origins, frame_rows)])
-        try:
-            from_fixed = np.linalg.inv(to_fixed)
-        except np.linalg.LinAlgError:
-            raise L.OcoccError('a pose is singular: not an ego -> world transform')
-        mats = host_index(np.stack([to_fixed[:, :3].reshape(n, 12), from_fixed[:, :3].reshape(n, 12)]), dev,
-                          dtype=torch.float64)                         # [2, n, 12]: M and inverse(M), one copy
-        fixed_boxes = self._boxes_through(boxes, mats[0])
-        xyz, feats, row, counts = scene_steps_rows(
-            points, sizes, boxes, scores, frame_rows, transforms=mats[0].float(), extra_width=cfg['extra_width'],
-            attr_dims=cfg['attr_dims'], point_cloud_range=cfg['point_cloud_range'], max_points=cfg['max_points'],
-            deco_boxes=fixed_boxes)
-        for s, o in started.items():                                    # (every host check has passed)
-            state.origin[s] = o
-        kw = dict(occ=True, occ_transforms=mats[1].float()) if occ else {}
-        out = self.simple_test_steps(xyz, feats, row, fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois, tune=tune, **kw)
-        if occ:
-            out['occ_ego'] = out.pop('occ')
-        out['boxes_ego'] = torch.where(out['valid'].to(dev).bool()[:, None], self._boxes_through(out['boxes'], mats[1]),
-                                       boxes[:, :7])
-        out['num_points'] = counts
+        else:
+            cfg = dict(self.SCENE_ROWS_DEFAULTS, **(self.test_cfg.get('scene_rows', None) or {}))
+            if occ:
+                self.online_occ_cfg()                                   # (a wrong test_cfg.online_occ: before the origins)
+            to_fixed = np.stack([o @ pose64[f] for o, f in zip(origins, frame_rows)])
+            try:
+                from_fixed = np.linalg.inv(to_fixed)
+            except np.linalg.LinAlgError:
+                raise L.OcoccError('a pose is singular: not an ego -> world transform')
+            mats = host_index(np.stack([to_fixed[:, :3].reshape(n, 12), from_fixed[:, :3].reshape(n, 12)]), dev,
+                              dtype=torch.float64)                     # [2, n, 12]: M and inverse(M), one copy
+            fixed_boxes = self._boxes_through(boxes, mats[0])
+            rows_kw = dict(transforms=mats[0].float(), extra_width=cfg['extra_width'], attr_dims=cfg['attr_dims'],
+                           point_cloud_range=cfg['point_cloud_range'], max_points=cfg['max_points'], deco_boxes=fixed_boxes)
+            if frames is None:
+                step, rows = self.simple_test_step, scene_step_rows(points, boxes, scores, **rows_kw)
+            else:
+                step, rows = self.simple_test_steps, scene_steps_rows(points, sizes, boxes, scores, frame_rows, **rows_kw)
+            for s, o in started.items():                                # (every host check has passed)
+                state.origin[s] = o
+            kw = dict(occ=True, occ_transforms=mats[1].float()) if occ else {}
+            out = step(*rows[:3], fixed_boxes, scores, labels, slots, state, gt_rois=gt_rois, tune=tune, **kw)
+            if occ:
+                out['occ_ego'] = out.pop('occ')
+            out['boxes_ego'] = torch.where(out['valid'].to(dev).bool()[:, None], self._boxes_through(out['boxes'], mats[1]),
+                                           boxes[:, :7])
+            out['num_points'] = rows[3]
+        if merged_cfg is not None:
+            row_score = torch.where(out['valid'].to(dev).bool(), out['scores'].float(), scores.float())
+            kw = dict(row_score=row_score, flags=out['occ_flags'], drop_observed=merged_cfg['drop_observed'],
+                      score_threshold=merged_cfg['score_threshold'])
+            if frames is None:
+                out['points_merged'], out['merged_counts'] = occ_merge(
+                    points, out['occ_ego'], out['occ_counts'], merged_cfg['use_dim'], **kw)
+            else:
+                out['points_merged'], out['merged_offsets'], out['merged_counts'] = occ_merge_frames(
+                    points, sizes, out['occ_ego'], out['occ_counts'], frame_rows, merged_cfg['use_dim'], **kw)
         return out
+
+    @torch.no_grad()
+    def simple_test_scene_steps(self, points, cloud_sizes, poses, boxes, scores, labels, frame_rows, slot_rows, state,
+                                gt_rois=None, occ=False, tune=None):
+        """simple_test_steps from what SEVERAL sensor frames bring -- a track confirmed after three hits comes with three
+        boxes in three clouds under three poses: ``points`` [N, >= 3 + attr] f32, the F scene clouds concatenated, each in its
+        own ego frame, ``cloud_sizes`` their F lengths (ints on the host), ``poses`` [F, 4, 4] the ego -> world pose of each
+        cloud (numpy or torch).  A row is one (tracklet, frame) exactly as in simple_test_steps: ``boxes`` [n, 7] each in the
+        ego frame of the row's own cloud, ``scores`` [n], ``labels`` [n], ``frame_rows`` the cloud 0..F-1 of every row,
+        ``slot_rows`` its slot; the rows of a slot are consecutive and in frame order, so within a slot's run ``frame_rows``
+        is strictly increasing (gaps are fine: a track may miss a frame).
+
+        Origins as in simple_test_scene_step: a slot whose frame counter is 0 takes inverse(pose of its FIRST row's cloud),
+        any other slot ``state.origin[slot]``; they are stored only after every host check has passed.  Row i gets
+        M_i = float32(origin[slot_i] @ poses[frame_rows[i]]) (float64 on the host; M and inverse(M) of all rows go up in
+        one copy), the boxes go through M_i, scene_rows.scene_steps_rows builds the rows of ALL clouds with one count launch,
+        one read-back and one fill launch (test_cfg.scene_rows as in the single step), and simple_test_steps runs on them.
+
+        Returns the keys of simple_test_scene_step for the n rows in input order: the dict of simple_test_steps,
+        ``boxes_ego`` (rows with valid == False their input box bit for bit), ``num_points`` [n] i64 on the host (uncapped),
+        and with ``occ=True`` ``occ_ego`` (each row's cells in the ego frame of ITS cloud), ``occ_flags``, ``occ_counts``.
+        ``tune`` passes through.  n == 0 returns empty tensors for every key, launches nothing and leaves the state as it is.
+
+        The occupancy-enhanced clouds of the F frames of such a call come from simple_test_scene_steps_merged, which runs
+        this call with ``occ=True`` and merges all F clouds with one count launch, one read-back and one fill launch.
+
+        Reported on the host before anything is launched: what simple_test_steps reports, poses that are not [F, 4, 4], not
+        finite or singular, cloud_sizes of another length than F, frame_rows outside 0..F-1, repeating or going back inside
+        a slot's run, a slot in mid-tracklet without an origin (OcoccError), training mode (RuntimeError)."""
+        if self.training:
+            raise RuntimeError('simple_test_scene_steps is inference only: call .eval() first')
+        pose64, frames = self._scene_frames(poses, cloud_sizes, frame_rows)
+        return self._simple_test_scene_rows(points, frames, pose64, boxes, scores, labels, slot_rows, state, gt_rois, occ,
+                                            tune, None)
 
     @torch.no_grad()
     def simple_test_scene_steps_merged(self, points, cloud_sizes, poses, boxes, scores, labels, frame_rows, slot_rows, state,
@@ -820,20 +812,12 @@ class TrackletRoIHeadOCC(nn.Module):
 
         Reported on the host before anything is launched: what simple_test_scene_steps reports, a wrong ``merged`` or
         test_cfg.online_merged (ValueError), a ``use_dim`` beyond the cloud's columns (OcoccError)."""
-        from . import _lib as L
-        from .occ.occ_ops import occ_merge_frames
         if self.training:
             raise RuntimeError('simple_test_scene_steps_merged is inference only: call .eval() first')
-        cfg = self.online_merged_cfg(merged)
-        if points.dim() != 2 or max(cfg['use_dim']) >= points.size(1):
-            raise L.OcoccError(f'merged: use_dim {cfg["use_dim"]} of a cloud {tuple(points.shape)}')
-        out = self.simple_test_scene_steps(points, cloud_sizes, poses, boxes, scores, labels, frame_rows, slot_rows, state,
-                                           gt_rois=gt_rois, occ=True, tune=tune)
-        row_score = torch.where(out['valid'].to(boxes.device).bool(), out['scores'].float(), scores.float())
-        out['points_merged'], out['merged_offsets'], out['merged_counts'] = occ_merge_frames(
-            points, cloud_sizes, out['occ_ego'], out['occ_counts'], frame_rows, cfg['use_dim'], row_score=row_score,
-            flags=out['occ_flags'], drop_observed=cfg['drop_observed'], score_threshold=cfg['score_threshold'])
-        return out
+        merged_cfg = self._merged_cfg_for(points, merged)
+        pose64, frames = self._scene_frames(poses, cloud_sizes, frame_rows)
+        return self._simple_test_scene_rows(points, frames, pose64, boxes, scores, labels, slot_rows, state, gt_rois, True,
+                                            tune, merged_cfg)
 
     def online_chunk(self):
         """test_cfg.online_chunk: the frames simple_test_online feeds per call, an int >= 1 (default 1: single steps)"""

@@ -90,34 +90,7 @@ def scene_step_rows(points, boxes, scores, transforms=None, extra_width=EXTRA_WI
     sorted by (row, point index).  One count launch, one read-back, one fill launch."""
     L.require_device(points, boxes, scores, transforms, deco_boxes)
     n, N, cap = _check_rows(points, boxes, scores, transforms, attr_dims, point_cloud_range, max_points, deco_boxes)
-    dev = points.device
-    points, crop, row_feats, transforms, rng = _row_inputs(points, boxes, scores, transforms, extra_width, point_cloud_range,
-                                                           deco_boxes)
-    A, K = int(attr_dims), row_feats.size(1)
-    counts = torch.zeros((n,), dtype=torch.int64, device=dev)
-    empty = lambda: (torch.zeros((0, 3), dtype=torch.float32, device=dev), torch.zeros((0, A + K), dtype=torch.float32, device=dev),
-                     torch.zeros((0,), dtype=torch.int64, device=dev), counts.cpu())
-    if n == 0 or N == 0:
-        return empty()
-    ws_bytes = int(L.lib.ococc_scene_rows_workspace_bytes(N, n))
-    ws = L.workspace(ws_bytes, dev)
-    L.check(L.lib.ococc_scene_rows_count(L.ptr(points), N, points.size(1), L.ptr(crop), n, L.ptr(transforms), rng,
-                                         L.ptr(counts), L.ptr(ws), ws_bytes, L.stream()), 'scene_rows_count')
-    counts_host = counts.cpu()                                   # the read-back
-    scans = torch.zeros((2, n + 1), dtype=torch.int64)
-    torch.cumsum(counts_host, 0, out=scans[0, 1:])
-    torch.cumsum(counts_host.clamp(max=cap) if cap > 0 else counts_host, 0, out=scans[1, 1:])
-    M = int(scans[1, -1])
-    if M == 0:
-        return empty()
-    scans_dev = scans.to(dev)                                    # (one upload for both)
-    xyz = L.empty((M, 3), torch.float32, dev)
-    feats = L.empty((M, A + K), torch.float32, dev)
-    row = L.empty((M,), torch.int64, dev)
-    L.check(L.lib.ococc_scene_rows_fill(L.ptr(points), N, points.size(1), L.ptr(crop), n, L.ptr(transforms), rng, A,
-                                        L.ptr(row_feats), K, cap, L.ptr(scans_dev[0]), L.ptr(scans_dev[1]), L.ptr(xyz),
-                                        L.ptr(feats), L.ptr(row), L.ptr(ws), ws_bytes, L.stream()), 'scene_rows_fill')
-    return xyz, feats, row, counts_host
+    return _rows(points, boxes, scores, n, N, cap, None, transforms, extra_width, attr_dims, point_cloud_range, deco_boxes)
 
 
 def frame_major(frame_rows, frames):
@@ -161,6 +134,14 @@ def scene_steps_rows(points, cloud_sizes, boxes, scores, frame_rows, transforms=
         raise L.OcoccError(f'frame_rows must hold the cloud 0..{F - 1} of each of the {n} rows, got {len(frame_rows)} values'
                            + (f' from {min(frame_rows)} to {max(frame_rows)}' if frame_rows else ''))
     L.require_device(points, boxes, scores, transforms, deco_boxes)
+    return _rows(points, boxes, scores, n, N, cap, (sizes, frame_rows), transforms, extra_width, attr_dims,
+                 point_cloud_range, deco_boxes)
+
+
+def _rows(points, boxes, scores, n, N, cap, frames, transforms, extra_width, attr_dims, point_cloud_range, deco_boxes):
+    """the body of scene_step_rows (``frames`` None: the one-cloud exports, whose fill pass reads the prefix tables
+    [n + 1] of the counts and of the kept) and scene_steps_rows (``frames`` = (cloud_sizes, frame_rows): the plan, the
+    many-cloud exports, whose fill pass reads every box's total and first output row) over checked arguments"""
     dev = points.device
     points, crop, row_feats, transforms, rng = _row_inputs(points, boxes, scores, transforms, extra_width, point_cloud_range,
                                                            deco_boxes)
@@ -170,24 +151,30 @@ def scene_steps_rows(points, cloud_sizes, boxes, scores, frame_rows, transforms=
                      torch.zeros((0,), dtype=torch.int64, device=dev), counts)
     if n == 0 or N == 0:
         return empty()
-    order, box_offsets = frame_major(frame_rows, F)
-    cloud_offsets = [0] * (F + 1)
-    for f, v in enumerate(sizes):
-        cloud_offsets[f + 1] = cloud_offsets[f] + v
-    max_pts, max_boxes = max(sizes), max(box_offsets[f + 1] - box_offsets[f] for f in range(F))
-    plan = torch.from_numpy(np.array(cloud_offsets + box_offsets + order, dtype=np.int64)).to(dev)   # (one upload)
-    cloud_off, box_off, order_dev = plan[:F + 1], plan[F + 1:2 * F + 2], plan[2 * F + 2:]
-    if order != list(range(n)):                                  # the boxes and what goes with them, grouped by frame
-        crop, row_feats = crop[order_dev], row_feats[order_dev]
-        transforms = None if transforms is None else transforms[order_dev]
+    # one cloud: the boxes stay in the caller's order and the exports take no plan
+    what, order, max_pts, caller_rows = 'scene_rows', slice(None), N, ()
+    head = (L.ptr(points), N, points.size(1), L.ptr(crop), n, L.ptr(transforms), rng)
+    if frames is not None:
+        (sizes, frame_rows), what = frames, 'scene_rows_frames'
+        F = len(sizes)
+        order, box_offsets = frame_major(frame_rows, F)
+        cloud_offsets = [0] * (F + 1)
+        for f, v in enumerate(sizes):
+            cloud_offsets[f + 1] = cloud_offsets[f] + v
+        max_pts, max_boxes = max(sizes), max(box_offsets[f + 1] - box_offsets[f] for f in range(F))
+        plan = torch.from_numpy(np.array(cloud_offsets + box_offsets + order, dtype=np.int64)).to(dev)   # (one upload)
+        cloud_off, box_off, order_dev = plan[:F + 1], plan[F + 1:2 * F + 2], plan[2 * F + 2:]
+        if order != list(range(n)):                              # the boxes and what goes with them, grouped by frame
+            crop, row_feats = crop[order_dev], row_feats[order_dev]
+            transforms = None if transforms is None else transforms[order_dev]
+        caller_rows = (L.ptr(order_dev),)
+        head = (L.ptr(points), N, points.size(1), L.ptr(cloud_off), L.ptr(crop), n, L.ptr(box_off), F, max_pts, max_boxes,
+                L.ptr(transforms), rng)
     counts_dev = torch.zeros((n,), dtype=torch.int64, device=dev)
     ws_bytes = int(L.lib.ococc_scene_rows_workspace_bytes(max_pts, n))
     ws = L.workspace(ws_bytes, dev)
-    head = (L.ptr(points), N, points.size(1), L.ptr(cloud_off), L.ptr(crop), n, L.ptr(box_off), F, max_pts, max_boxes,
-            L.ptr(transforms), rng)
-    L.check(L.lib.ococc_scene_rows_frames_count(*head, L.ptr(counts_dev), L.ptr(ws), ws_bytes, L.stream()),
-            'scene_rows_frames_count')
-    totals = counts_dev.cpu().numpy()                            # the read-back (frame-major)
+    L.check(getattr(L.lib, f'ococc_{what}_count')(*head, L.ptr(counts_dev), L.ptr(ws), ws_bytes, L.stream()), f'{what}_count')
+    totals = counts_dev.cpu().numpy()                            # the read-back (frames: frame-major)
     per_row = counts.numpy()                                     # (the same memory: numpy for the host's few integers)
     per_row[order] = totals                                      # the caller's order
     kept = np.minimum(per_row, cap) if cap > 0 else per_row
@@ -195,11 +182,19 @@ def scene_steps_rows(points, cloud_sizes, boxes, scores, frame_rows, transforms=
     M = int(ends[-1])
     if M == 0:
         return empty()
-    scans_dev = torch.from_numpy(np.stack([totals, (ends - kept)[order]])).to(dev)   # (one upload for both)
+    # what the fill pass reads per box -- one cloud: the prefix tables [n + 1] of the counts and of the kept; frames: the
+    # total and the first output row of every box, frame-major
+    if frames is None:
+        scans = np.zeros((2, n + 1), dtype=np.int64)
+        np.cumsum(totals, out=scans[0, 1:])
+        scans[1, 1:] = ends
+    else:
+        scans = np.stack([totals, (ends - kept)[order]])
+    scans_dev = torch.from_numpy(scans).to(dev)                  # (one upload for both)
     xyz = L.empty((M, 3), torch.float32, dev)
     feats = L.empty((M, A + K), torch.float32, dev)
     row = L.empty((M,), torch.int64, dev)
-    L.check(L.lib.ococc_scene_rows_frames_fill(*head, A, L.ptr(row_feats), K, L.ptr(order_dev), cap, L.ptr(scans_dev[0]),
-                                               L.ptr(scans_dev[1]), M, L.ptr(xyz), L.ptr(feats), L.ptr(row), L.ptr(ws),
-                                               ws_bytes, L.stream()), 'scene_rows_frames_fill')
+    L.check(getattr(L.lib, f'ococc_{what}_fill')(
+        *head, A, L.ptr(row_feats), K, *caller_rows, cap, L.ptr(scans_dev[0]), L.ptr(scans_dev[1]),
+        *(() if frames is None else (M,)), L.ptr(xyz), L.ptr(feats), L.ptr(row), L.ptr(ws), ws_bytes, L.stream()), f'{what}_fill')
     return xyz, feats, row, counts

@@ -396,6 +396,48 @@ def test_head_scene_step_matches_the_existing_operators(dev, model):
         assert worst[key] <= 2 * d0[key] + 1e-7, (key, worst[key], d0[key])
 
 
+def test_single_step_refusals_and_empty_call_leave_the_state_alone(dev, model):
+    """The single step behaves as the chunked call does (one host body under both): a call without boxes returns the empty
+    dict of the chunked call -- its keys, with ``occ=True`` its three more, every value of length 0 -- and launches nothing;
+    a step refused after its slot check (a float64 cloud, which scene_step_rows reports; a wrong test_cfg.online_occ, which
+    is reported before any launch) leaves origins, frame counters and the K/V cache as they were; a plain step of two
+    boxes on the same state then succeeds and sets both origins."""
+    rh = model.roi_head
+    state = rh.online_begin(2, dev, cap=2)
+    boxes = torch.tensor([[10, 0, 0, 2, 4.5, 1.6, 0.1], [10, 10, 0, 2, 4.5, 1.6, -0.2]], device=dev)
+    g = np.random.default_rng(8)
+    xyz = np.concatenate([boxes.cpu().numpy()[[0, 0, 0, 0, 1, 1, 1, 1], :3] + g.uniform(0.1, 0.6, (8, 3)), g.random((8, 2))], 1)
+    points = torch.from_numpy(xyz.astype(np.float32)).to(dev)
+    scores, labels, pose = torch.tensor([0.5, 0.6], device=dev), torch.zeros(2, dtype=torch.long, device=dev), ego_pose(1)
+    snapshot = lambda: (list(state.frames), list(state.origin), state.cache.pos.clone(), [t.clone() for t in state.cache.k + state.cache.v])
+
+    def unchanged(before):
+        now = snapshot()
+        return (now[0] == before[0] and now[1] == before[1] == [None, None] and torch.equal(now[2], before[2])
+                and all(torch.equal(a, b) for a, b in zip(now[3], before[3])))
+
+    before = snapshot()
+    sizes, poses = [8], pose[None]
+    for occ in (False, True):                                               # (c)
+        want = rh.simple_test_scene_steps(points, sizes, poses, boxes[:0], scores[:0], labels[:0], [], [], state, occ=occ)
+        got = rh.simple_test_scene_step(points, pose, boxes[:0], scores[:0], labels[:0], [], state, occ=occ)
+        assert set(got) == set(want) and ('occ_ego' in got) == occ and all(len(v) == 0 for v in got.values())
+        assert got['boxes_ego'].shape == (0, 7) and unchanged(before)
+    with pytest.raises(L.OcoccError, match='float32'):                      # (a)
+        rh.simple_test_scene_step(points.double(), pose, boxes[:1], scores[:1], labels[:1], [0], state)
+    assert state.origin[0] is None and unchanged(before)
+    rh.test_cfg['online_occ'] = dict(chunk=0)                               # (b)
+    try:
+        with pytest.raises(ValueError, match='online_occ'):
+            rh.simple_test_scene_step(points, pose, boxes[:1], scores[:1], labels[:1], [0], state, occ=True)
+    finally:
+        del rh.test_cfg['online_occ']
+    assert state.origin[0] is None and state.frames[0] == 0 and unchanged(before)
+    out = rh.simple_test_scene_step(points, pose, boxes, scores, labels, [0, 1], state)
+    assert out['num_points'].tolist() == [4, 4] and state.frames == [1, 1]
+    assert all(np.array_equal(o, np.linalg.inv(pose)) for o in state.origin)
+
+
 def test_replay_of_a_synthetic_raw_tree(dev, model, tmp_path):
     """G: make_synthetic_raw's tree (1 segment, 2 objects and one false positive above every point, 6 frames, 500 background
     points) replayed through tools/online_raw.py: one output object per input object with its id and timestamp, finite

@@ -179,6 +179,30 @@ def test_scene_step_reports_on_the_host(model):
         model.eval()
 
 
+def test_scene_step_reports_lengths_before_the_device(model):
+    """the order of host checks is the chunked call's: wrong lengths are reported before CPU tensors, and no refusal --
+    lengths, device, a singular pose, a bad slot -- leaves anything in the state"""
+    from objectcentricocccompletion_amd import _lib as L
+    rh = model.roi_head
+    state = rh.online_begin(3, 'cpu', cap=4)
+    state.cache.pos_host[1], state.origin[1] = 2, np.eye(4)
+    origin, frames = list(state.origin), list(state.frames)
+    same = lambda: state.frames == frames and all(a is b for a, b in zip(state.origin, origin))
+    for bad in (dict(scores=torch.ones(3)), dict(labels=torch.zeros(1, dtype=torch.long)), dict(boxes=torch.ones(3, 7))):
+        with pytest.raises(L.OcoccError, match=r'2 slots, \d scores, \d labels for \d boxes'):
+            rh.simple_test_scene_step(**dict(_scene_frame(2), **bad), slot=[0, 1], state=state)
+        assert same()
+    with pytest.raises(L.OcoccError, match='CPU tensor'):
+        rh.simple_test_scene_step(**_scene_frame(2), slot=[0, 1], state=state)
+    assert same()
+    with pytest.raises(L.OcoccError, match='singular'):
+        rh.simple_test_scene_step(**dict(_scene_frame(2), pose=np.diag([1.0, 1.0, 0.0, 1.0])), slot=[1, 0], state=state)
+    assert same()
+    with pytest.raises(L.OcoccError, match='outside'):
+        rh.simple_test_scene_step(**_scene_frame(2), slot=[0, 3], state=state)
+    assert same()
+
+
 def test_replay_tool_arguments_and_cache_choice(model):
     import importlib.util
     from objectcentricocccompletion_amd import _lib as L
